@@ -11,12 +11,17 @@ the path's one exchange step: an RCCL all-gather of the per-rank ddG tables.
 `python -m torch.distributed.run --nproc-per-node N` (one process per GPU, RCCL); the line then carries a `collective`
 block proving what the process group saw (`ranks_seen` = all_reduce of ones, one device id per rank).
 `--scaling strong` runs BASELINE.json configs[3] instead (300 Megascale-like proteins / 200 000 listed mutants, FIXED total
-work sharded over the ranks by LPT, timed with and without the all-gather of the ddG tables).
+work sharded over the ranks by LPT, timed with the all-gather of the ddG tables, and with `--full` also without it).
 
-Prints ONE JSON line on rank 0: whole-job preds/s + `roofline` (dominant kernel, HIP-event timed inside the
-timed region, BOTH roofs: algorithmic HBM bytes / 8 TB/s and executed MFMA flops / peak, `bound` = the binding one) +
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times exactly --steps steps and prints whole-job preds/s
+(`value`, `ms_per_step`, the per-step spread). `--full` adds everything else, measured around the same timed steps:
+`roofline` (dominant kernel, HIP-event timed inside the timed region, BOTH roofs: algorithmic HBM bytes / 8 TB/s and
+executed MFMA flops / peak, `bound` = the binding one), per-kernel times, the clock under load, the timings without the
+exchange (N > 1, strong scaling), the gather microbench, single-protein latency, the other precisions, the end-to-end leg and
 `cpu_baseline` (the CPU oracle on the host cores, bounded sample, rank 0 at N=1 only; `saturated` = P processes x 8
 threads filling the host).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32): `ddg` = the [rows, 21] ddG table
+(gathered over the ranks when N > 1), or `ddg_listed` = the 200 000 listed values in strong mode.
 """
 import argparse
 import ctypes as C
@@ -41,6 +46,20 @@ FP32_MFMA_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_* dense pea
 BF16_MFMA_PEAK_TFLOPS = 2500.0     # MI355X_MICROARCH.md: dense bf16 / f16 MFMA peak
 SPLIT_TERMS = {"f16x2": 3, "bf16x3": 6}   # 16-bit MFMAs per fp32-class multiply-accumulate (tmpnn_split.h)
 HBM_PEAK_GBS = 8000.0              # MI355X_MICROARCH.md: HBM3E spec peak (6.29 TB/s measured copy)
+DUMP_CAP_BYTES = 64 << 20          # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, arrays, cap_bytes=DUMP_CAP_BYTES):
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float32. If they hold more than cap_bytes in all, each array keeps a
+    fixed sample of its rows (default_rng(0), sorted), so two builds run with the same arguments write comparable files."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {n: np.ascontiguousarray(a, dtype=np.float32) for n, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > cap_bytes:
+            keep = max(1, a.shape[0] * cap_bytes // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def kernel_flops(name, T, edges):
@@ -844,13 +863,20 @@ def main():
                          "200 000 listed mutants in total, sharded over the ranks")
     ap.add_argument("--precision", default=None, choices=["f16x2", "bf16x3", "fp32"],
                     help="matrix-core path of the per-edge GEMMs (default: the library default, f16x2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the PDB-files -> CSV / binary wall-clock leg")
-    ap.add_argument("--no-live-pmc", action="store_true", help="quote the committed PMC traffic file instead of measuring HBM bytes in two rocprofv3 child passes")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (per-kernel times, roofline, clock, timings "
+                         "without the exchange, extra legs, CPU baseline); the --no-* options below trim this")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline legs")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the per-kernel times and roofline")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --full: skip the PDB-files -> CSV / binary wall-clock leg")
+    ap.add_argument("--no-live-pmc", action="store_true", help="with --full: quote the committed PMC traffic file instead of measuring HBM bytes in two rocprofv3 child passes")
     ap.add_argument("--no-extras", action="store_true",
-                    help="timed workload only (no gather microbench / single-protein leg / cpu baseline): use under rocprofv3")
+                    help="with --full: no gather microbench / single-protein leg / cpu baseline: use under rocprofv3")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if os.environ.get("TMPNN_BENCH_WATCHDOG"):     # debugging aid: dump every thread's stack and exit if the run takes longer than N s
         import faulthandler
@@ -1016,8 +1042,9 @@ def main():
     # idle gaps that 40 records per step open lower the average power and let the clocks rise, so a kernel timed between gaps is
     # faster than the same kernel in the back-to-back stream that `value` is measured on. Both figures are in `kernels`;
     # rocprofv3's trace opens gaps too.)
+    # A plain run records no per-kernel events: (a) and the dominant kernel's events in (b) are --full only.
     prof_all, n_all, dom_name = {}, 0, None
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         n_all = max(5, min(args.steps, 20))
         _, prof_all, _ = timed(n_all, True, True)
         if prof_all:
@@ -1027,10 +1054,15 @@ def main():
     lib.tmpnn_profile_select(None)
     eng.check_last_status()                              # a range / max_len problem in the timed work is an error, not a number
     step_spread = spread(events)
-    clock_probe_ghz = shader_clock_ghz(lib, device) if rank == 0 else None
-    clock_ghz = clock_under_load_ghz(lib, device, step, dt / args.steps * 1e3) if rank == 0 and not grouped else None
-    if clock_ghz is None:
-        clock_ghz = clock_probe_ghz
+    if args.dump_outputs and rank == 0:                  # before any later leg runs the step again
+        table = gathered[(step_no[0] - 1) & 1] if grouped else outs[0]["ddg"]
+        got = {"ddg_listed": table.view(-1)[sw["sel"]]} if strong else {"ddg": table}
+        dump_outputs(args.dump_outputs, {n: t.cpu().numpy() for n, t in got.items()})
+    if args.full:
+        clock_probe_ghz = shader_clock_ghz(lib, device) if rank == 0 else None
+        clock_ghz = clock_under_load_ghz(lib, device, step, dt / args.steps * 1e3) if rank == 0 and not grouped else None
+        if clock_ghz is None:
+            clock_ghz = clock_probe_ghz
     n_cus = torch.cuda.get_device_properties(device).multi_processor_count
 
     if strong:
@@ -1066,15 +1098,16 @@ def main():
         result["collective"] = collective
     if strong:
         result["table_preds_per_s"] = 20 * sw["total_T"] * args.steps / dt
-        if grouped:                                      # the same steps without the exchange (and without the selection)
+        if grouped and args.full:                        # the same steps without the exchange (and without the selection)
             for _ in range(2):
                 step(gather=False)
             barrier()
             dt_nc, _, _ = timed(args.steps, False, False)
             result["excl_collective"] = {"value": 200000 * args.steps / dt_nc, "ms_per_step": dt_nc / args.steps * 1e3,
                                          "note": "forward on every rank's shard only: no all-gather, no selection"}
-        result["checksum_listed"] = float(picked[0].double().sum().item()) if picked[0] is not None else None
-    elif grouped:
+        if args.full:
+            result["checksum_listed"] = float(picked[0].double().sum().item()) if picked[0] is not None else None
+    elif grouped and args.full:
         # weak scaling too: the same steps without the per-step exchange, so a scaling curve separates compute from the collective
         for _ in range(2):
             step(gather=False)
@@ -1156,7 +1189,7 @@ def main():
                                   "note": "frac_of_binding_roof = sum over the launches of a step of max(t_hbm, t_mfma) / measured step time; "
                                           "frac_of_fp32_mfma_peak > 1 means faster than the fp32 matrix pipe could run the algorithmic flops",
                                   "gpu_kernel_ms_per_step": sum(v["avg_ms"] * v["launches_per_step"] for v in kern.values())}
-    if rank == 0 and not args.no_extras and not strong:
+    if rank == 0 and args.full and not args.no_extras and not strong:
         result["roofline_gather"] = gather_microbench(eng, device)
         result["roofline_gather"]["traffic"] = pmc_traffic("gather_rows", 16384)
         # HBM traffic of the dominant kernel measured in THIS run (two rocprofv3 --pmc child passes, ~1 min; the committed file stays the
@@ -1261,7 +1294,7 @@ def main():
             result["cpu_baseline"]["gpu_over_cpu"] = result["value"] / ref_cpu
             result["cpu_baseline"]["gpu_over_cpu_note"] = ("against the saturated host (all logical CPUs busy)" if sat.get("value")
                                                            else "against the best single-process thread count")
-    if grouped and dist.is_initialized() and not args.no_extras and not args.no_end_to_end and not strong:
+    if grouped and dist.is_initialized() and args.full and not args.no_extras and not args.no_end_to_end and not strong:
         try:                                                 # every rank takes part (the other ranks waited here for rank 0's extras)
             e2e = end_to_end_sharded(eng, rank, world)
         except Exception as e:                               # noqa: BLE001 - an extra leg must never take the bench line down

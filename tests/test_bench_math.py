@@ -153,3 +153,24 @@ def test_tracked_round_evidence_is_not_empty_and_belongs_to_these_kernels():
         "profiles/*_pmc_traffic.json was measured on other kernel sources: rerun tools/pmc_traffic.sh (tools/measure_round.sh)"
     line = json.load(open(os.path.join(REPO, "profiles", f"r{newest}_bench_full.json")))
     assert line["roofline"]["traffic"] and line["roofline"]["issue"]["frac_overlap"] < line["roofline"]["issue"]["frac_serial"] < 1.0
+
+
+def test_dump_outputs_writes_float32_and_keeps_a_fixed_sample_under_the_cap(tmp_path):
+    """--dump-outputs: arrays within the cap are written whole as float32; above it every array keeps the same seeded rows, so two
+    runs with the same arguments write the same files, and the files hold at most the cap in all."""
+    import numpy as np
+    import bench
+    table = np.arange(1000 * 21, dtype=np.float64).reshape(1000, 21)
+    listed = np.linspace(-1.0, 1.0, 3000)
+    bench.dump_outputs(str(tmp_path / "whole"), {"ddg": table})
+    got = np.load(tmp_path / "whole" / "ddg.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, table.astype(np.float32))
+    cap = 40000
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"ddg": table, "ddg_listed": listed}, cap_bytes=cap)
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("ddg", "ddg_listed")}
+    b = {n: np.load(tmp_path / "b" / f"{n}.npy") for n in ("ddg", "ddg_listed")}
+    assert all(np.array_equal(a[n], b[n]) for n in a) and sum(x.nbytes for x in a.values()) <= cap
+    assert a["ddg"].shape[1] == 21 and 0 < a["ddg"].shape[0] < 1000 and 0 < a["ddg_listed"].shape[0] < 3000
+    rows = a["ddg"][:, 0].astype(np.int64) // 21                      # every kept row is a whole row of the table, in order
+    assert np.array_equal(a["ddg"], table[rows].astype(np.float32)) and np.all(np.diff(rows) > 0)

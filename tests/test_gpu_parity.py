@@ -867,7 +867,7 @@ def test_two_rank_bench_and_cli(tmp_path):
     torchrun writes the same CSV as the single-process run."""
     import json
     repo = os.path.dirname(os.path.dirname(GOLDEN))
-    r = _torchrun([os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--proteins-per-gpu", "2"],
+    r = _torchrun([os.path.join(repo, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--proteins-per-gpu", "2"],
                   {"TMPNN_BENCH_ONE_DEVICE": "1", "TMPNN_BENCH_BACKEND": "gloo", "TMPNN_BENCH_WARMUP_SKEW": "1",
                    "TMPNN_BENCH_WATCHDOG": "120", "TMPNN_E2E_FILES": "16"})     # ranks warm up for different times: no collective may sit in that loop
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-2500:]
@@ -949,7 +949,7 @@ def test_profile_hook_records_one_kernel_when_asked(engine):
 
 
 def test_bench_line_times_the_dominant_kernel_inside_the_timed_region():
-    d = _bench(["--steps", "6", "--warmup", "2", "--proteins-per-gpu", "8", "--no-extras", "--no-cpu-baseline"])
+    d = _bench(["--full", "--steps", "6", "--warmup", "2", "--proteins-per-gpu", "8", "--no-extras", "--no-cpu-baseline"])
     r, k = d["roofline"], d["kernels"]
     dom = r["kernel"]
     assert k[dom]["timed"].startswith("inside the timed region") and k[dom]["launches"] == 6 * k[dom]["launches_per_step"]
@@ -968,7 +968,7 @@ def test_bench_self_launches_and_proves_its_ranks():
     try:
         os.environ.clear()
         os.environ.update(env)
-        d = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--proteins-per-gpu", "2"], smoke)
+        d = _bench(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--proteins-per-gpu", "2"], smoke)
     finally:
         os.environ.clear()
         os.environ.update(os_env_backup)
@@ -996,8 +996,8 @@ def test_rccl_runs_on_this_box_with_one_rank():
     assert c["backend"].startswith("nccl") and c["world_size"] == 1 and c["ranks_seen"] == 1 and c["distinct_devices"] == 1
     plain = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--proteins-per-gpu", "2", "--no-extras"])
     assert "collective" not in plain and d["config"]["preds_per_step"] == plain["config"]["preds_per_step"]
-    s1 = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--scaling", "strong"], {"TMPNN_BENCH_FORCE_GROUP": "1"})
-    s0 = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--scaling", "strong"])
+    s1 = _bench(["--full", "--gpus", "1", "--steps", "2", "--warmup", "1", "--scaling", "strong"], {"TMPNN_BENCH_FORCE_GROUP": "1"})
+    s0 = _bench(["--full", "--gpus", "1", "--steps", "2", "--warmup", "1", "--scaling", "strong"])
     assert s1["checksum_listed"] == s0["checksum_listed"] and s1["excl_collective"]["value"] > 0     # gathered by RCCL == computed locally
     repo = os.path.dirname(os.path.dirname(GOLDEN))
     code = ("import os, sys, socket, torch, torch.distributed as dist\n"
@@ -1015,17 +1015,21 @@ def test_rccl_runs_on_this_box_with_one_rank():
     assert r.returncode == 0 and "rccl-ok" in r.stdout, r.stdout[-1000:] + r.stderr[-3000:]
 
 
-def test_bench_strong_scaling_mode_is_rank_invariant():
+def test_bench_strong_scaling_mode_is_rank_invariant(tmp_path):
     """--scaling strong = BASELINE configs[3] (300 proteins / 200 000 listed mutants, fixed total work). The listed values
-    gathered from two ranks are the same numbers as from one (their float64 sum is bit-equal)."""
-    one = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--scaling", "strong"])
-    two = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--scaling", "strong"],
+    gathered from two ranks are the same numbers as from one (their float64 sum is bit-equal, and so are the dumped values)."""
+    one = _bench(["--full", "--gpus", "1", "--steps", "2", "--warmup", "1", "--scaling", "strong", "--dump-outputs", str(tmp_path / "one")])
+    two = _bench(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--scaling", "strong", "--dump-outputs", str(tmp_path / "two")],
                  {"TMPNN_BENCH_ONE_DEVICE": "1", "TMPNN_BENCH_BACKEND": "gloo", "TMPNN_BENCH_WATCHDOG": "300"})
     for d, n in ((one, 1), (two, 2)):
         assert d["scaling"] == "strong" and d["n_gpus"] == n and d["config"]["preds_per_step"] == 200000
         assert abs(d["value"] - 200000 * 2 / (d["ms_per_step"] * 2e-3)) / d["value"] < 1e-6
     assert one["checksum_listed"] == two["checksum_listed"] and np.isfinite(one["checksum_listed"])
     assert two["collective"]["ranks_seen"] == 2 and two["excl_collective"]["value"] > 0
+    a, b = np.load(tmp_path / "one" / "ddg_listed.npy"), np.load(tmp_path / "two" / "ddg_listed.npy")
+    assert a.dtype == np.float32 and a.shape == (200000,)
+    np.testing.assert_array_equal(a, b)
+    assert abs(a.astype(np.float64).sum() - one["checksum_listed"]) <= 1e-9 * np.abs(a).astype(np.float64).sum()   # the path's own values
 
 
 def test_captured_graph_owns_its_buffers(synthetic_weights):
@@ -1176,7 +1180,7 @@ def test_bench_contract_line():
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(GOLDEN))
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--full", "--gpus", "1", "--steps", "2", "--warmup", "1",
                         "--proteins-per-gpu", "2", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600,
                        env=dict(os.environ, TMPNN_E2E_FILES="48"))
     assert r.returncode == 0, r.stderr[-2000:]
@@ -1198,3 +1202,20 @@ def test_bench_contract_line():
     assert rf["bound"] == ("hbm" if rf["t_hbm_roof_us"] >= rf["t_mfma_roof_us"] else "mfma")
     assert 0 < d["pipeline"]["frac_of_binding_roof"] < 1 and d["ms_per_step_spread"]["n"] == 2
     assert d["roofline_gather"]["bound"] == "hbm" and d["roofline_gather"]["unit"] == "GB/s"
+
+
+def test_plain_bench_line_is_lean_and_dumps_the_timed_outputs(tmp_path, engine):
+    """Without --full the line carries the headline figure alone, --steps is the number of timed steps, and --dump-outputs writes
+    the ddG table of the last timed step: the same bits as one forward of the same seeded batch."""
+    import bench
+    d = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--proteins-per-gpu", "2", "--dump-outputs", str(tmp_path)])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["ms_per_step_spread"]["n"] == 3 and d["unit"] == "preds/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 2 * 256 * 20 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert not {"roofline", "kernels", "pipeline", "roofline_gather", "single_protein", "modes", "end_to_end", "cpu_baseline"} & set(d)
+    got = np.load(tmp_path / "ddg.npy")
+    b = bench.build_batch(2, 256, 0, torch.device("cuda:0"))
+    want = engine.ssm_forward(b["X"], b["S"], b["mask"], b["ridx"], b["cenc"], b["offsets"], max_len=256)["ddg"].cpu().numpy()
+    assert got.dtype == np.float32 and got.shape == (2 * 256, 21)
+    np.testing.assert_array_equal(got, want)

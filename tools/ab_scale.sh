@@ -2,7 +2,7 @@
 # per-kernel time vs batch size (prologue / fixed cost = intercept): tools/ab_scale.sh "ENV=VAL ..." 8 16 32 64 128
 envs=$1; shift
 for B in "$@"; do
-  env $envs python bench.py --steps 15 --warmup 8 --no-extras --proteins-per-gpu $B > /tmp/sc.json 2>/tmp/sc.err
+  env $envs python bench.py --full --steps 15 --warmup 8 --no-extras --proteins-per-gpu $B > /tmp/sc.json 2>/tmp/sc.err
   python - $B <<'PY'
 import json, sys
 try:

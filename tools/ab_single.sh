@@ -5,7 +5,7 @@ for spec in "$@"; do
   name=${spec%%:*}
   envs=""
   if [[ "$spec" == *:* ]]; then envs=$(echo "${spec#*:}" | tr ',' ' '); fi
-  env $envs python bench.py --steps 15 --warmup 8 --no-extras --proteins-per-gpu 1 > /tmp/s1.json 2>/tmp/s1.err
+  env $envs python bench.py --full --steps 15 --warmup 8 --no-extras --proteins-per-gpu 1 > /tmp/s1.json 2>/tmp/s1.err
   env $envs python - "$name" <<'PY'
 import json, sys, time
 import torch

@@ -13,19 +13,19 @@ python tools/isa_counts.py $O/${TAG}_isa_counts.json > /dev/null 2>&1
 bash tools/pmc_traffic.sh > $O/${TAG}_pmc_traffic.log 2>&1
 cp $O/pmc_traffic/pmc_traffic.json $O/${TAG}_pmc_traffic.json; cp $O/pmc_traffic/FETCH_SIZE_per_kernel.csv $O/${TAG}_pmc_FETCH_SIZE_per_kernel.csv; cp $O/pmc_traffic/WRITE_SIZE_per_kernel.csv $O/${TAG}_pmc_WRITE_SIZE_per_kernel.csv
 cp $O/${TAG}_pmc_traffic.json $R/profiles/${TAG}_pmc_traffic.json   # bench.py reads the stamped file: PMC pass first, so the bench line of THIS call carries traffic
-python bench.py > $O/${TAG}_bench_full.json 2> $O/${TAG}_bench_full.err
+python bench.py --full > $O/${TAG}_bench_full.json 2> $O/${TAG}_bench_full.err
 python tools/run_configs.py > $O/${TAG}_configs_2to5.json 2> $O/${TAG}_configs.err
 ( cd /tmp && export TMPDIR=/tmp && rm -rf $O/prof_$TAG && \
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$TAG -o $TAG -- python $R/bench.py --steps 10 --warmup 3 --no-extras > $O/${TAG}_bench_under_rocprof.json 2> $O/${TAG}_rocprof.err )
 cp $(find $O/prof_$TAG -name "*kernel_stats.csv" | head -1) $O/${TAG}_bench_kernel_stats.csv 2>/dev/null
 # the same trace restricted to the 10 timed steps (the --stats CSV also averages the clock warm-up launches)
 python tools/rocprof_timed_stats.py $(find $O/prof_$TAG -name "*kernel_trace.csv" | head -1) 10 > $O/${TAG}_bench_kernel_stats_timed.csv
-python bench.py --scaling strong --steps 20 --warmup 5 > $O/${TAG}_bench_strong_1gpu.json 2> $O/${TAG}_bench_strong.err
-TMPNN_BENCH_ONE_DEVICE=1 TMPNN_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 5 --warmup 2 --proteins-per-gpu 8 --no-cpu-baseline > $O/${TAG}_bench_selflaunch_2ranks_one_device.json 2> $O/${TAG}_bench_selflaunch.err
+python bench.py --full --scaling strong --steps 20 --warmup 5 > $O/${TAG}_bench_strong_1gpu.json 2> $O/${TAG}_bench_strong.err
+TMPNN_BENCH_ONE_DEVICE=1 TMPNN_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --steps 5 --warmup 2 --proteins-per-gpu 8 --no-cpu-baseline > $O/${TAG}_bench_selflaunch_2ranks_one_device.json 2> $O/${TAG}_bench_selflaunch.err
 # round 6: the line the driver would run cold on an 8-GPU node, executed once with EIGHT ranks (all on this one device, gloo): collective.ranks_seen == 8
-TMPNN_BENCH_ONE_DEVICE=1 TMPNN_BENCH_BACKEND=gloo python bench.py --gpus 8 --steps 5 --warmup 2 --proteins-per-gpu 8 --no-cpu-baseline > $O/${TAG}_bench_selflaunch_8ranks_one_device.json 2> $O/${TAG}_bench_selflaunch8.err
+TMPNN_BENCH_ONE_DEVICE=1 TMPNN_BENCH_BACKEND=gloo python bench.py --full --gpus 8 --steps 5 --warmup 2 --proteins-per-gpu 8 --no-cpu-baseline > $O/${TAG}_bench_selflaunch_8ranks_one_device.json 2> $O/${TAG}_bench_selflaunch8.err
 # RCCL itself, on this 1-GPU box: a process group of ONE rank (init_process_group("nccl"), device-buffer all_gather_into_tensor, the async overlap)
-TMPNN_BENCH_FORCE_GROUP=1 python bench.py --steps 20 --warmup 5 --no-extras > $O/${TAG}_bench_rccl_1rank.json 2> $O/${TAG}_bench_rccl_1rank.err
+TMPNN_BENCH_FORCE_GROUP=1 python bench.py --full --steps 20 --warmup 5 --no-extras > $O/${TAG}_bench_rccl_1rank.json 2> $O/${TAG}_bench_rccl_1rank.err
 bash tools/pmc_sq.sh > $O/${TAG}_pmc_sq.log 2>&1
 cp $O/pmc_sq_summary.txt $O/${TAG}_pmc_sq_summary.txt
 # round 4: the end-to-end leg on its own, the kernel-boundary probe (+ its rocprofv3 trace), the margin probe
