@@ -90,32 +90,39 @@ def test_product_refuses_cpu():
         gather_nodes(torch.zeros(1, 4, 8), torch.zeros(1, 4, 2, dtype=torch.long))
 
 
-def test_shipped_library_has_no_environment_switches():
-    """kernel-form switches and phase timers (getenv, hipMalloc + blocking hipMemcpy + fprintf inside
-    launchers) live only in the -DTMPNN_DEBUG_BUILD variant; the shipped library's launchers pick forms from the launch size."""
+def test_environment_switches_live_in_the_debug_library_only():
+    """launch-size switches and phase timers (getenv, hipMalloc + blocking hipMemcpy + fprintf inside
+    launchers) live only in the -DTMPNN_DEBUG_BUILD variant; the shipped library's launchers pick forms from the launch size and
+    the handle's precision. The retired kernel-form switches (forms no shipped launch reaches) are in neither library."""
     from thermompnn_amd import _lib, build
     build.build_library()
     build.build_debug_library()
-    names = [b"TMPNN_KNN_REG", b"TMPNN_KNN_SEL", b"TMPNN_FEAT_IMG", b"TMPNN_FEAT_WAVES", b"TMPNN_FEAT_SPLIT", b"TMPNN_FEAT_PROF",
-             b"TMPNN_HEAD_SPLIT", b"TMPNN_NODE_IMG", b"TMPNN_NODE_SPLIT", b"TMPNN_NODE_DEEP", b"TMPNN_NODE_PROF", b"TMPNN_EDGE_PROF",
+    names = [b"TMPNN_KNN_REG", b"TMPNN_KNN_SEL", b"TMPNN_FEAT_PROF", b"TMPNN_NODE_DEEP", b"TMPNN_NODE_PROF", b"TMPNN_EDGE_PROF",
              b"TMPNN_MSG_PROF", b"TMPNN_MSG_WAVE_MIN", b"TMPNN_FUSE_SMALL"]
+    retired = [b"TMPNN_FEAT_IMG", b"TMPNN_FEAT_WAVES", b"TMPNN_FEAT_SPLIT", b"TMPNN_HEAD_SPLIT", b"TMPNN_NODE_IMG", b"TMPNN_NODE_SPLIT",
+               b"TMPNN_EDGE_WAVE_MIN"]
     shipped, debug = open(_lib.LIB_PATH, "rb").read(), open(_lib.DEBUG_LIB_PATH, "rb").read()
     assert not [n for n in names if n in shipped]
     assert all(n in debug for n in names)
+    assert not [n for n in retired if n in shipped or n in debug]
     assert b"phases (" not in shipped and b"phases (" in debug          # the timers' fprintf formats
 
 
 def test_shipped_kernels_have_one_form_and_no_ablations():
     """the lab is out of the product sources. Timing ablations (TM_ABL_*: results wrong by construction) compile
     only with -DTMPNN_DEBUG_BUILD — the shipped flags refuse them with an #error —, the dead kernel-form switches of rounds 1-4 are
-    gone from the sources, and no 'TM_ABL' string is in the shipped library."""
+    gone from the sources (so are the f16x2 forms without fragment images, the fp32-kernel switches of f16x2 handles and the
+    wavefront-per-block edge update), and no 'TM_ABL' string is in the shipped library."""
     import glob
     import subprocess
     from thermompnn_amd import _lib, build
     csrc = os.path.join(os.path.dirname(_lib.LIB_PATH), "csrc")
     text = {f: open(f).read() for f in glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h"))}
-    for gone in ("TM_EDGE_UNROLL2", "TM_SETPRIO", "TM_SPLIT_MIX", "TM_MSG_PFD", "TM_EDGE_Y_ALIAS", "TM_GELU_FORM", "TM_GELU_ASM", "TM_MSG_TOUCH"):
+    for gone in ("TM_EDGE_UNROLL2", "TM_SETPRIO", "TM_SPLIT_MIX", "TM_MSG_PFD", "TM_EDGE_Y_ALIAS", "TM_GELU_FORM", "TM_GELU_ASM", "TM_MSG_TOUCH",
+                 "TMPNN_FEAT_IMG", "TMPNN_FEAT_WAVES", "TMPNN_FEAT_SPLIT", "TMPNN_HEAD_SPLIT", "TMPNN_NODE_IMG", "TMPNN_NODE_SPLIT",
+                 "TMPNN_EDGE_WAVE_MIN", "TM_FEAT_DMA", "TM_FEAT_DIST2", "imgp11"):
         assert not [f for f, t in text.items() if gone in t], gone
+    assert not os.path.exists(os.path.join(csrc, "tmpnn_edge_wave.hip"))
     assert b"TM_ABL" not in open(_lib.LIB_PATH, "rb").read()
     assert set(os.path.basename(f) for f in text) >= {"tmpnn_edge.hip", "tmpnn_msg.hip", "tmpnn_edge_msg.hip", "tmpnn_node.hip"}
     assert max(t.count("\n") for t in text.values()) < 1300              # (round 4: one 1 735-line file held seven kernels)

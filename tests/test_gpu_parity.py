@@ -634,11 +634,8 @@ def test_precision_default_comes_from_the_environment():
     assert bad.returncode != 0 and "unknown precision" in bad.stderr      # an error, not an abort()
 
 
-@pytest.mark.parametrize("env", [{"TMPNN_NODE_SPLIT": "0", "TMPNN_FEAT_SPLIT": "0", "TMPNN_HEAD_SPLIT": "0"},
-                                 {"TMPNN_NODE_IMG": "0", "TMPNN_FEAT_IMG": "0"}, {"TMPNN_NODE_DEEP": "0", "TMPNN_KNN_REG": "0"},
-                                 {"TMPNN_MSG_WAVE_MIN": "0", "TMPNN_FUSE_SMALL": "0"}],
-                         ids=["fp32_node_featurizer_head", "no_weight_fragment_images", "tall_node_tiles_and_lds_knn_for_small_launches",
-                              "wavefront_per_residue_message_pass_for_small_launches"])
+@pytest.mark.parametrize("env", [{"TMPNN_NODE_DEEP": "0", "TMPNN_KNN_REG": "0"}, {"TMPNN_MSG_WAVE_MIN": "0", "TMPNN_FUSE_SMALL": "0"}],
+                         ids=["tall_node_tiles_and_lds_knn_for_small_launches", "wavefront_per_residue_message_pass_for_small_launches"])
 def test_selectable_kernel_forms_pass_golden_parity(env):
     """The non-default kernel forms of the f16x2 mode stay parity-green. The switches exist only in the debug variant of the
     library (libtmpnn_debug.so, -DTMPNN_DEBUG_BUILD; read once per process) — the shipped library ignores them."""

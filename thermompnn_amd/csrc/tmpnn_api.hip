@@ -235,7 +235,7 @@ static const size_t POS_TABLE_FLOATS = 66 * TMPNN_HID, SEQ_TABLE_FLOATS = TMPNN_
                     CONV_CENTER_FLOATS = 384 * 384;
 static size_t packed_bytes_for(int mode) {    // the f16 fragment images exist for f16x2 handles only (nothing else reads them)
     return (POS_TABLE_FLOATS + 3 * SEQ_TABLE_FLOATS + CONV_CENTER_FLOATS) * sizeof(float) +
-           (mode == TM_MM_F16X2 ? (size_t)(TM_N_WIMG + TM_N_WIMGP_BUILT) * TM_WIMG_BYTES : 0);
+           (mode == TM_MM_F16X2 ? (size_t)(TM_N_WIMG + TM_N_WIMGP) * TM_WIMG_BYTES : 0);
 }
 extern "C" size_t tmpnn_weights_packed_bytes(void) { return packed_bytes_for(TM_MM_F16X2); }   // upper bound over the precisions
 extern "C" size_t tmpnn_weights_packed_bytes_p(const char *precision) {
@@ -357,7 +357,7 @@ extern "C" int tmpnn_weights_create_p(tmpnn_weights_t **out, const float *const 
         }
         std::sort(w->wimg, w->wimg + w->n_wimg, [](const WImg &x, const WImg &y) { return x.base < y.base; });   // tm_find_wimg searches it
         auto addp = [&](const float *base, int ld) {     // K-permuted images (msg8_wave_kernel)
-            if (rc != TMPNN_OK || w->n_wimgp >= TM_N_WIMGP_BUILT) return;
+            if (rc != TMPNN_OK || w->n_wimgp >= TM_N_WIMGP) return;
             w->wimgp[w->n_wimgp++] = WImg{base, img};
             rc = launch_prep_wimg(base, ld, img, (hipStream_t)stream, 128, 128, 0, true);
             img += TM_WIMG_BYTES;
@@ -365,9 +365,6 @@ extern "C" int tmpnn_weights_create_p(tmpnn_weights_t **out, const float *const 
         for (int l = 0; l < 3; ++l) {
             addp(w->enc[l].W1 + 128, 384); addp(w->enc[l].W2, 128);
             addp(w->dec[l].W1 + 128, 512); addp(w->dec[l].W2, 128);
-#ifdef TMPNN_DEBUG_BUILD      // the edge update's wavefront-per-block experiment (tmpnn_edge_wave.hip, debug library only)
-            addp(w->enc[l].W11 + 128, 384); addp(w->enc[l].W12, 128); addp(w->enc[l].W13, 128);
-#endif
         }
     }
     if (rc != TMPNN_OK) { delete w; return rc; }
@@ -676,7 +673,7 @@ extern "C" int tmpnn_ssm_forward(const tmpnn_weights_t *w, const float *X, const
     static const bool fuse_small = TM_DBG_FLAG("TMPNN_FUSE_SMALL", true);     // (A/B switch in the debug library only)
     bool head_done = false;                                                   // the ddG head ran inside the last node update's launch
     const KnnInit kinit{hV[0], ws.P, w->enc[0].b1, status_opt};
-    if (fuse_small && max_len <= 256 && featurize_fusable(w, T)) {             // one tile per workgroup: k-NN inside the featurizer launch
+    if (fuse_small && max_len <= 256 && featurize_fusable(tm_matmul_mode(), T)) {             // one tile per workgroup: k-NN inside the featurizer launch
         const KnnFuse kf{mask, offsets, n_proteins, max_len, K, E_idx, D_nb, kinit};
         TRY(launch_featurize(w, X, residue_idx, chain_enc, E_idx, D_nb, T, hE, nullptr, st, &kf));
     } else {
@@ -710,7 +707,7 @@ extern "C" int tmpnn_ssm_forward(const tmpnn_weights_t *w, const float *X, const
             // last layer: its node update and the ddG head of the same 16 residues are ONE launch (node_head_fused_kernel, bit-identical)
             HeadArgs ha;
             const bool with_head = l == 2 && ddg && node_head_fusable(tm_matmul_mode(), T);
-            if (with_head) ha = tm_head_args(w, hV[3], hV[2], S, T, ddg, nullptr, status_opt, E_idx);
+            if (with_head) TRY(tm_head_args(ha, w, hV[3], hV[2], S, T, ddg, nullptr, status_opt, E_idx));
             TRY(launch_node_update(d.W3, d.b3, d.norm1_w, d.norm1_b, d.Win, d.bin, d.Wout, d.bout, d.norm2_w, d.norm2_b, hV[l],
                                    ws.Ssum, ws.cnt, mask, T, hV[l + 1], l < 2 ? &next : nullptr, nullptr, st, with_head ? &ha : nullptr,
                                    with_head ? &head_done : nullptr));

@@ -229,10 +229,9 @@ __global__ __launch_bounds__(512, 2) void enc_edge8_rp_kernel(EdgeArgsB a, unsig
 int launch_enc_edge_split(int mode, const EncW &e, const float *P, float *hE, const int32_t *E_idx, int64_t T, hipStream_t st) {
     const bool h2 = mode == TM_MM_F16X2;
     EdgeArgsB a{e.W11 + 128, e.W12, e.b12, e.W13, e.b13, e.norm3_w, e.norm3_b, P, hE, E_idx, (int)T,
-                h2 ? tm_find_wimg(e.W11 + 128) : nullptr, h2 ? tm_find_wimg(e.W12) : nullptr, h2 ? tm_find_wimg(e.W13) : nullptr,
-                h2 ? tm_find_wimgp(e.W11 + 128) : nullptr, h2 ? tm_find_wimgp(e.W12) : nullptr, h2 ? tm_find_wimgp(e.W13) : nullptr};
-    // f16x2, large launches: one wavefront per 16-row block, one wavefront per SIMD (tmpnn_edge_wave.hip)
-    if (h2 && a.imgp11 && a.imgp12 && a.imgp13 && enc_edge_wave_wanted(T)) return launch_enc_edge_wave(a, T, st);
+                h2 ? tm_find_wimg(e.W11 + 128) : nullptr, h2 ? tm_find_wimg(e.W12) : nullptr, h2 ? tm_find_wimg(e.W13) : nullptr};
+    if (h2 && !(a.img11 && a.img12 && a.img13))
+        return tm_set_error(TMPNN_E_INVALID, "enc_edge_split: f16x2 handle without the fragment images of W11e / W12 / W13");
     const int64_t cap = tm_num_cus();
     const int grid = (int)(T < cap ? T : cap);
     if (mode == TM_MM_BF16X3) {

@@ -415,13 +415,12 @@ __device__ __forceinline__ void atoms5(const float *__restrict__ x, float *out /
     }
 }
 
-// NW wavefronts per workgroup (1 workgroup per CU): NW = 8 puts two wavefronts on every SIMD, each owning ONE
-// 16-column block (132 weight VGPRs). The matrix-pipe work per SIMD is unchanged, but the serial phases in front of
-// the GEMM (atom gather -> 1200 distances -> 19200 Gaussians) and the LayerNorm / store phases run on twice the
-// threads with twice the latency hiding — they were 50 % of this kernel's time with 4 wavefronts.
-template <int NW>
-__global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : 1)) void featurize_kernel(FeatArgs a) {
-    constexpr int NT = 64 * NW, NCB = 8 / NW, RPW = TM_TILE / NW;    // threads, column blocks / wave, rows / wave
+// 8 wavefronts per workgroup (1 workgroup per CU): two wavefronts on every SIMD, each owning ONE 16-column block (132 weight
+// VGPRs). Against 4 wavefronts the matrix-pipe work per SIMD is unchanged, but the serial phases in front of the GEMM (atom
+// gather -> 1200 distances -> 19200 Gaussians) and the LayerNorm / store phases run on twice the threads with twice the
+// latency hiding — they were 50 % of this kernel's time with 4 wavefronts.
+__global__ __launch_bounds__(512, 2) void featurize_kernel(FeatArgs a) {
+    constexpr int NW = 8, NT = 64 * NW, NCB = 8 / NW, RPW = TM_TILE / NW;    // waves, threads, column blocks / wave, rows / wave
     __shared__ __attribute__((aligned(16))) float rbf[TM_TILE * RBF_RS];
     __shared__ __attribute__((aligned(16))) float tA[TM_TILE * TM_H];
     __shared__ __attribute__((aligned(16))) float tB[TM_TILE * TM_H];
@@ -551,13 +550,6 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : 1)) void featurize_kernel(F
 #ifndef TM_FEAT_PF
 #define TM_FEAT_PF 1      // B-fragment prefetch distance of GEMM 1 (mma_tile_split): 1 = 0.500 ms with 38 spilled VGPRs (reloaded around the GEMM, not in it) against 0.524 at 0 (13 spilled), 0.527 at 2
 #endif
-#ifndef TM_FEAT_DIST2
-#define TM_FEAT_DIST2 1
-#endif
-#ifndef TM_FEAT_DMA
-#define TM_FEAT_DMA 1     // 1: the next tile's rows go global -> LDS by LDS-DMA, issued before the Gaussians (see the kernel); 0: through 18
-                          // VGPRs of every wavefront, issued after them (round 2)
-#endif
 // one LDS-DMA piece: lane l's 16 (4) bytes at `src` land at LDS byte address lds + 16 (4) * l (wave-uniform base in M0; retired
 // through vmcnt). Inline asm ON PURPOSE: with the builtin, hipcc orders every later ds_read of the wavefront behind the piece
 // (s_waitcnt vmcnt(0) in front of the first LDS read — here the Gaussians), which exposes exactly the latency the piece is
@@ -578,7 +570,7 @@ __device__ __forceinline__ void tm_glds4(const void *src, unsigned lds) {
 // launch less in front of a single protein (2.5 us of dispatch + the start-up latency of a kernel, tools/gap_probe.py).
 struct KnnFuseArgs { const float *mask; const int32_t *offsets; int N, max_len, K; int32_t *E_idx; float *D_nb; KnnInit init; int sel_rows; };
 
-template <typename SP, bool PROF = false, bool IMG = false, bool KNN = false>
+template <typename SP, bool PROF = false, bool KNN = false>
 __global__ __launch_bounds__(512, 2) void featurize_split_kernel(FeatArgs a, unsigned long long *prof = nullptr, KnnFuseArgs kf = KnnFuseArgs{}) {
     unsigned long long t_last = 0;
     auto mark = [&](int k) {
@@ -603,33 +595,28 @@ __global__ __launch_bounds__(512, 2) void featurize_split_kernel(FeatArgs a, uns
     const int tid = tm_tid(), lane = tid & 63, wv = tid >> 6, m = lane & 15, q = lane >> 4;
     const int ncol = 16 * wv + 4 * q, c4 = 4 * wv + q;
 
-    // Weight fragments, resident for the whole launch (136 VGPRs). With fragment images (f16x2 handles) they arrive as coalesced
-    // 1 KB loads instead of 16-row fp32 gathers split on the fly (the prologue is what a single protein pays for). Re-reading
+    // Weight fragments, resident for the whole launch (136 VGPRs), from the fragment images: coalesced 1 KB loads instead of
+    // 16-row fp32 gathers split on the fly (the prologue is what a single protein pays for). Re-reading
     // W_e per tile instead of keeping it (to free 32 VGPRs for the GEMM-1 pipeline) was measured twice: 64 KB per tile through
     // the CU's 64 B/clk return path costs more than the pipeline gains (0.546 vs 0.534 ms).
+    static_assert(SP::NP == 2, "the fragment images hold the two f16x2 planes");
     WFragS<SP> wedge[1][13], we[1][4];
-    if constexpr (IMG) {
 #pragma unroll
-        for (int st = 0; st < 13; ++st) {
-            const char *p = a.img_e[st >> 2] + (size_t)wv * 8192 + (st & 3) * 2048 + lane * 16;
-            wedge[0][st].p[0] = *reinterpret_cast<const u4 *>(p);
-            wedge[0][st].p[1] = *reinterpret_cast<const u4 *>(p + 1024);
-        }
-        const char *pw = a.img_we + (size_t)wv * 8192 + lane * 16;
+    for (int st = 0; st < 13; ++st) {
+        const char *p = a.img_e[st >> 2] + (size_t)wv * 8192 + (st & 3) * 2048 + lane * 16;
+        wedge[0][st].p[0] = *reinterpret_cast<const u4 *>(p);
+        wedge[0][st].p[1] = *reinterpret_cast<const u4 *>(p + 1024);
+    }
+    const char *pw = a.img_we + (size_t)wv * 8192 + lane * 16;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            we[0][c].p[0] = *reinterpret_cast<const u4 *>(pw + 2048 * c);
-            we[0][c].p[1] = *reinterpret_cast<const u4 *>(pw + 2048 * c + 1024);
-        }
-    } else {
-        load_wfrag_split<SP, 13>(a.edge_w, 416, 16 * wv, 16, 400, wedge[0], lane, 16);
-        load_wfrag_split<SP, 4>(a.We_w, TM_H, 16 * wv, 0, TM_H, we[0], lane);
+    for (int c = 0; c < 4; ++c) {
+        we[0][c].p[0] = *reinterpret_cast<const u4 *>(pw + 2048 * c);
+        we[0][c].p[1] = *reinterpret_cast<const u4 *>(pw + 2048 * c + 1024);
     }
     if (tid < 3 * TM_H / 4) {
         const int w = tid >> 5, c = 4 * (tid & 31);
         st4(&s_const[w][c], ld4((w == 0 ? a.We_b : w == 1 ? a.ln_w : a.ln_b) + c));   // visible after the prologue's barriers
     }
-#if TM_FEAT_DMA
     // PositionalEncodings (:896-908) = one_hot(d) . W_pos^T + b_pos: 16 values per edge, a 66-row table in LDS. They ride GEMM 1
     // in its K padding (columns 400..415 against edge_embedding.weight[:, 0:16]) instead of arriving as accumulator rows from
     // a [66,128] global table: no global load between the tile loop's barriers at all
@@ -638,7 +625,6 @@ __global__ __launch_bounds__(512, 2) void featurize_split_kernel(FeatArgs a, uns
         const int d = e >> 4, pp = e & 15;
         s_pos[d][pp] = a.pos_w[pp * 66 + d] + a.pos_b[pp];
     }
-#endif
     f4 mu4;                                                   // this thread's 4 Gaussian centres: (tid & 3) is fixed
 #pragma unroll
     for (int r = 0; r < 4; ++r) mu4[r] = a.mu[(tid & 3) * 4 + r];
@@ -647,7 +633,7 @@ __global__ __launch_bounds__(512, 2) void featurize_split_kernel(FeatArgs a, uns
     asm volatile("" ::"v"(mu4.x), "v"(mu4.y), "v"(mu4.z), "v"(mu4.w));
 
     // Per-tile inputs (neighbour list, 5 atoms of every neighbour, positional index, Ca-Ca distance), one tile ahead.
-    // TM_FEAT_DMA = 1 (round 3): the phase profile showed GEMM 1 at 1.85 x its matrix time only because wavefront 0 met the
+    // Round 3: the phase profile showed GEMM 1 at 1.85 x its matrix time only because wavefront 0 met the
     // dependent global loads (E_idx -> X[j]) in front of it — vmcnt retires in order, so the accumulator rows issued behind
     // them waited for both latencies (2 600 of the tile's 17 300 cycles), and the 18 registers holding the rows across the
     // GEMM were spilled and reloaded in `publish` (900 cycles, serial). Now: the list entry of tile i+2 is an ordinary load
@@ -655,21 +641,13 @@ __global__ __launch_bounds__(512, 2) void featurize_split_kernel(FeatArgs a, uns
     // and 1 (the residue itself) BEFORE the Gaussians, which outlast their latency; this tile's positional rows are loaded
     // into the accumulators at the same point. `publish` reads the raw rows back, adds the virtual Cb and writes the tables
     // `distances` uses. (All 64 lanes of both wavefronts issue: lanes >= 48 duplicate neighbour 47, so no EXEC-masked DMA.)
-    // TM_FEAT_DMA = 0: registers, issued after the Gaussians; a two-deep variant of that form was measured in round 2: no gain.
-#if TM_FEAT_DMA
     __shared__ __attribute__((aligned(16))) float s_raw[3][64][4];   // neighbours' rows: [16-byte piece of the 48-byte row][lane]
     __shared__ __attribute__((aligned(16))) float s_sraw[64];        // the residue's own row, one word per lane (12 used)
     __shared__ int s_misc[3][64];                            // per neighbour: masked Ca-Ca distance, residue_idx[j], chain[j]; lane 48 of the last two: [i]
     __shared__ int s_list[2][64];                            // neighbour lists, two tiles ahead: [tile parity][neighbour]
     const int wu = __builtin_amdgcn_readfirstlane(wv);       // scalar branches around the pieces
-#else
-    float g_at[15];
-    float g_d0 = 0.f;
-    int g_idx = -1, g_dpos = 0;
-#endif
     // (lane offsets laundered through an empty asm: otherwise the compiler hoists base + lane as 64-bit pairs out of the tile
     //  loop, spills them, and the reload's vmcnt(0) — in order behind the DMA pieces — waits for the pieces)
-#if TM_FEAT_DMA
     // the 8 pieces of one tile, ONE per wavefront (a piece costs its wavefront several hundred cycles of issue): rows of tile ii
     // through its list in s_list[lb] (landed a tile ago), and the list of tile i2 (two ahead; < 0: none) into s_list[lb ^ 1].
     // Lanes 48..63 of the per-neighbour pieces address the residue itself: lane 48 of residue_idx / chain is what `publish`
@@ -699,24 +677,7 @@ __global__ __launch_bounds__(512, 2) void featurize_split_kernel(FeatArgs a, uns
         }
     };
     auto landed = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };   // in front of the barrier that publishes the pieces
-#else
-    auto fetch = [&](int ii) {
-        if (tid < TM_TILE) {
-            const int j = a.E_idx[(size_t)ii * TM_KS + tid];
-            g_idx = j;
-            const int jj = j < 0 ? ii : j;
-            atoms5(a.X + (size_t)jj * 12, g_at);
-            const int off = a.ridx[ii] - a.ridx[jj];              // PositionalEncodings index (:903-905, :1170-1175)
-            const int same = a.cenc[ii] == a.cenc[jj];
-            g_dpos = same ? min(max(off + 32, 0), 64) : 65;
-            g_d0 = a.D_nb[(size_t)ii * TM_KS + tid];              // masked Ca-Ca distance from _dist (:1142)
-        } else if (tid == 64) {
-            atoms5(a.X + (size_t)ii * 12, g_at);
-        }
-    };
-#endif
     auto publish = [&](int buf, int lb) {
-#if TM_FEAT_DMA
         // (everything local: a value assigned under a wavefront test and declared outside the tile loop is carried through
         //  it as a phi in every wavefront — 17 VGPRs of pressure in the round-2 form)
         if (wu < 2) {                                           // (the pieces landed before the last barrier)
@@ -742,18 +703,6 @@ __global__ __launch_bounds__(512, 2) void featurize_split_kernel(FeatArgs a, uns
                 s_atoms[lane][15] = __builtin_bit_cast(float, s_misc[0][lane]);
             }
         }
-#else
-        if (tid < TM_TILE) {
-            s_ix[buf][0][tid] = g_idx;
-            s_ix[buf][1][tid] = g_dpos;
-#pragma unroll
-            for (int k = 0; k < 15; ++k) s_atoms[tid][k] = g_at[k];
-            s_atoms[tid][15] = g_d0;
-        } else if (tid == 64) {
-#pragma unroll
-            for (int k = 0; k < 15; ++k) s_self[k] = g_at[k];
-        }
-#endif
     };
     // 25 atom-pair distances of the 48 neighbours: 1 200 values over 512 threads
     auto dist_one = [&](int e) {
@@ -770,7 +719,6 @@ __global__ __launch_bounds__(512, 2) void featurize_split_kernel(FeatArgs a, uns
         return p == 0 ? d0 : D;
     };
     auto distances = [&]() {
-#if TM_FEAT_DIST2
         // the two full rounds as one straight-line block (their LDS reads and square roots overlap), then the round of 176
         const float D0 = dist_one(tid), D1 = dist_one(tid + 512);
         const int m0 = tid / 25, m1 = (tid + 512) / 25;
@@ -780,18 +728,11 @@ __global__ __launch_bounds__(512, 2) void featurize_split_kernel(FeatArgs a, uns
             const int e = tid + 1024, mm = e / 25;
             s_dist[mm][e - 25 * mm] = dist_one(e);
         }
-#else
-        for (int e = tid; e < TM_TILE * 25; e += 512) {
-            const int mm = e / 25;
-            s_dist[mm][e - 25 * mm] = dist_one(e);
-        }
-#endif
     };
 
     const TileRange tr = xcd_tile_range(a.T);
     int i = tr.begin, cur = 0;
     if constexpr (KNN) {
-#if TM_FEAT_DMA
         __shared__ unsigned s_selk[64][2];
         if (tm_bid() == 0 && tid == 0 && kf.init.status_zero) *kf.init.status_zero = 0;     // (as knn_kernel: nothing in this launch ORs into it)
         if (wu == 0)
@@ -799,10 +740,8 @@ __global__ __launch_bounds__(512, 2) void featurize_split_kernel(FeatArgs a, uns
                 knn_residue<4>(nullptr, s_selk, a.X, kf.mask, kf.offsets, kf.N, kf.max_len, kf.K, kf.E_idx, kf.D_nb, nullptr, kf.init, kf.sel_rows, r, lane);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the row is in L2 before any wavefront of this workgroup asks for it
         __syncthreads();
-#endif
     }
     if (i < tr.end) {
-#if TM_FEAT_DMA
         if (wu == 7) {
             const int nb = lane < TM_TILE ? lane : TM_TILE - 1;
             tm_glds4((a.E_idx + (size_t)i * TM_KS) + nb, tm_lds_addr(s_list[0]));
@@ -812,9 +751,6 @@ __global__ __launch_bounds__(512, 2) void featurize_split_kernel(FeatArgs a, uns
         fetch(i, 0, i + tr.step < tr.end ? i + tr.step : -1);
         landed();
         __syncthreads();
-#else
-        fetch(i);
-#endif
         publish(0, 0);
         __syncthreads();
         distances();
@@ -824,7 +760,6 @@ __global__ __launch_bounds__(512, 2) void featurize_split_kernel(FeatArgs a, uns
     for (; i < tr.end; i += tr.step) {
         const int inext = i + tr.step;
         const bool has_next = inext < tr.end;
-#if TM_FEAT_DMA
         if (tid < TM_TILE * 4) {                                // K columns 400..415: this tile's positional features
             const int row = tid >> 2, c = tid & 3;
             store_split<SP, TM_TILE, RBFP_ROWB>(rbf, row, 100 + c, ld4(&s_pos[s_ix[cur][1][row]][4 * c]));
@@ -833,13 +768,6 @@ __global__ __launch_bounds__(512, 2) void featurize_split_kernel(FeatArgs a, uns
 #pragma unroll
         for (int rb = 0; rb < 3; ++rb) acc[rb][0] = f4{0.f, 0.f, 0.f, 0.f};
         if (has_next) fetch(inext, cur ^ 1, inext + tr.step < tr.end ? inext + tr.step : -1);   // tile i's list is in s_list[cur]
-#else
-        if (tid < TM_TILE * 2 * SP::NP) {                       // zero the K padding (columns 400..415) of every plane row
-            const int p = tid / (TM_TILE * 2), rem = tid - p * (TM_TILE * 2);
-            *reinterpret_cast<u4 *>(rbf + plane_off8<TM_TILE, RBFP_ROWB>(p, rem >> 1, 50 + (rem & 1))) = u4{0u, 0u, 0u, 0u};
-        }
-        f4 acc[3][1];
-#endif
         // 16 Gaussians per pair, 4 per thread-iteration (:1111-1119). (Measured and dropped in the spill-free kernel: stepping
         // (row, quad) instead of dividing by 100 — 8 simple ops for 3 integer multiplies, +1.6 %; the v_fma_mix split, nil.)
 #if TM_ABL_NOGAUSS
@@ -865,17 +793,10 @@ __global__ __launch_bounds__(512, 2) void featurize_split_kernel(FeatArgs a, uns
                 *reinterpret_cast<u2 *>(rbf + plane_off4<TM_TILE, RBFP_ROWB>(p, mm, c)) = u2{lo2[p], hi2[p]};
         }
         mark(0);
-#if TM_FEAT_DMA
         landed();
-#endif
         __syncthreads();                                       // RBF planes complete; s_dist / s_atoms consumed; DMA pieces in LDS
         mark(1);
 
-#if !TM_FEAT_DMA
-        if (has_next) fetch(inext);
-#pragma unroll
-        for (int rb = 0; rb < 3; ++rb) acc[rb][0] = ld4(a.pos_table + s_ix[cur][1][16 * rb + m] * TM_H + ncol);
-#endif
         mma_tile_split<SP, 13, 1, 3, TM_TILE, RBFP_ROWB, 13, 0, true, TM_FEAT_PF>(rbf, wedge, acc, lane);
 #pragma unroll
         for (int rb = 0; rb < 3; ++rb) row_stats_partial1b(acc[rb][0], &s_stat[16 * rb + m][2 * wv], q);
@@ -1044,11 +965,7 @@ int launch_knn(const float *X, const float *mask, const int32_t *offsets, int N,
 }
 
 // kf != nullptr: the k-NN rows are computed inside the launch (featurize_fusable says when that form exists)
-bool featurize_fusable(const tmpnn_weights *w, int64_t T) {
-    if (tm_matmul_mode() != TM_MM_F16X2 || T <= 0 || T > (int64_t)tm_num_cus() || !TM_FEAT_DMA) return false;
-    for (int b = 0; b < 4; ++b) if (!tm_find_wimg(w->edge_w + 16 + 128 * b)) return false;
-    return tm_find_wimg(w->We_w) != nullptr;
-}
+bool featurize_fusable(int mode, int64_t T) { return mode == TM_MM_F16X2 && T > 0 && T <= (int64_t)tm_num_cus(); }
 
 int launch_featurize(const tmpnn_weights *w, const float *X, const int32_t *ridx, const int32_t *cenc,
                      const int32_t *E_idx, const float *D_nb, int64_t T, float *h_E, float *E_opt, hipStream_t st,
@@ -1059,27 +976,25 @@ int launch_featurize(const tmpnn_weights *w, const float *X, const int32_t *ridx
     a.hE = h_E; a.E_opt = E_opt; a.T = (int)T;
     for (int i = 0; i < 16; ++i)   // torch.linspace(2, 22, 16): double arithmetic, symmetric halves, cast to fp32
         a.mu[i] = i < 8 ? (float)(2.0 + (20.0 / 15.0) * i) : (float)(22.0 - (20.0 / 15.0) * (15 - i));
-    bool img = tm_matmul_mode() == TM_MM_F16X2;
-    for (int b = 0; b < 4; ++b) { a.img_e[b] = img ? tm_find_wimg(w->edge_w + 16 + 128 * b) : nullptr; img = img && a.img_e[b]; }
-    a.img_we = img ? tm_find_wimg(w->We_w) : nullptr;
-    img = img && a.img_we;
-    static const bool img_on = TM_DBG_FLAG("TMPNN_FEAT_IMG", true);
-    if (!img_on) img = false;
+    const bool h2 = tm_matmul_mode() == TM_MM_F16X2;
+    if (h2) {
+        for (int b = 0; b < 4; ++b) a.img_e[b] = tm_find_wimg(w->edge_w + 16 + 128 * b);
+        a.img_we = tm_find_wimg(w->We_w);
+        if (!a.img_e[0] || !a.img_e[1] || !a.img_e[2] || !a.img_e[3] || !a.img_we)
+            return tm_set_error(TMPNN_E_INVALID, "edge_featurize: f16x2 handle without the fragment images of W_edge / W_e");
+    }
     const int64_t cap = tm_num_cus();
-    static const int nw = TM_DBG_INT("TMPNN_FEAT_WAVES", 8);
     // (two split-precision bf16x3 forms of this kernel — half-width tiles, and one 126 KB single-pass plane tile — were
     //  measured and dropped: generating + splitting the 19 200 Gaussians into three planes and the extra LDS traffic cost as
     //  much as the shorter 400->128 GEMM saved: 1.07-1.08 ms vs 1.08 ms)
     tm_prof_begin("featurize", st);
-    static const bool split_ok = TM_DBG_FLAG("TMPNN_FEAT_SPLIT", true);
 #ifdef TMPNN_DEBUG_BUILD
     static const bool feat_prof = TM_DBG_FLAG("TMPNN_FEAT_PROF", false);
-    if (tm_matmul_mode() == TM_MM_F16X2 && split_ok && feat_prof) {       // debug build: phase timing of workgroup 0 (synchronises!)
+    if (h2 && !knn && feat_prof) {                               // debug build: phase timing of workgroup 0 (synchronises!)
         static unsigned long long *d_prof = nullptr;
         if (!d_prof) (void)hipMalloc(&d_prof, 16 * sizeof(unsigned long long));
         (void)hipMemsetAsync(d_prof, 0, 16 * sizeof(unsigned long long), st);
-        if (img) featurize_split_kernel<SplitH2, true, true><<<(int)(T < cap ? T : cap), 512, 0, st>>>(a, d_prof);
-        else featurize_split_kernel<SplitH2, true><<<(int)(T < cap ? T : cap), 512, 0, st>>>(a, d_prof);
+        featurize_split_kernel<SplitH2, true><<<(int)(T < cap ? T : cap), 512, 0, st>>>(a, d_prof);
         unsigned long long h[16];
         (void)hipMemcpy(h, d_prof, sizeof(h), hipMemcpyDeviceToHost);
         fprintf(stderr, "featurize phases (cycles, wg 0): gauss %llu bar %llu gemm1+stats %llu publish %llu bar %llu ln+split %llu dist %llu bar %llu gemm2+store %llu\n",
@@ -1088,28 +1003,15 @@ int launch_featurize(const tmpnn_weights *w, const float *X, const int32_t *ridx
         return tm_check_launch("edge_featurize");
     }
 #endif
-    if (knn && !(tm_matmul_mode() == TM_MM_F16X2 && split_ok && img && T <= cap)) {
-        // (only reachable in the debug library, whose switches can take the image / split form away after featurize_fusable said yes)
-        tm_prof_end(st);
-        const int rc = launch_knn(X, knn->mask, knn->offsets, knn->N, T, knn->max_len, knn->K, knn->E_idx, knn->D_nb, nullptr, st, knn->init);
-        if (rc != TMPNN_OK) return rc;
-        return launch_featurize(w, X, ridx, cenc, E_idx, D_nb, T, h_E, E_opt, st, nullptr);
-    }
     if (knn) {                                                   // small launch: k-NN + featurizer in one (the caller asked featurize_fusable)
         static const bool sel_rows = TM_DBG_FLAG("TMPNN_KNN_SEL", true);
         KnnFuseArgs kf{knn->mask, knn->offsets, knn->N, knn->max_len, knn->K, knn->E_idx, knn->D_nb, knn->init, sel_rows ? 1 : 0};
-        featurize_split_kernel<SplitH2, false, true, true><<<(int)T, 512, 0, st>>>(a, nullptr, kf);
+        featurize_split_kernel<SplitH2, false, true><<<(int)T, 512, 0, st>>>(a, nullptr, kf);
         tm_prof_end(st);
         return tm_check_launch("knn_featurize_fused");
     }
-    if (tm_matmul_mode() == TM_MM_F16X2 && split_ok) {
-        if (img) featurize_split_kernel<SplitH2, false, true><<<(int)(T < cap ? T : cap), 512, 0, st>>>(a);
-        else featurize_split_kernel<SplitH2><<<(int)(T < cap ? T : cap), 512, 0, st>>>(a);
-        tm_prof_end(st);
-        return tm_check_launch("edge_featurize");
-    }
-    if (nw == 4) featurize_kernel<4><<<(int)(T < cap ? T : cap), 256, 0, st>>>(a);
-    else featurize_kernel<8><<<(int)(T < cap ? T : cap), 512, 0, st>>>(a);
+    if (h2) featurize_split_kernel<SplitH2><<<(int)(T < cap ? T : cap), 512, 0, st>>>(a);
+    else featurize_kernel<<<(int)(T < cap ? T : cap), 512, 0, st>>>(a);
     tm_prof_end(st);
     return tm_check_launch("edge_featurize");
 }

@@ -124,8 +124,8 @@ __global__ __launch_bounds__(TM_THREADS, 1) void head_kernel(HeadArgs a) {
     }
 }
 
-template <typename SP, int NRB, bool IMG>
-__global__ __launch_bounds__(512, 2) void head8_split_kernel(HeadArgs a) { head8_body<SP, NRB, IMG>(a); }
+template <typename SP, int NRB>
+__global__ __launch_bounds__(512, 2) void head8_split_kernel(HeadArgs a) { head8_body<SP, NRB>(a); }
 
 // log_softmax(W_out h + b): one wavefront per residue, lane a < 21 owns logit a.
 __global__ __launch_bounds__(TM_THREADS) void log_probs_kernel(const float *__restrict__ W, const float *__restrict__ b,
@@ -200,22 +200,23 @@ int launch_prep_tables(tmpnn_weights *w, hipStream_t st) {
     return tm_check_launch("prep_tables");
 }
 
-HeadArgs tm_head_args(const tmpnn_weights *w, const float *hA, const float *hB, const int32_t *S, int64_t T, float *ddg, float *z_opt,
-                      int32_t *status, const int32_t *maxlen_probe) {
-    HeadArgs a{w->conv_center, w->conv_b, w->mlp_w[0], w->mlp_b[0], w->mlp_w[1], w->mlp_b[1], w->mlp_w[2], w->mlp_b[2],
-               w->ddg_w, w->ddg_b, w->Ws_w, hA, hB, S, ddg, z_opt, (int)T, status, maxlen_probe, {}};
-    bool have_img = tm_matmul_mode() == TM_MM_F16X2;
-    for (int u = 0; u < 12 && have_img; ++u) {
+int tm_head_args(HeadArgs &a, const tmpnn_weights *w, const float *hA, const float *hB, const int32_t *S, int64_t T, float *ddg,
+                 float *z_opt, int32_t *status, const int32_t *maxlen_probe) {
+    a = HeadArgs{w->conv_center, w->conv_b, w->mlp_w[0], w->mlp_b[0], w->mlp_w[1], w->mlp_b[1], w->mlp_w[2], w->mlp_b[2],
+                 w->ddg_w, w->ddg_b, w->Ws_w, hA, hB, S, ddg, z_opt, (int)T, status, maxlen_probe, {}};
+    if (tm_matmul_mode() != TM_MM_F16X2) return TMPNN_OK;
+    for (int u = 0; u < 12; ++u) {
         a.img[u] = tm_find_wimg(u < 9 ? w->conv_center + (size_t)128 * (u / 3) * 384 + 128 * (u % 3) : w->mlp_w[0] + 128 * (u - 9));
-        have_img = a.img[u] != nullptr;
+        if (!a.img[u]) return tm_set_error(TMPNN_E_INVALID, "ddg_head: f16x2 handle without the fragment image of unit %d", u);
     }
-    if (!have_img) for (int u = 0; u < 12; ++u) a.img[u] = nullptr;
-    return a;
+    return TMPNN_OK;
 }
 
 int launch_head(const tmpnn_weights *w, const float *hA, const float *hB, const int32_t *S, int64_t T, float *ddg,
                 float *z_opt, int32_t *status, hipStream_t st, const int32_t *maxlen_probe) {
-    HeadArgs a = tm_head_args(w, hA, hB, S, T, ddg, z_opt, status, maxlen_probe);
+    HeadArgs a;
+    const int rc = tm_head_args(a, w, hA, hB, S, T, ddg, z_opt, status, maxlen_probe);
+    if (rc != TMPNN_OK) return rc;
     // tile height for load balance, as in node_update: 1 workgroup per CU, ~1.2 MB of weights streamed per tile
     const int64_t slots = tm_num_cus();
     int best_rows = 48;
@@ -228,15 +229,10 @@ int launch_head(const tmpnn_weights *w, const float *hA, const float *hB, const 
     const int64_t tiles = (T + best_rows - 1) / best_rows;
     const int grid = (int)(tiles < slots ? tiles : slots);
     tm_prof_begin("head", st);
-    static const bool split_ok = TM_DBG_FLAG("TMPNN_HEAD_SPLIT", true);
-    if (tm_matmul_mode() == TM_MM_F16X2 && split_ok) {
-#define TM_HEAD8(NRB)                                                             \
-    if (a.img[0]) head8_split_kernel<SplitH2, NRB, true><<<grid, 512, 0, st>>>(a); \
-    else head8_split_kernel<SplitH2, NRB, false><<<grid, 512, 0, st>>>(a)
-        if (best_rows == 16) { TM_HEAD8(1); }
-        else if (best_rows == 32) { TM_HEAD8(2); }
-        else { TM_HEAD8(3); }
-#undef TM_HEAD8
+    if (tm_matmul_mode() == TM_MM_F16X2) {
+        if (best_rows == 16) head8_split_kernel<SplitH2, 1><<<grid, 512, 0, st>>>(a);
+        else if (best_rows == 32) head8_split_kernel<SplitH2, 2><<<grid, 512, 0, st>>>(a);
+        else head8_split_kernel<SplitH2, 3><<<grid, 512, 0, st>>>(a);
         tm_prof_end(st);
         return tm_check_launch("ddg_head");
     }

@@ -18,20 +18,20 @@ struct HeadArgs {
     const int32_t *maxlen_probe;          // fused forward: E_idx [T,48]; slot 0 < 0 marks a row the k-NN kernel left empty because its
                                           // protein is longer than max_len -> TMPNN_STATUS_MAXLEN (the k-NN kernel zeroes the word and
                                           // therefore cannot OR into it itself: no memset launch in front of the forward)
-    const char *img[12];                  // f16 fragment images of the 12 GEMM units (WImg, tmpnn_internal.h) or all null
+    const char *img[12];                  // f16 fragment images of the 12 GEMM units (WImg, tmpnn_internal.h); f16x2 only
 };
 
 __device__ __forceinline__ f4 relu4(f4 v) { return f4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)}; }
 
 // ------------------------------------------------------------------------------------------------
 // head, 8-wavefront f16x2 form (default in f16x2 mode): the 384 -> 384 centre-tap GEMM and the 384 -> 64 layer (12 GEMM
-// units of K = 128) on the 16-bit matrix cores, 16 output columns per wavefront, the fp32 weight fragment of unit u+1
+// units of K = 128) on the 16-bit matrix cores, 16 output columns per wavefront, the fragment image of unit u+1
 // fetched from L2 under the MFMAs of unit u (as in node_update8_split_kernel); the two tiny layers (64 -> 32 -> 21) and
 // the ddG epilogue are the fp32 code of head_kernel.
 // ------------------------------------------------------------------------------------------------
 // The kernel's body as a device function (round 6): head8_split_kernel runs it on its own, node_head_fused_kernel (tmpnn_node.hip) behind
 // the last decoder layer's node update of the same 16 residues (small launches: one launch less per forward).
-template <typename SP, int NRB, bool IMG>
+template <typename SP, int NRB>
 __device__ __forceinline__ void head8_body(const HeadArgs &a) {
     constexpr int ROWS = 16 * NRB, PLT = SP::NP * ROWS * 256;
     static_assert(PLT >= ROWS * TM_H * 4, "fp32 tiles of the small layers are aliased on dead x planes");
@@ -44,49 +44,24 @@ __device__ __forceinline__ void head8_body(const HeadArgs &a) {
     const int n_tiles = (a.T + ROWS - 1) / ROWS;
     const float dw = a.ddg_w[0], db = a.ddg_b[0];
 
-    // units 0..8: conv_center rows 128 g + 16 wv + m, columns 128 kt (u = 3 g + kt); units 9..11: w1 rows 16 wv + m (wv < 4)
-    auto src = [&](int u) -> const float * {
-        if (u < 9) return a.conv_center + (size_t)(128 * (u / 3) + 16 * wv + m) * 384 + 128 * (u % 3) + 8 * q;
-        return a.w1 + (size_t)(16 * (wv & 3) + m) * 384 + 128 * (u - 9) + 8 * q;
-    };
+    // units 0..8: conv_center rows 128 g + 16 wv + m, columns 128 kt (u = 3 g + kt); units 9..11: w1 rows 16 wv + m (wv < 4).
+    // A unit's fragment is its ready-made f16 planes, 8 coalesced loads (see node_update8_split_kernel).
+    static_assert(SP::NP == 2, "the fragment images hold the two f16x2 planes");
     f4 raw[8];
     auto issue = [&](int u) {
-        if constexpr (IMG) {                                     // ready-made planes, 8 coalesced loads (see node_update8_split_kernel)
-            const char *p = a.img[u] + (size_t)wv * 8192 + lane * 16;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                raw[2 * c] = *reinterpret_cast<const f4 *>(p + 2048 * c);
-                raw[2 * c + 1] = *reinterpret_cast<const f4 *>(p + 2048 * c + 1024);
-            }
-            return;
-        }
-        const float *p = src(u);
+        const char *p = a.img[u] + (size_t)wv * 8192 + lane * 16;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            raw[2 * c] = ld4(p + 32 * c);
-            raw[2 * c + 1] = ld4(p + 32 * c + 4);
+            raw[2 * c] = *reinterpret_cast<const f4 *>(p + 2048 * c);
+            raw[2 * c + 1] = *reinterpret_cast<const f4 *>(p + 2048 * c + 1024);
         }
     };
     WFragS<SP> wf[1][4];
     auto split_raw = [&]() {
-        if constexpr (IMG) {
-            static_assert(SP::NP == 2, "the fragment images hold the two f16x2 planes");
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                wf[0][c].p[0] = __builtin_bit_cast(u4, raw[2 * c]);
-                wf[0][c].p[1] = __builtin_bit_cast(u4, raw[2 * c + 1]);
-            }
-            return;
-        }
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            unsigned w4[4][SP::NP];
-            SP::split2(f2{raw[2 * c].x, raw[2 * c].y}, w4[0]);
-            SP::split2(f2{raw[2 * c].z, raw[2 * c].w}, w4[1]);
-            SP::split2(f2{raw[2 * c + 1].x, raw[2 * c + 1].y}, w4[2]);
-            SP::split2(f2{raw[2 * c + 1].z, raw[2 * c + 1].w}, w4[3]);
-#pragma unroll
-            for (int p = 0; p < SP::NP; ++p) wf[0][c].p[p] = u4{w4[0][p], w4[1][p], w4[2][p], w4[3][p]};
+            wf[0][c].p[0] = __builtin_bit_cast(u4, raw[2 * c]);
+            wf[0][c].p[1] = __builtin_bit_cast(u4, raw[2 * c + 1]);
         }
     };
 

@@ -20,15 +20,11 @@ struct DecW {
 // instead of 16-row gathers of fp32 that are split on the fly (tmpnn_split.hip: node_update8_split_kernel).
 #define TM_WIMG_BYTES 65536
 #define TM_N_WIMG 110          // enc: W3 + 4 W_in + 4 W_out + W1a W1c W11a W11c + W1e W2 W11e W12 W13 (18) x 3; dec: W3 + 4 + 4 + W1a W1d + W1e W2 (13) x 3; head: 9 blocks of the centre tap + 3 of both_out.1; featurizer: 4 blocks of W_edge[:, 16:416] + W_e
-#define TM_N_WIMGP 21          // the message kernels' W1e and W2 (3 encoder + 3 decoder layers) again with the K axis permuted inside every 32-deep step: 12;
-                               // + room for the edge update's W11e, W12, W13 (3 layers), which only the debug library builds (tmpnn_edge_wave.hip; the
-                               // same struct layout in both libraries: A/B variants link debug objects of a few files with the shipped ones)
+#define TM_N_WIMGP 12          // the message kernels' W1e and W2 (3 encoder + 3 decoder layers) again with the K axis permuted inside every 32-deep step
                                // (msg8_wave_kernel, tmpnn_msg.hip): element e of lane group q <-> k = 32 c + 16 (e >> 2) + 4 q + (e & 3)
-#ifdef TMPNN_DEBUG_BUILD
-#define TM_N_WIMGP_BUILT 21    // images a handle of THIS library builds (and its packed buffer has room for)
-#else
-#define TM_N_WIMGP_BUILT 12
-#endif
+// The image rule: an f16x2 handle always carries every fragment image above (tmpnn_weights_create builds them all); an f16x2 launcher
+// looks up the images it needs and refuses with TMPNN_E_INVALID when one is missing; the f16x2 kernels assume them. fp32 and bf16x3
+// handles build no images and do not take this path.
 struct WImg { const float *base; const char *img; };      // base = address of the block's element [0][0] in the raw tensor
 
 struct tmpnn_weights {
@@ -78,7 +74,7 @@ int launch_centrality(const float *X, const float *mask, const int32_t *offsets,
                       int32_t *out, hipStream_t st);
 // small launches: the k-NN rows computed inside the featurizer launch (E_idx / D_nb are then OUTPUTS of it)
 struct KnnFuse { const float *mask; const int32_t *offsets; int N, max_len, K; int32_t *E_idx; float *D_nb; KnnInit init; };
-bool featurize_fusable(const tmpnn_weights *w, int64_t T);
+bool featurize_fusable(int mode, int64_t T);
 int launch_featurize(const tmpnn_weights *w, const float *X, const int32_t *ridx, const int32_t *cenc,
                      const int32_t *E_idx, const float *D_nb, int64_t T, float *h_E, float *E_opt, hipStream_t st,
                      const KnnFuse *knn = nullptr);
@@ -118,8 +114,8 @@ int launch_enc_edge(const EncW &e, const float *P, float *hE, const int32_t *E_i
 // tmpnn_head.hip
 int launch_head(const tmpnn_weights *w, const float *hA, const float *hB, const int32_t *S, int64_t T, float *ddg,
                 float *z_opt, int32_t *status, hipStream_t st, const int32_t *maxlen_probe = nullptr);
-HeadArgs tm_head_args(const tmpnn_weights *w, const float *hA, const float *hB, const int32_t *S, int64_t T, float *ddg, float *z_opt,
-                      int32_t *status, const int32_t *maxlen_probe);
+int tm_head_args(HeadArgs &a, const tmpnn_weights *w, const float *hA, const float *hB, const int32_t *S, int64_t T, float *ddg,
+                 float *z_opt, int32_t *status, const int32_t *maxlen_probe);
 int launch_log_probs(const tmpnn_weights *w, const float *h, int64_t T, float *out, int32_t *status, hipStream_t st,
                      const int32_t *maxlen_probe = nullptr);
 int launch_seq_embed(const tmpnn_weights *w, const int32_t *S, int64_t T, float *hS, hipStream_t st);
@@ -144,13 +140,8 @@ int launch_edge_msg_fused(const EncW &e, const float *P_edge, float *hE, const i
                           const float *W2, const float *b2, const float *P_msg, const float *mask, int64_t T, float *Ssum, float *cnt,
                           hipStream_t st);
 int launch_selftest(int32_t *status, hipStream_t st);
-// tmpnn_edge_wave.hip: f16x2 edge update of large launches, one wavefront per 16-row block (same bits as the 8-wavefront forms)
-struct EdgeArgsB;
-bool enc_edge_wave_wanted(int64_t T);
-int launch_enc_edge_wave(const EdgeArgsB &a, int64_t T, hipStream_t st);
-
 int tm_num_cus();
-// Kernel-form switches (TMPNN_KNN_REG, TMPNN_NODE_DEEP, TMPNN_FEAT_SPLIT ...) and the per-phase timers (TMPNN_*_PROF, which
+// Kernel-form switches (TMPNN_KNN_REG, TMPNN_NODE_DEEP, TMPNN_FUSE_SMALL ...) and the per-phase timers (TMPNN_*_PROF, which
 // hipMalloc a scratch buffer, copy it back with a blocking hipMemcpy and print) exist ONLY in the debug variant of the library
 //   python -m thermompnn_amd.build --variant debug -DTMPNN_DEBUG_BUILD      (-> libtmpnn_debug.so; select with TMPNN_LIB)
 // The shipped libtmpnn.so picks every kernel form from the launch size and the handle's precision alone: its launchers never

@@ -528,17 +528,19 @@ int launch_node_update(const float *W3, const float *b3, const float *n1w, const
     for (int k = 0; k < 2; ++k)
         a.proj[k] = ps[k] ? ProjSpec{ps[k]->Wa, ps[k]->lda, ps[k]->ba, ps[k]->Wc, ps[k]->ldc, ps[k]->P, ps[k]->add_tab, ps[k]->add_idx}
                           : ProjSpec{nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr};
-    {   // pre-built fragment images (all 13 units or none)
+    if (tm_matmul_mode() == TM_MM_F16X2) {   // fragment images of the 13 GEMM units (none for an absent projection)
         const float *base[13] = {W3};
         for (int c = 0; c < 4; ++c) { base[1 + 2 * c] = Win + (size_t)128 * c * 128; base[2 + 2 * c] = Wout + 128 * c; }
         for (int k = 0; k < 2; ++k) { base[9 + 2 * k] = ps[k] ? ps[k]->Wa : nullptr; base[10 + 2 * k] = ps[k] ? ps[k]->Wc : nullptr; }
-        bool all = true;
         for (int u = 0; u < 13; ++u) {
             a.img[u] = base[u] ? tm_find_wimg(base[u]) : nullptr;
-            if (base[u] && !a.img[u]) all = false;
+            if (base[u] && !a.img[u])
+                return tm_set_error(TMPNN_E_INVALID, "node_update: f16x2 handle without the fragment image of unit %d", u);
         }
-        static const bool img_on = TM_DBG_FLAG("TMPNN_NODE_IMG", true);
-        if (!all || !img_on) for (int u = 0; u < 13; ++u) a.img[u] = nullptr;
+        tm_prof_begin("node_update", st);
+        const int rc = launch_node_update_split(a, T, st, head, head_ran);
+        tm_prof_end(st);
+        return rc;
     }
     tm_prof_begin("node_update", st);
     // Tile height (16 / 32 / 48 residues) chosen for load balance: the grid offers 2 workgroup slots per CU, every
@@ -551,12 +553,6 @@ int launch_node_update(const float *W3, const float *b3, const float *n1w, const
         const int64_t tiles = (T + rows - 1) / rows, rounds = (tiles + slots - 1) / slots;
         const int64_t cost = rounds * (rows + 16);
         if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_rows = rows; }
-    }
-    static const bool split_ok = TM_DBG_FLAG("TMPNN_NODE_SPLIT", true);
-    if (tm_matmul_mode() == TM_MM_F16X2 && split_ok) {
-        const int rc = launch_node_update_split(a, T, st, head, head_ran);
-        tm_prof_end(st);
-        return rc;
     }
     const int64_t tiles = (T + best_rows - 1) / best_rows;
     if (best_rows == 16) node_update_kernel<1><<<grid_for(tiles, 2), TM_THREADS, 0, st>>>(a);

@@ -481,13 +481,15 @@ int launch_msg_split(int mode, bool dec, const float *W1e, int ld1, const float 
     const bool h2 = mode == TM_MM_F16X2;
     MsgArgsB a{W1e, ld1, W2, b2, P, hE, E_idx, mask, Ssum, cnt, (int)T, h2 ? tm_find_wimg(W1e) : nullptr, h2 ? tm_find_wimg(W2) : nullptr,
                h2 ? tm_find_wimgp(W1e) : nullptr, h2 ? tm_find_wimgp(W2) : nullptr, 0};
+    if (h2 && !(a.imgp1 && a.imgp2))
+        return tm_set_error(TMPNN_E_INVALID, "msg_split: f16x2 handle without the K-permuted fragment images of W1e / W2");
     const int64_t cap = tm_num_cus();
     const bool off32 = T < ((int64_t)1 << 22);       // projection table < 4 GB: 32-bit gather offsets
     // f16x2, large launches: whole multiples of 8 residues per workgroup go one wavefront per residue, the rest (< 8 per workgroup) to
     // the 8-wavefront form behind it — same K order, same summation order, same bits (tests: config 3 against single-protein forwards)
     static const int wave_min = TM_DBG_INT("TMPNN_MSG_WAVE_MIN", TM_MSG_WAVE_MIN);   // (debug library: 0 = from one residue per wavefront)
     int64_t Tw = 0;
-    if (h2 && a.imgp1 && a.imgp2 && cap % 8 == 0) {
+    if (h2 && cap % 8 == 0) {
         const int64_t q = T / (8 * cap);
         if (q >= (wave_min > 0 ? wave_min : 1)) Tw = q * 8 * cap;
         else if (wave_min == 0 && T > 0) Tw = T;      // (debug switch: everything, whatever the size)

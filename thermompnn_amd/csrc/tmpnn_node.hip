@@ -10,11 +10,11 @@
 
 // ------------------------------------------------------------------------------------------------
 // node_update, 8-wavefront f16x2 form (default): one workgroup per CU, up to 64 residues per tile, 16 output columns per
-// wavefront. A tile runs 9..13 dependent GEMMs whose weights stream from L2: the raw fp32 fragment of GEMM u+1 (32 VGPRs)
-// is requested before the MFMAs of GEMM u and split into f16 planes after them, so no GEMM waits on an L2 round trip
+// wavefront. A tile runs 9..13 dependent GEMMs whose weights stream from L2: the fragment image of GEMM u+1 (32 VGPRs)
+// is requested during the MFMAs of GEMM u, so no GEMM waits on an L2 round trip
 // (the 4-wavefront form above does, 13 times per tile); the taller tile halves the weight traffic per residue.
 // ------------------------------------------------------------------------------------------------
-template <typename SP, int NRB, bool IMG, bool PROF = false>
+template <typename SP, int NRB, bool PROF = false>
 __global__ __launch_bounds__(512, 2) void node_update8_split_kernel(NodeArgs a, unsigned long long *prof = nullptr) {
     int n_mark = 0;
     auto mark = [&]() {                 // TMPNN_NODE_PROF=1: cycle stamps of thread 0 of workgroup 0 at every stage boundary (first tile)
@@ -44,79 +44,41 @@ __global__ __launch_bounds__(512, 2) void node_update8_split_kernel(NodeArgs a, 
     const bool has0 = a.proj[0].P != nullptr, has1 = a.proj[1].P != nullptr;
 
     // GEMM units of a tile: 0 = W3; 1 + 2c = W_in chunk c, 2 + 2c = W_out chunk c; 9 / 10 = projection 0 (A / C half);
-    // 11 / 12 = projection 1. src(u) = this lane's fragment row: W[(n0 + m) * ld + k0 + 8 q ...]
-    auto src = [&](int u) -> const float * {
-        const size_t r = (size_t)(16 * wv + m);
-        if (u == 0) return a.W3 + r * TM_H + 8 * q;
-        if (u <= 8) {
-            const int c = (u - 1) >> 1;
-            return ((u - 1) & 1) ? a.Wout + r * 512 + 128 * c + 8 * q : a.Win + (r + 128 * c) * TM_H + 8 * q;
-        }
-        const ProjSpec &ps = a.proj[(u - 9) >> 1];
-        return ((u - 9) & 1) ? ps.Wc + r * ps.ldc + 8 * q : ps.Wa + r * ps.lda + 8 * q;
-    };
-    // With pre-built fragment images (NodeArgs::img, built by tmpnn_weights_create) a unit's fragment is 8 coalesced 1 KB
-    // loads of ready-made f16 planes; without them (standalone callers) it is gathered from 16 fp32 rows per load and split
-    // on the fly. Measured (MI355X): 22.9 vs 30.3 us per launch on a single L=256 protein — the strided gathers ran at a
-    // third of the L2 -> CU fill rate and every one of the 9-13 dependent GEMM units of a tile waited for them.
+    // 11 / 12 = projection 1. A unit's fragment is 8 coalesced 1 KB loads of its pre-built f16 planes (NodeArgs::img, built by
+    // tmpnn_weights_create). Measured (MI355X): 22.9 vs 30.3 us per launch on a single L=256 protein against gathering 16 fp32 rows
+    // per load and splitting on the fly — the strided gathers ran at a third of the L2 -> CU fill rate and every one of the 9-13
+    // dependent GEMM units of a tile waited for them.
+    static_assert(SP::NP == 2, "the fragment images hold the two f16x2 planes");
     f4 raw[8];
     auto issue = [&](int u) {
-        if constexpr (IMG) {
-            const char *p = a.img[u] + (size_t)wv * 8192 + lane * 16;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                raw[2 * c] = *reinterpret_cast<const f4 *>(p + 2048 * c);
-                raw[2 * c + 1] = *reinterpret_cast<const f4 *>(p + 2048 * c + 1024);
-            }
-            return;
-        }
-        const float *p = src(u);
+        const char *p = a.img[u] + (size_t)wv * 8192 + lane * 16;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            raw[2 * c] = ld4(p + 32 * c);
-            raw[2 * c + 1] = ld4(p + 32 * c + 4);
+            raw[2 * c] = *reinterpret_cast<const f4 *>(p + 2048 * c);
+            raw[2 * c + 1] = *reinterpret_cast<const f4 *>(p + 2048 * c + 1024);
         }
     };
     WFragS<SP> wf[1][4];
     auto split_raw = [&]() {
-        if constexpr (IMG) {
-            static_assert(SP::NP == 2, "the fragment images hold the two f16x2 planes");
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                wf[0][c].p[0] = __builtin_bit_cast(u4, raw[2 * c]);
-                wf[0][c].p[1] = __builtin_bit_cast(u4, raw[2 * c + 1]);
-            }
-            return;
-        }
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            unsigned w4[4][SP::NP];
-            SP::split2(f2{raw[2 * c].x, raw[2 * c].y}, w4[0]);
-            SP::split2(f2{raw[2 * c].z, raw[2 * c].w}, w4[1]);
-            SP::split2(f2{raw[2 * c + 1].x, raw[2 * c + 1].y}, w4[2]);
-            SP::split2(f2{raw[2 * c + 1].z, raw[2 * c + 1].w}, w4[3]);
-#pragma unroll
-            for (int p = 0; p < SP::NP; ++p) wf[0][c].p[p] = u4{w4[0][p], w4[1][p], w4[2][p], w4[3][p]};
+            wf[0][c].p[0] = __builtin_bit_cast(u4, raw[2 * c]);
+            wf[0][c].p[1] = __builtin_bit_cast(u4, raw[2 * c + 1]);
         }
     };
     const int first_proj = has0 ? 9 : 11;                       // first projection unit, if any
-    // GEMM of the unit in `wf` with the NEXT unit's fragment requested meanwhile (u_next < 0: none). With images (round 6) its eight
-    // requests ride one by one behind the GEMM's MFMA steps instead of standing in a row in front of it (~85 cycles of issue each).
+    // GEMM of the unit in `wf` with the NEXT unit's fragment requested meanwhile (u_next < 0: none). Its eight requests ride one by
+    // one behind the GEMM's MFMA steps instead of standing in a row in front of it (~85 cycles of issue each).
     auto gemm = [&](const char *plane, f4 (&ac)[NRB][1], int u_next) {
-        if constexpr (IMG) {
-            const char *pn = a.img[u_next < 0 ? 0 : u_next] + (size_t)wv * 8192 + lane * 16;     // (none: unit 0 again, unconditional requests)
-            constexpr int NS = 4 * NRB;
-            mma_tile_split_ride<SP, 4, NRB, TM_NODE_PF, ROWS>(plane, wf, ac, lane, [&](auto S) {
-                constexpr int s = decltype(S)::value;
-                static_for<0, 8>([&](auto K) {
-                    constexpr int k = decltype(K)::value;
-                    if constexpr ((k * NS) / 8 == s) raw[k] = *reinterpret_cast<const f4 *>(pn + 2048 * (k >> 1) + 1024 * (k & 1));
-                });
+        const char *pn = a.img[u_next < 0 ? 0 : u_next] + (size_t)wv * 8192 + lane * 16;     // (none: unit 0 again, unconditional requests)
+        constexpr int NS = 4 * NRB;
+        mma_tile_split_ride<SP, 4, NRB, TM_NODE_PF, ROWS>(plane, wf, ac, lane, [&](auto S) {
+            constexpr int s = decltype(S)::value;
+            static_for<0, 8>([&](auto K) {
+                constexpr int k = decltype(K)::value;
+                if constexpr ((k * NS) / 8 == s) raw[k] = *reinterpret_cast<const f4 *>(pn + 2048 * (k >> 1) + 1024 * (k & 1));
             });
-        } else {
-            if (u_next >= 0) issue(u_next);
-            mma_tile_split<SP, 4, 1, NRB, ROWS, 256, 4, 0, true, TM_NODE_PF>(plane, wf, ac, lane);
-        }
+        });
     };
 
     int tile = tm_bid();
@@ -496,7 +458,7 @@ __global__ __launch_bounds__(512) void node_update8_deep_kernel(NodeArgs a, unsi
 __global__ __launch_bounds__(512) void node_head_fused_kernel(NodeArgs a, HeadArgs h) {
     node_deep_body<0, TM_NODE_DEEP_D>(a, nullptr);
     __syncthreads();
-    head8_body<SplitH2, 1, true>(h);
+    head8_body<SplitH2, 1>(h);
 }
 
 int launch_node_update_split(const NodeArgs &a, int64_t T, hipStream_t st, const HeadArgs *head, bool *head_ran) {
@@ -515,7 +477,7 @@ int launch_node_update_split(const NodeArgs &a, int64_t T, hipStream_t st, const
     const int64_t tiles = (T + best_rows - 1) / best_rows;
     const int grid = (int)(tiles < slots ? tiles : slots);
     static const int deep = TM_DBG_INT("TMPNN_NODE_DEEP", 1);
-    if (deep && a.img[0] && (T + 15) / 16 <= slots) {           // one 16-row tile per workgroup: the deep-prefetch form
+    if (deep && (T + 15) / 16 <= slots) {                      // one 16-row tile per workgroup: the deep-prefetch form
         const int g16 = (int)((T + 15) / 16);
         const int np = (a.proj[0].P != nullptr) + (a.proj[1].P != nullptr);
         NodeArgs b = a;
@@ -543,7 +505,7 @@ int launch_node_update_split(const NodeArgs &a, int64_t T, hipStream_t st, const
             return tm_check_launch("node_update8_deep");
         }
 #endif
-        if (np == 0 && head && head->img[0]) {                  // + the ddG head of the same rows (the caller checked node_head_fusable)
+        if (np == 0 && head) {                                  // + the ddG head of the same rows (the caller checked node_head_fusable)
             node_head_fused_kernel<<<g16, 512, 0, st>>>(b, *head);
             if (head_ran) *head_ran = true;
             return tm_check_launch("node_head_fused");
@@ -555,11 +517,11 @@ int launch_node_update_split(const NodeArgs &a, int64_t T, hipStream_t st, const
     }
 #ifdef TMPNN_DEBUG_BUILD
     static const bool prof4 = TM_DBG_FLAG("TMPNN_NODE_PROF", false);
-    if (prof4 && a.img[0] && best_rows == 64) {                 // debug build: stage stamps of workgroup 0 (synchronises!)
+    if (prof4 && best_rows == 64) {                             // debug build: stage stamps of workgroup 0 (synchronises!)
         static unsigned long long *d_prof = nullptr;
         if (!d_prof) (void)hipMalloc(&d_prof, 32 * sizeof(unsigned long long));
         (void)hipMemsetAsync(d_prof, 0, 32 * sizeof(unsigned long long), st);
-        node_update8_split_kernel<SplitH2, 4, true, true><<<grid, 512, 0, st>>>(a, d_prof);
+        node_update8_split_kernel<SplitH2, 4, true><<<grid, 512, 0, st>>>(a, d_prof);
         unsigned long long h[32];
         (void)hipMemcpy(h, d_prof, sizeof(h), hipMemcpyDeviceToHost);
         fprintf(stderr, "node_update8 (64 rows) stages (cycles since entry, wg 0):");
@@ -568,22 +530,17 @@ int launch_node_update_split(const NodeArgs &a, int64_t T, hipStream_t st, const
         return tm_check_launch("node_update8_split");
     }
 #endif
-#define TM_NODE8(NRB)                                                                    \
-    if (a.img[0]) node_update8_split_kernel<SplitH2, NRB, true><<<grid, 512, 0, st>>>(a); \
-    else node_update8_split_kernel<SplitH2, NRB, false><<<grid, 512, 0, st>>>(a)
     switch (best_rows) {
-        case 16: TM_NODE8(1); break;
-        case 32: TM_NODE8(2); break;
-        case 48: TM_NODE8(3); break;
-        default: TM_NODE8(4); break;
+        case 16: node_update8_split_kernel<SplitH2, 1><<<grid, 512, 0, st>>>(a); break;
+        case 32: node_update8_split_kernel<SplitH2, 2><<<grid, 512, 0, st>>>(a); break;
+        case 48: node_update8_split_kernel<SplitH2, 3><<<grid, 512, 0, st>>>(a); break;
+        default: node_update8_split_kernel<SplitH2, 4><<<grid, 512, 0, st>>>(a); break;
     }
-#undef TM_NODE8
     return tm_check_launch("node_update8_split");
 }
 
 // the fused launch exists for f16x2 handles with fragment images, when every workgroup has one 16-row tile (the deep form's condition)
 bool node_head_fusable(int mode, int64_t T) {
     static const int deep = TM_DBG_INT("TMPNN_NODE_DEEP", 1);
-    static const bool split = TM_DBG_FLAG("TMPNN_NODE_SPLIT", true) && TM_DBG_FLAG("TMPNN_HEAD_SPLIT", true);   // (the debug library's fp32-form switches)
-    return mode == TM_MM_F16X2 && deep && split && T > 0 && (T + 15) / 16 <= (int64_t)tm_num_cus();
+    return mode == TM_MM_F16X2 && deep && T > 0 && (T + 15) / 16 <= (int64_t)tm_num_cus();
 }

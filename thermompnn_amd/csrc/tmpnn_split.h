@@ -456,7 +456,6 @@ struct EdgeArgsB {
     const int32_t *E_idx;
     int T;
     const char *img11, *img12, *img13;      // fragment images of the three weights (f16x2 only) or null
-    const char *imgp11, *imgp12, *imgp13;   // ... their K-permuted forms (perm_c4) or null
 };
 
 struct MsgArgsB {

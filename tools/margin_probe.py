@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Which op thins the margin of E / h_E0 / h_E_final in f16x2 mode? Featurizer outputs of the golden
 structures against the float64 truth and the reference-equal fp32 oracle, for: the f16x2 featurizer (split GEMMs + packed
-Gaussians), the fp32 featurizer inside f16x2 mode (debug library, TMPNN_FEAT_SPLIT=0) and the fp32 engine.
+Gaussians), the fp32 featurizer of the bf16x3 engine and the fp32 engine.
     python tools/margin_probe.py        (GPU box; spawns itself once per configuration)"""
 import json
 import os
@@ -41,10 +41,8 @@ if __name__ == "__main__":
     if len(sys.argv) > 1:
         worker(sys.argv[1])
         sys.exit(0)
-    dbg = os.path.join(REPO, "thermompnn_amd", "libtmpnn_debug.so")
     res = {}
     for name, prec, env in (("f16x2 (shipped: split GEMMs + packed Gaussians)", "f16x2", {}),
-                            ("f16x2 engine, fp32 featurizer (debug lib, TMPNN_FEAT_SPLIT=0)", "f16x2", {"TMPNN_LIB": dbg, "TMPNN_FEAT_SPLIT": "0"}),
                             ("bf16x3 engine (fp32 featurizer)", "bf16x3", {}), ("fp32 engine", "fp32", {})):
         r = subprocess.run([sys.executable, __file__, prec], env=dict(os.environ, **env), capture_output=True, text=True)
         line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]

@@ -7,7 +7,8 @@ cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/pmc_traffic; rm -rf $OUT; mkdir -p $OUT
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/$c -o $c -- python $R/tools/pmc_workload.py > $OUT/$c.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/$c -o $c -- python $R/tools/pmc_workload.py > $OUT/$c.log 2>&1 \
+    || { echo "$c pass failed (exit $?): see $OUT/$c.log"; exit 1; }
 done
 python - <<PY
 import csv, glob, json, collections, sys
