@@ -6,6 +6,12 @@ from thermompnn_amd.transfer_model import TransferModel
 from thermompnn_amd.weights import load_thermompnn_checkpoint
 
 
+def train(cfg):
+    """The reference's train(cfg) for the frozen-encoder recipe (thermompnn_amd.train.train)."""
+    from thermompnn_amd.train import train as _train
+    return _train(cfg)
+
+
 class TransferModelPL:
     def __init__(self, cfg):
         self.cfg = cfg

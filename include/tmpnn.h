@@ -194,6 +194,39 @@ int tmpnn_ddg_head_generic(const float *const *hidden, int n_final, const float 
                            const float *const *mlp_b, const int32_t *dims, const float *ddg_w, const float *ddg_b, float *ddg,
                            float *z_opt, void *workspace, size_t workspace_bytes, int32_t *status_opt, tmpnn_stream_t stream);
 
+/* ---- training of the ddG head with ProteinMPNN frozen (train_thermompnn.py:48-113; thermompnn_amd/train.py drives it) ----
+ * Parameters, gradients and the AdamW moments each live in ONE flat fp32 slab holding the head's trainable tensors in state-dict
+ * order: [light_attention.feature_convolution.weight [D0,D0,9], .bias, attention_convolution.weight, .bias] (lightattn only),
+ * both_out Linear l weight [dims[l+1], dims[l]] + bias for l < n_layers, ddg_out.weight, ddg_out.bias. dims as
+ * tmpnn_ddg_head_generic (HOST array). tmpnn_head_slab_numel -> its length (-1 = bad dims). */
+int64_t tmpnn_head_slab_numel(int n_final, int lightattn, int n_layers, const int32_t *dims);
+size_t tmpnn_head_train_workspace_bytes(int64_t M, int n_final, int lightattn, int n_layers, const int32_t *dims);   /* 0 = bad */
+/* One training step's forward + backward over M labelled mutants of one protein: mutant i reads feature row rows[i] of feat
+ * [n_feat, D0] (the [h_dec(last) | ... | W_s[S]] rows of head_concat; indices are clamped to [0, n_feat)), mutant / wild-type
+ * amino-acid indices mut[i], wt[i] (< 21) and target[i]. Dropout on the centre-tap output (LightAttention only): keep_in [M, D0]
+ * (0 / 1, an injected mask) or, with keep_in NULL and p_drop > 0, the in-kernel counter-based generator keyed on (seed, step,
+ * mutant row, column) — keep_out [M, D0] (may be NULL) receives its mask. Writes loss[0] = mean (pred - target)^2, pred_opt [M],
+ * and every gradient entry that can be non-zero into grads (the 8 non-centre taps and the attention convolution are never
+ * written: zero the slab once). Deterministic: no floating-point atomics. All of feat..target, params, grads, keep_*, loss, pred
+ * are device memory. */
+int tmpnn_head_train_step(const float *feat, int64_t n_feat, const int32_t *rows, const int32_t *mut, const int32_t *wt,
+                          const float *target, int64_t M, int n_final, int lightattn, int n_layers, const int32_t *dims,
+                          int subtract_mut, const float *params, float *grads, int64_t slab_numel, float p_drop,
+                          const float *keep_in, float *keep_out, uint64_t seed, uint64_t step, float *loss, float *pred_opt,
+                          void *workspace, size_t workspace_bytes, tmpnn_stream_t stream);
+/* Eval-mode predictions (no dropout) pred [M] for the same mutant description. */
+int tmpnn_head_eval(const float *feat, int64_t n_feat, const int32_t *rows, const int32_t *mut, const int32_t *wt, int64_t M,
+                    int n_final, int lightattn, int n_layers, const int32_t *dims, int subtract_mut, const float *params,
+                    int64_t slab_numel, float *pred, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream);
+/* torch.optim.AdamW (decoupled decay, torch/optim/adam.py's order) over the slab: segment s = [seg_begin[s], seg_begin[s+1])
+ * with learning rate seg_lr[s] and kind seg_kind[s]: 1 = full update, 2 = only the centre taps (offset % 9 == 4) of a
+ * convolution weight have a gradient, 0 = structurally zero gradient (decay only; m, v stay 0 and are not read). step counts
+ * from 1. seg_begin [n_seg + 1], seg_kind, seg_lr are HOST arrays; n_seg <= 32. */
+int tmpnn_adamw_step(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t numel, int n_seg,
+                     const int64_t *seg_begin, const int32_t *seg_kind, const double *seg_lr, double beta1, double beta2,
+                     double eps, double weight_decay, int64_t step, tmpnn_stream_t stream);
+
+
 /* ---- the fused path ------------------------------------------------------------------------------
  * Everything TransferModel.forward does on the device for a ragged batch of N proteins
  * (transfer_model.py:75-121 + protein_mpnn_utils.py:1222-1277), one call, 18 launches on `stream` (14 when every workgroup has at most one residue tile).

@@ -1,0 +1,307 @@
+"""Head training on the MI355X: gradients against the imported reference and a float64 restatement, the fused AdamW against
+torch.optim.AdamW, determinism and the dropout generator, learning, and train(cfg) end to end."""
+import ctypes as C
+import os
+import pickle
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN, load_golden
+
+pytestmark = pytest.mark.gpu
+AA20 = "ACDEFGHIKLMNPQRSTVWY"
+RELEASED = dict(hidden_dims=[64, 32], num_final_layers=2, lightattn=True)
+
+
+def _model(tmp_path, head=None, subtract=True, seed=0, head_seed=None):
+    """TransferModel with synthetic weights (ProteinMPNN from ``seed``, head from ``head_seed``) on cuda:0."""
+    from thermompnn_amd import weights
+    from thermompnn_amd.train import Config
+    from thermompnn_amd.transfer_model import TransferModel
+    head = head or RELEASED
+    sd = weights.synthetic_state_dict(seed, head=head)
+    if head_seed is not None:
+        sd.update({k: v for k, v in weights.synthetic_state_dict(head_seed, head=head).items() if not k.startswith("prot_mpnn.")})
+    vdir = os.path.join(str(tmp_path), "vanilla_model_weights")
+    os.makedirs(vdir, exist_ok=True)
+    weights.save_vanilla_checkpoint(os.path.join(vdir, "v_48_020.pt"), weights.split_transfer_state_dict(sd)[0], 48)
+    cfg = Config.wrap(dict(model=dict(hidden_dims=list(head["hidden_dims"]), subtract_mut=subtract, num_final_layers=head["num_final_layers"],
+                                      freeze_weights=True, load_pretrained=True, lightattn=head["lightattn"]),
+                           platform=dict(thermompnn_dir=str(tmp_path))))
+    model = TransferModel(cfg)
+    model.load_state_dict(sd)
+    return model.cuda()
+
+
+def _golden_item():
+    from thermompnn_amd.datasets import Mutation
+    from thermompnn_amd.pdb_io import alt_parse_PDB
+    g = load_golden("train_2OCJ_A")
+    pdb = alt_parse_PDB(os.path.join(GOLDEN, "2OCJ.pdb"), "A")
+    muts = [Mutation(int(p), AA20[w], AA20[m], None if np.isnan(t) else torch.tensor([float(t)]), "2OCJ")
+            for p, w, m, t in zip(g["positions"], g["wildtype"], g["mutation"], g["targets"])]
+    return g, pdb, muts
+
+
+def _mix(x):
+    x = np.asarray(x, np.uint64)
+    with np.errstate(over="ignore"):
+        x = x ^ (x >> np.uint64(30))
+        x = x * np.uint64(0xBF58476D1CE4E5B9)
+        x = x ^ (x >> np.uint64(27))
+        x = x * np.uint64(0x94D049BB133111EB)
+        x = x ^ (x >> np.uint64(31))
+    return x
+
+
+def numpy_keep_mask(seed, step, M, D, p=0.25):
+    """The documented generator of csrc/tmpnn_train.hip, restated: keep = (mix(k2 ^ (row << 32 | col)) >> 40) >= round(p 2^24)."""
+    with np.errstate(over="ignore"):
+        k1 = _mix(np.uint64(seed) ^ np.uint64(0x9E3779B97F4A7C15))
+        k2 = _mix(k1 + np.uint64(step))
+    rows = np.arange(M, dtype=np.uint64)[:, None] << np.uint64(32)
+    cols = np.arange(D, dtype=np.uint64)[None, :]
+    h = _mix(k2 ^ (rows | cols))
+    return ((h >> np.uint64(40)) >= np.uint64(round(p * 2 ** 24))).astype(np.float32)
+
+
+def test_gradients_and_loss_match_the_reference_golden(tmp_path):
+    from thermompnn_amd.train import HeadTrainer
+    g, pdb, muts = _golden_item()
+    tr = HeadTrainer(_model(tmp_path))
+    split = tr.build_cache([(pdb, muts)])
+    assert split.counts == [int(np.isfinite(g["targets"]).sum())]
+    for tag, keep in (("ones", np.ones_like(g["keep_p25"])), ("p25", g["keep_p25"])):
+        tr.grad.zero_()
+        loss = tr.forward_backward(split, 0, keep_in=torch.from_numpy(keep).cuda())
+        assert abs(float(loss) - float(g[f"{tag}_loss"])) <= 1e-4 * float(g[f"{tag}_loss"]), tag
+        got = {"conv_center": tr.tensor("light_attention.feature_convolution.weight", "grad")[g["centre_rows"], :, 4],
+               "conv_bias": tr.tensor("light_attention.feature_convolution.bias", "grad")}
+        for name in tr.shapes:
+            if name.startswith("both_out") or name == "ddg_out.weight":
+                got[name] = tr.tensor(name, "grad")
+        for name, t in got.items():
+            ref = g[f"{tag}_{name}"]
+            err = float(np.abs(t.cpu().numpy() - ref).max())
+            assert err <= 1e-4 * float(np.abs(ref).max()), (tag, name, err, float(np.abs(ref).max()))
+        w = tr.tensor("light_attention.feature_convolution.weight", "grad")
+        assert float(w[:, :, [0, 1, 2, 3, 5, 6, 7, 8]].abs().max()) == 0.0
+        assert float(tr.tensor("light_attention.attention_convolution.weight", "grad").abs().max()) == 0.0
+        assert float(tr.tensor("light_attention.attention_convolution.bias", "grad").abs().max()) == 0.0
+        assert float(tr.tensor("ddg_out.bias", "grad").abs().max()) == 0.0
+
+
+def _float64_grads(tr, split, keep, p_drop=0.25):
+    """The head in float64 torch.autograd on the trainer's own device-cached features: -> (loss, {name: grad})."""
+    P = {k: tr.tensor(k).double().clone().requires_grad_(True) for k in tr.shapes}
+    rows = split.rows.long()
+    x = split.feat.double()[rows]
+    mut, wt, t = split.mut.long(), split.wt.long(), split.target.double()
+    h = x
+    if tr.lightattn:
+        h = x @ P["light_attention.feature_convolution.weight"][:, :, 4].T + P["light_attention.feature_convolution.bias"]
+        h = h * keep.double() / (1.0 - p_drop)
+    for i in range(tr.n_layers):
+        h = torch.relu(h) @ P[f"both_out.{2 * i + 1}.weight"].T + P[f"both_out.{2 * i + 1}.bias"]
+    out = h * P["ddg_out.weight"].view(()) + P["ddg_out.bias"].view(())
+    ar = torch.arange(len(rows), device=out.device)
+    pred = out[ar, mut] - out[ar, wt] if tr.subtract else out[ar, mut]
+    loss = ((pred - t) ** 2).mean()
+    loss.backward()
+    return float(loss.detach()), {k: v.grad if v.grad is not None else torch.zeros_like(v) for k, v in P.items()}
+
+
+@pytest.mark.parametrize("head,subtract", [(RELEASED, True), (dict(hidden_dims=[128], num_final_layers=1, lightattn=True), True),
+                                           (dict(hidden_dims=[64, 32], num_final_layers=0, lightattn=True), True),
+                                           (dict(hidden_dims=[64, 32], num_final_layers=3, lightattn=True), False),
+                                           (dict(hidden_dims=[32], num_final_layers=1, lightattn=False), True),
+                                           (dict(hidden_dims=[], num_final_layers=2, lightattn=False), False)])
+def test_gradients_match_a_float64_restatement(tmp_path, head, subtract):
+    from thermompnn_amd.train import HeadTrainer
+    _, pdb, muts = _golden_item()
+    tr = HeadTrainer(_model(tmp_path, head, subtract), seed=3)
+    split = tr.build_cache([(pdb, muts)])
+    M = split.counts[0]
+    keep = torch.empty((M, tr.dims[0]), device="cuda") if tr.lightattn else None
+    loss = tr.forward_backward(split, 0, keep_out=keep, step=5)
+    ref_loss, ref = _float64_grads(tr, split, keep)
+    if tr.subtract:             # analytically zero (the bias cancels); float64 autograd leaves a 1e-17 residue of d_i - d_i
+        assert float(ref["ddg_out.bias"].abs().max()) <= 1e-12
+        ref["ddg_out.bias"] = torch.zeros_like(ref["ddg_out.bias"])
+    assert abs(float(loss) - ref_loss) <= 1e-5 * ref_loss
+    worst = 0.0
+    for name, r in ref.items():
+        got = tr.tensor(name, "grad").double()
+        scale = float(r.abs().max())
+        if scale == 0.0:
+            assert float(got.abs().max()) == 0.0, name
+            continue
+        rel = float((got - r).abs().max()) / scale
+        worst = max(worst, rel)
+        assert rel <= 1e-5, (name, rel)
+    print(f"head {head} subtract {subtract}: loss {float(loss):.6g}, worst gradient error / max|g| = {worst:.2e}")
+
+
+def test_fused_adamw_matches_torch():
+    from thermompnn_amd import _lib
+    lib = _lib.load()
+    gen = torch.Generator().manual_seed(0)
+    shapes = [((8, 8, 9), 2, 0), ((300,), 1, 0), ((57, 13), 1, 1), ((700,), 0, 1), ((5,), 1, 1)]     # (shape, kind, group)
+    lrs = [1e-3, 3e-3]
+    p0 = [torch.randn(s, generator=gen) for s, _, _ in shapes]
+    tparams = [p.clone().cuda().requires_grad_(True) for p in p0]
+    opt = torch.optim.AdamW([{"params": [tparams[i] for i in range(len(shapes)) if shapes[i][2] == g], "lr": lrs[g]} for g in (0, 1)])
+    slab = torch.cat([p.reshape(-1) for p in p0]).cuda()
+    grad, m, v = torch.zeros_like(slab), torch.zeros_like(slab), torch.zeros_like(slab)
+    sizes = [p.numel() for p in p0]
+    begins = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    cb = (C.c_int64 * len(begins))(*begins)
+    ck = (C.c_int32 * len(shapes))(*[k for _, k, _ in shapes])
+    cl = (C.c_double * len(shapes))(*[lrs[g] for _, _, g in shapes])
+    for step in range(1, 6):
+        gs = []
+        for (s, kind, _), tp in zip(shapes, tparams):
+            gg = torch.randn(s, generator=gen)
+            if kind == 0:
+                gg.zero_()
+            elif kind == 2:
+                centre = torch.zeros(s)
+                centre[:, :, 4] = gg[:, :, 4]
+                gg = centre
+            tp.grad = gg.cuda()
+            gs.append(gg.reshape(-1))
+        grad.copy_(torch.cat(gs).cuda())
+        opt.step()
+        _lib.check(lib.tmpnn_adamw_step(C.c_void_p(slab.data_ptr()), C.c_void_p(grad.data_ptr()), C.c_void_p(m.data_ptr()),
+                                        C.c_void_p(v.data_ptr()), slab.numel(), len(shapes), cb, ck, cl, 0.9, 0.999, 1e-8, 0.01, step,
+                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)), "adamw")
+    want = torch.cat([p.detach().reshape(-1) for p in tparams])
+    want_m = torch.cat([opt.state[p]["exp_avg"].reshape(-1) for p in tparams])
+    want_v = torch.cat([opt.state[p]["exp_avg_sq"].reshape(-1) for p in tparams])
+    assert float(((slab - want).abs() / want.abs().clamp_min(1e-30)).max()) <= 1e-6
+    assert float((m - want_m).abs().max()) <= 1e-6 * float(want_m.abs().max())
+    assert float((v - want_v).abs().max()) <= 1e-6 * float(want_v.abs().max())
+    # decay-only tensor: p0 * prod(1 - lr wd), in fp32 step by step; its moments stay exactly zero
+    seg = slice(int(begins[3]), int(begins[4]))
+    d = np.float32(1.0 - lrs[1] * 0.01)
+    ref = p0[3].numpy().copy()
+    for _ in range(5):
+        ref = ref * d
+    assert np.array_equal(slab[seg].cpu().numpy(), ref)
+    assert float(m[seg].abs().max()) == 0.0 and float(v[seg].abs().max()) == 0.0
+    # non-centre taps of the centre-only segment: also decay only, bit-identical to torch's full update with zero gradient
+    conv = slab[:sizes[0]].view(8, 8, 9).cpu()
+    tconv = tparams[0].detach().cpu()
+    assert torch.equal(conv[:, :, [0, 1, 2, 3, 5, 6, 7, 8]], tconv[:, :, [0, 1, 2, 3, 5, 6, 7, 8]])
+
+
+def test_steps_are_deterministic_and_the_dropout_generator_is_documented(tmp_path):
+    from thermompnn_amd.datasets import Mutation
+    from thermompnn_amd.synthetic import synthetic_pdb_dict
+    from thermompnn_amd.train import HeadTrainer
+    _, pdb, muts = _golden_item()
+    model = _model(tmp_path)
+    slabs = []
+    for seed in (11, 11, 12):
+        tr = HeadTrainer(model, seed=seed)
+        split = tr.build_cache([(pdb, muts)])
+        tr.begin_epoch(20)
+        for _ in range(20):
+            assert tr.step(split, 0)
+        slabs.append(tr.slab.clone())
+    assert torch.equal(slabs[0], slabs[1])
+    assert not torch.equal(slabs[0], slabs[2])
+    # the in-kernel mask = the numpy restatement, bit for bit, over > 10^6 draws
+    p = synthetic_pdb_dict(200, seed=4)
+    seq = p["seq"]
+    big = [Mutation(i, seq[i], a, torch.tensor([0.1]), "syn") for i in range(len(seq)) for a in AA20 if a != seq[i]]
+    tr = HeadTrainer(model, seed=123456789)
+    split = tr.build_cache([([p], big)])
+    M = split.counts[0]
+    keep = torch.empty((M, 384), device="cuda")
+    tr.forward_backward(split, 0, keep_out=keep, step=77)
+    got = keep.cpu().numpy()
+    assert M * 384 >= 10 ** 6
+    assert np.array_equal(got, numpy_keep_mask(123456789, 77, M, 384))
+    assert abs(float(got.mean()) - 0.75) <= 0.005
+
+
+def test_a_student_head_learns_the_teacher(tmp_path):
+    """Teacher: the head of synthetic weight seed 1; student: seed 0 (same ProteinMPNN). Targets = teacher's ssm_table."""
+    from thermompnn_amd.datasets import Mutation
+    from thermompnn_amd.synthetic import synthetic_pdb_dict
+    from thermompnn_amd.train import HeadTrainer
+    rng = np.random.default_rng(0)
+    prots = [synthetic_pdb_dict(int(L), seed=100 + i) for i, L in enumerate(rng.integers(40, 73, 24))]
+    teacher = _model(tmp_path / "t", head_seed=1)
+    items = []
+    for p in prots:
+        table = teacher.ssm_table([p]).cpu().numpy()
+        seq = p["seq"]
+        items.append(([p], [Mutation(i, seq[i], a, torch.tensor([float(table[i, AA20.index(a)])]), "syn")
+                            for i in range(len(seq)) for a in AA20 if a != seq[i]]))
+    tr = HeadTrainer(_model(tmp_path / "s"), seed=0, learn_rate=1e-3)
+    train_split, val_split = tr.build_cache(items[:20]), tr.build_cache(items[20:])
+    mse0 = tr.evaluate(val_split)["mse"]
+    order_rng = np.random.default_rng(1)
+    hist = []
+    for epoch in range(15):
+        tr.begin_epoch(len(train_split))
+        for i in order_rng.permutation(len(train_split)):
+            tr.step(train_split, int(i))
+        hist.append(tr.evaluate(val_split)["mse"])
+    print(f"teacher-student: val MSE {mse0:.4g} -> {hist[-1]:.4g} in 15 epochs ({[round(h, 4) for h in hist]})")
+    assert hist[-1] * 5 <= mse0, (mse0, hist)
+
+
+def test_train_end_to_end_writes_a_loadable_checkpoint(tmp_path):
+    from thermompnn_amd import weights
+    from thermompnn_amd.pdb_io import alt_parse_PDB
+    from thermompnn_amd.thermompnn_benchmarking import get_trained_model
+    from thermompnn_amd.train import Config, train
+    _model(tmp_path)                                                   # writes vanilla_model_weights/v_48_020.pt (seed 0)
+    pdbs = tmp_path / "pdbs"
+    pdbs.mkdir()
+    rng = np.random.default_rng(5)
+    rows = []
+    for name, src in (("2OCJ", "2OCJ.pdb"), ("2OCJgap", "2OCJ_gap_chainA.pdb")):
+        (pdbs / f"{name}.pdb").write_bytes(open(os.path.join(GOLDEN, src), "rb").read())
+        seq = alt_parse_PDB(str(pdbs / f"{name}.pdb"), None)[0]["seq"]
+        for pos in rng.choice([i for i, c in enumerate(seq) if c in AA20], 40, replace=False):
+            rows.append((name, seq, int(pos), seq[pos], AA20[(AA20.index(seq[pos]) + 1 + int(rng.integers(19))) % 20],
+                         f"{rng.normal():.3f}"))
+    with open(tmp_path / "fireprot.csv", "w") as fh:
+        fh.write("pdb_id_corrected,pdb_sequence,pdb_position,wild_type,mutation,ddG\n")
+        for r in rows:
+            fh.write(",".join(str(x) for x in r) + "\n")
+    with open(tmp_path / "splits.pkl", "wb") as fh:
+        pickle.dump({"train": ["2OCJ"], "val": ["2OCJgap"], "test": []}, fh)
+    cfg = Config.wrap(dict(datasets=["fireprot"], training=dict(learn_rate=1e-3, epochs=1, lr_schedule=True,
+                                                                 checkpoint_dir=str(tmp_path / "checkpoints")),
+                           model=dict(hidden_dims=[64, 32], subtract_mut=True, num_final_layers=2, freeze_weights=True,
+                                      load_pretrained=True, lightattn=True),
+                           platform=dict(thermompnn_dir=str(tmp_path), accel="gpu"),
+                           data_loc=dict(fireprot_csv=str(tmp_path / "fireprot.csv"), fireprot_splits=str(tmp_path / "splits.pkl"),
+                                         fireprot_pdbs=str(pdbs))))
+    res = train(cfg, log=lambda s: None)
+    path = res["best_checkpoint"]
+    assert path and os.path.exists(path)
+    sp = res["history"][0]["val_ddG_spearman"]
+    assert os.path.basename(path) == f"test_epoch=00_val_ddG_spearman={sp:.02}.ckpt"
+    assert os.listdir(tmp_path / "checkpoints") == [os.path.basename(path)]
+    trainer, model = res["trainer"], res["model"]
+    from thermompnn_amd.datasets import FireProtDataset
+    val_ds = FireProtDataset(cfg, "val")
+    vsplit = trainer.build_cache([val_ds[0]])
+    want = trainer.predict(vsplit).cpu().numpy()
+    pdb, muts = val_ds[0]
+    live = [m for m in muts if m.ddG is not None]
+    pos = np.array([m.position for m in live])
+    aa = np.array([AA20.index(m.mutation) for m in live])
+    for m in (model, get_trained_model(path, cfg, override_custom=True).cuda()):
+        table = m.ssm_table(pdb).cpu().numpy()                     # a stale engine would still carry the initial head
+        assert float(np.abs(table[pos, aa] - want).max()) <= 1e-4
+    loaded = weights.load_thermompnn_checkpoint(path)
+    assert all(torch.equal(loaded[k].cuda(), v) for k, v in model.state_dict().items())

@@ -52,6 +52,12 @@ SIGNATURES = {
     "tmpnn_ddg_head": (_i, [_p, _p, _p, _p, _i64, _p, _p, _p, _p]),
     "tmpnn_head_generic_workspace_bytes": (_sz, [_i64, _i, _i, _p]),
     "tmpnn_ddg_head_generic": (_i, [_p, _i, _p, _p, _i64, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p, _p]),
+    "tmpnn_head_slab_numel": (_i64, [_i, _i, _i, _p]),
+    "tmpnn_head_train_workspace_bytes": (_sz, [_i64, _i, _i, _i, _p]),
+    "tmpnn_head_train_step": (_i, [_p, _i64, _p, _p, _p, _p, _i64, _i, _i, _i, _p, _i, _p, _p, _i64, C.c_float, _p, _p, C.c_uint64,
+                                   C.c_uint64, _p, _p, _p, _sz, _p]),
+    "tmpnn_head_eval": (_i, [_p, _i64, _p, _p, _p, _i64, _i, _i, _i, _p, _i, _p, _i64, _p, _p, _sz, _p]),
+    "tmpnn_adamw_step": (_i, [_p, _p, _p, _p, _i64, _i, _p, _p, _p, C.c_double, C.c_double, C.c_double, C.c_double, _i64, _p]),
     "tmpnn_pdb_parse": (_i, [C.c_char_p, C.c_char_p, C.POINTER(_p)]),
     "tmpnn_pdb_parse_batch": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, _i, C.POINTER(_p)]),
     "tmpnn_pdb_parse_batch_status": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, _i, C.POINTER(_p), _p]),

@@ -181,3 +181,96 @@ class FireProtDataset:
 
     def __iter__(self):
         return (self[i] for i in range(len(self)))
+
+
+class MegaScaleDataset:
+    """Mega-scale cDNA display set (/root/reference/datasets.py:61-164): the CSV ``cfg.data_loc.megascale_csv`` (columns ddG_ML,
+    mut_type, WT_name, aa_seq, dG_ML; read with the stdlib csv module) and the pickled splits ``cfg.data_loc.megascale_splits``
+    (read with ``weights.safe_unpickle``). Rows with ddG_ML '-' and insertions / deletions / multiple mutants (':') are dropped;
+    ``mut_type`` = wt + 1-based position + mutant; ddG = -ddG_ML. The structure is ``{megascale_pdbs}/{WT_name}.pdb`` with '.pdb'
+    stripped and '|' replaced by ':'; its sequence is replaced by the 'wt' row's aa_seq (lengths must agree). Each item is
+    (pdb, mutations) as the reference yields it."""
+
+    def __init__(self, cfg, split: str):
+        from .weights import safe_unpickle
+        self.cfg, self.split = cfg, split
+        reduce = cfg.get("reduce", "") if isinstance(cfg, dict) else getattr(cfg, "reduce", "")
+        if reduce not in (None, ""):
+            raise NotImplementedError("MegaScaleDataset: cfg.reduce (random subsampling) is not supported")
+        keep = ("ddG_ML", "mut_type", "WT_name", "aa_seq", "dG_ML")
+        rows = []
+        with open(cfg.data_loc.megascale_csv, newline="") as fh:
+            for r in _csv.DictReader(fh):
+                r = {k: r.get(k) for k in keep}
+                mt = r["mut_type"] or ""
+                if r["ddG_ML"] == "-" or "ins" in mt or "del" in mt or ":" in mt:
+                    continue
+                rows.append(r)
+        splits = safe_unpickle(cfg.data_loc.megascale_splits)
+        if not isinstance(splits, dict):
+            raise ValueError(f"{cfg.data_loc.megascale_splits}: expected a pickled dict of split name -> protein names")
+        if split == "all":
+            self.wt_names = list(splits["train"]) + list(splits["val"]) + list(splits["test"])
+        else:
+            self.wt_names = list(splits[split])
+        by_name = {}
+        for r in rows:
+            by_name.setdefault(r["WT_name"], []).append(r)
+        self.mut_rows, self.wt_seqs = {}, {}
+        for name in self.wt_names:
+            group = by_name.get(name, [])
+            wt_rows = [r for r in group if r["mut_type"] == "wt"]
+            if not wt_rows:
+                raise ValueError(f"MegaScaleDataset: {name} has no 'wt' row")
+            self.wt_seqs[name] = wt_rows[0]["aa_seq"]
+            self.mut_rows[name] = [r for r in group if r["mut_type"] != "wt"]
+
+    def __len__(self):
+        return len(self.wt_names)
+
+    def __getitem__(self, index):
+        import torch
+        from .pdb_io import alt_parse_PDB
+        wt_name = self.wt_names[index]
+        wt_seq = self.wt_seqs[wt_name]
+        pdb_name = wt_name.split(".pdb")[0].replace("|", ":")
+        pdb = alt_parse_PDB(_os.path.join(self.cfg.data_loc.megascale_pdbs, f"{pdb_name}.pdb"), None)
+        assert len(pdb[0]["seq"]) == len(wt_seq), f"{wt_name}: structure length {len(pdb[0]['seq'])} != wild-type {len(wt_seq)}"
+        pdb[0]["seq"] = wt_seq
+        mutations = []
+        for r in self.mut_rows[wt_name]:
+            mt = r["mut_type"]
+            assert len(r["aa_seq"]) == len(wt_seq)
+            wt, mut, idx = mt[0], mt[-1], int(mt[1:-1]) - 1
+            assert wt_seq[idx] == wt, f"{wt_name} {mt}: wild type is {wt_seq[idx]}"
+            assert r["aa_seq"][idx] == mut, f"{wt_name} {mt}: mutant sequence has {r['aa_seq'][idx]}"
+            ddg = -torch.tensor([float(r["ddG_ML"])], dtype=torch.float32)
+            mutations.append(Mutation(idx, wt, mut, ddg, pdb_name))
+        return pdb, mutations
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
+
+
+class ComboDataset:
+    """FireProt and / or Mega-scale of ``cfg.datasets`` concatenated (/root/reference/datasets.py:320-337)."""
+
+    def __init__(self, cfg, split: str):
+        self.datasets = []
+        if "fireprot" in cfg.datasets:
+            self.datasets.append(FireProtDataset(cfg, split))
+        if "megascale" in cfg.datasets:
+            self.datasets.append(MegaScaleDataset(cfg, split))
+
+    def __len__(self):
+        return sum(len(d) for d in self.datasets)
+
+    def __getitem__(self, index):
+        for d in self.datasets:
+            if index < len(d):
+                return d[index]
+            index -= len(d)
+        raise IndexError(index)
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
