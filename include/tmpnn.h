@@ -227,6 +227,34 @@ int tmpnn_adamw_step(float *params, const float *grads, float *exp_avg, float *e
                      double eps, double weight_decay, int64_t step, tmpnn_stream_t stream);
 
 
+/* ---- fine-tuning of ProteinMPNN together with the head (freeze_weights: false, train_thermompnn.py:88-113; thermompnn_amd/finetune.py)
+ * ONE flat fp32 slab: ProteinMPNN's tensors in state-dict order without W_out.weight / W_out.bias (not in the loss: never touched),
+ * then the head slab of tmpnn_head_slab_numel. With num_final_layers 0 the head reads W_s[S] only, and W_s is the one ProteinMPNN
+ * tensor in the slab. tmpnn_finetune_slab_numel -> its length (-1 = bad dims). */
+int64_t tmpnn_finetune_slab_numel(int n_final, int lightattn, int n_layers, const int32_t *dims);
+/* Length of the flat dropout-mask buffer of one protein of length L (keep_in / keep_out below; -1 = bad L): the 15 sites of
+ * csrc/tmpnn_finetune.hip in site order, [L, 128] per node site and [L K, 128] per edge site, K = min(48, L). */
+int64_t tmpnn_finetune_mask_numel(int64_t L);
+size_t tmpnn_finetune_workspace_bytes(int64_t L, int64_t M, int n_final, int lightattn, int n_layers, const int32_t *dims);  /* 0 = bad */
+/* One training step of one protein (L residues: X [L,4,3], S, mask, residue_idx, chain_enc as tied_featurize gives them) over M
+ * labelled mutants at residues pos[i] (mut / wt / target as tmpnn_head_train_step): the training forward (ProteinMPNN in train mode,
+ * dropout p_mpnn at its 15 sites; the head's centre-tap dropout p_head), loss[0] = mean (pred - target)^2, pred_opt [M], and every
+ * gradient of the slab into grads. ProteinMPNN's dropout: keep_in (0 / 1, injected) or the counter-based generator keyed on
+ * (seed, step, site, row, col), whose masks keep_out receives (may be NULL); the head's: head_keep_in [M, D0] or its own generator
+ * (tmpnn_head_train_step's, same seed / step). E_idx_opt [L, K] receives the k-NN graph and rows_opt [M, D0] the head rows
+ * [h_dec(last) | ... | W_s[S]]. Deterministic: no floating-point atomics, bit-identical reruns. All data pointers are device memory. */
+int tmpnn_finetune_step(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
+                        int64_t L, const int32_t *pos, const int32_t *mut, const int32_t *wt, const float *target, int64_t M,
+                        int n_final, int lightattn, int n_layers, const int32_t *dims, int subtract_mut, const float *params,
+                        float *grads, int64_t slab_numel, float p_mpnn, float p_head, const float *keep_in, float *keep_out,
+                        const float *head_keep_in, uint64_t seed, uint64_t step, float *loss, float *pred_opt, int32_t *E_idx_opt,
+                        float *rows_opt, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream);
+/* Eval-mode predictions (no dropout anywhere) pred [M] with the slab's weights; E_idx_opt / rows_opt as above. */
+int tmpnn_finetune_eval(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
+                        int64_t L, const int32_t *pos, const int32_t *mut, const int32_t *wt, int64_t M, int n_final, int lightattn,
+                        int n_layers, const int32_t *dims, int subtract_mut, const float *params, int64_t slab_numel, float *pred,
+                        int32_t *E_idx_opt, float *rows_opt, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream);
+
 /* ---- the fused path ------------------------------------------------------------------------------
  * Everything TransferModel.forward does on the device for a ragged batch of N proteins
  * (transfer_model.py:75-121 + protein_mpnn_utils.py:1222-1277), one call, 18 launches on `stream` (14 when every workgroup has at most one residue tile).

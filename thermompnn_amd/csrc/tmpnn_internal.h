@@ -123,6 +123,12 @@ int launch_head_generic(const float *const *hidden, int n_final, const float *Ws
                         const float *conv_b, int n_layers, const float *const *mlp_w, const float *const *mlp_b, const int32_t *dims,
                         const float *ddg_w, const float *ddg_b, float *ddg, float *z_opt, float *buf0, float *buf1, int32_t *status,
                         hipStream_t st);
+// tmpnn_train.hip: the launches of tmpnn_head_train_step (arguments validated by the caller); dfeat [M, D0] (may be null) receives
+// d loss / d feature row and needs rows[i] == i. tmpnn_finetune.hip back-propagates it into ProteinMPNN.
+int tm_head_train_core(const float *feat, int64_t n_feat, const int32_t *rows, const int32_t *mut, const int32_t *wt,
+                       const float *target, int64_t M, int lightattn, int n_layers, const int32_t *dims, int subtract_mut,
+                       const float *params, float *grads, float p_drop, const float *keep_in, float *keep_out, uint64_t seed,
+                       uint64_t step, float *loss, float *pred_opt, void *workspace, hipStream_t st, float *dfeat);
 int launch_range_check(const float *x, int64_t n, int32_t *status, hipStream_t st, const int32_t *maxlen_probe = nullptr,
                        int64_t T = 0);   // ORs TMPNN_STATUS_RANGE if any x is inf / NaN (+ the MAXLEN probe of the fused forward)
 int launch_prep_tables(tmpnn_weights *w, hipStream_t st);

@@ -382,7 +382,16 @@ extern "C" int tmpnn_head_train_step(const float *feat, int64_t n_feat, const in
     const size_t need = tmpnn_head_train_workspace_bytes(M, n_final, lightattn, n_layers, dims);
     if (!workspace || workspace_bytes < need)
         return tm_set_error(TMPNN_E_WORKSPACE, "head_train_step: workspace %zu < %zu bytes", workspace_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
+    return tm_head_train_core(feat, n_feat, rows, mut, wt, target, M, lightattn, n_layers, dims, subtract_mut, params, grads, p_drop,
+                              keep_in, keep_out, seed, step, loss, pred_opt, workspace, (hipStream_t)stream, nullptr);
+}
+
+// The launches of one head training step (arguments already validated). dfeat [M, D0] (may be null): d loss / d feature row of
+// every mutant, for a caller that back-propagates further (tmpnn_finetune.hip); it needs rows[i] == i (feat holds the mutants' rows).
+int tm_head_train_core(const float *feat, int64_t n_feat, const int32_t *rows, const int32_t *mut, const int32_t *wt,
+                       const float *target, int64_t M, int lightattn, int n_layers, const int32_t *dims, int subtract_mut,
+                       const float *params, float *grads, float p_drop, const float *keep_in, float *keep_out, uint64_t seed,
+                       uint64_t step, float *loss, float *pred_opt, void *workspace, hipStream_t st, float *dfeat) {
     const TrLayout L = tr_layout(lightattn, n_layers, dims);
     const TrWs w = tr_carve(workspace, M, lightattn, n_layers, dims);
     const int D0 = dims[0], Mi = (int)M, nf = (int)n_feat;
@@ -411,6 +420,13 @@ extern "C" int tmpnn_head_train_step(const float *feat, int64_t n_feat, const in
     }
     if (lightattn)   // centre tap of feature_convolution, strided into the [D0, D0, 9] weight: ldw 9 D0, wks 9, wk0 4
         tr_launch_wgrad(dY, feat, rows, nf, 0, Mi, D0, D0, grads + L.conv_w, 9 * D0, 9, 4, grads + L.conv_b, w.P, st);
+    if (dfeat && lightattn) {   // dfeat = dY Wc[:, :, 4]: the centre tap read transposed (element (n, k) at n 9 D0 + 9 k + 4)
+        TrDense d{dY, nullptr, Mi, params + L.conv_w, nullptr, dfeat, nullptr, nullptr, nullptr, 0, 0, 0, 1.f, 0, Mi, D0, D0, 9, 9 * D0, 4, 0};
+        tr_launch_dense(d, st);
+    } else if (dfeat) {         // dfeat = (dY W_0) * [feat > 0]: both_out's first ReLU reads the feature row itself
+        TrDense d{dY, nullptr, Mi, params + L.W[0], nullptr, dfeat, feat, nullptr, nullptr, 0, 0, 0, 1.f, 0, Mi, dims[1], D0, 1, D0, 0, 0};
+        tr_launch_dense(d, st);
+    }
     return tm_check_launch("head_train_step");
 }
 
