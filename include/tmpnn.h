@@ -255,6 +255,33 @@ int tmpnn_finetune_eval(const float *X, const int32_t *S, const float *mask, con
                         int n_layers, const int32_t *dims, int subtract_mut, const float *params, int64_t slab_numel, float *pred,
                         int32_t *E_idx_opt, float *rows_opt, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream);
 
+/* tmpnn_finetune_step split in two calls, for a host autograd (thermompnn_amd/autograd.py): the forward fills a SAVED buffer that the
+ * backward only reads, so the saved state stays alive between them (and a second backward over it gives the same bits), while the
+ * backward's SCRATCH buffer may be shared by every backward. Sizes as tmpnn_finetune_workspace_bytes (0 = bad arguments); the saved
+ * part holds the graph, the features, every activation the backward reads and the head rows. */
+size_t tmpnn_finetune_saved_bytes(int64_t L, int64_t M, int n_final, int lightattn, int n_layers, const int32_t *dims);
+size_t tmpnn_finetune_scratch_bytes(int64_t L, int64_t M, int n_final, int lightattn, int n_layers, const int32_t *dims);
+/* The training forward of tmpnn_finetune_step (same description, same dropout: keep_in / the generator keyed on (seed, step) at p_mpnn,
+ * head_keep_in / the head's generator at p_head): pred [M] equals tmpnn_finetune_step's pred_opt bit for bit. keep_out, E_idx_opt and
+ * rows_opt as there. */
+int tmpnn_finetune_forward(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
+                           int64_t L, const int32_t *pos, const int32_t *mut, const int32_t *wt, int64_t M, int n_final, int lightattn,
+                           int n_layers, const int32_t *dims, int subtract_mut, const float *params, int64_t slab_numel, float p_mpnn,
+                           float p_head, const float *keep_in, float *keep_out, const float *head_keep_in, uint64_t seed, uint64_t step,
+                           float *pred, int32_t *E_idx_opt, float *rows_opt, void *saved, size_t saved_bytes, tmpnn_stream_t stream);
+/* The backward of the forward that filled `saved` (same arguments, same params, saved untouched since), seeded from any upstream
+ * gradient dpred [M] = dL / dpred (device). The dropout masks are recomputed (or keep_in / head_keep_in read again). Writes the
+ * gradient entries of the slab that can be non-zero into grads, as tmpnn_finetune_step does (the caller zeroes the slab); with
+ * mpnn_grads = 0 only the head's part of the slab is written and the ProteinMPNN backward does not run (frozen encoder).
+ * Contract: with dpred[i] = 2 * (pred[i] - t[i]) * (1.0f / M) formed in fp32, forward then backward give the same pred and grads as
+ * tmpnn_finetune_step, bit for bit. Deterministic; `saved` is never written. */
+int tmpnn_finetune_backward(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
+                            int64_t L, const int32_t *pos, const int32_t *mut, const int32_t *wt, int64_t M, int n_final, int lightattn,
+                            int n_layers, const int32_t *dims, int subtract_mut, const float *params, int64_t slab_numel, float p_mpnn,
+                            float p_head, const float *keep_in, const float *head_keep_in, uint64_t seed, uint64_t step,
+                            const float *dpred, float *grads, int mpnn_grads, const void *saved, size_t saved_bytes, void *scratch,
+                            size_t scratch_bytes, tmpnn_stream_t stream);
+
 /* ---- the fused path ------------------------------------------------------------------------------
  * Everything TransferModel.forward does on the device for a ragged batch of N proteins
  * (transfer_model.py:75-121 + protein_mpnn_utils.py:1222-1277), one call, 18 launches on `stream` (14 when every workgroup has at most one residue tile).

@@ -535,7 +535,12 @@ static int ft_cparts(int64_t R) {
     return (int)(p < 1 ? 1 : p > FT_CLS_PARTS ? FT_CLS_PARTS : p);
 }
 
-// Workspace: every saved activation and scratch buffer of one call, carved in a fixed order.
+// Workspace, in two parts carved in a fixed order. SAVED: what the backward reads from the forward (the graph, the features, every
+// saved activation, W_s[S], the head rows) and the head's workspace of the forward. SCRATCH: what only the backward writes (the CSR
+// lists, the gradients of activations, the weight-gradient partials) and the head's workspace of the backward. The fused entries take
+// one workspace, saved part first; there the forward's temporaries (ftm, fdh, fdF) are the backward's tm, dh1, dF, and both head
+// passes share one head workspace. The split entries (tmpnn_finetune_forward / _backward) give the forward its own temporaries in the
+// saved part and the backward its own head workspace in the scratch part, so that the backward never writes the saved part.
 struct FtEncS { float *a1, *a2, *b1, *b2, *x3, *mu3, *rs3, *x1, *mu1, *rs1, *hV1, *fa, *x2, *mu2, *rs2, *out; };
 struct FtDecS { float *a1, *a2, *x1, *mu1, *rs1, *hV1, *fa, *x2, *mu2, *rs2, *out; };
 struct FtWs {
@@ -544,24 +549,26 @@ struct FtWs {
     FtEncS enc[3];
     FtDecS dec[3];
     float *tm, *t1, *t2, *dA, *dE, *dE2, *dEd, *gx, *gb, *dEp, *dV, *dV2, *dh1, *dF, *dhS, *dH[3], *dG, *P, *CP;
-    void *head_ws;
-    size_t head_bytes, bytes;
+    float *ftm, *fdh, *fdF;                       // the forward's temporaries: message / LayerNorm input, message sum, FFN output
+    void *head_ws, *head_ws_b;                    // the head's workspace of the forward / of the backward
+    size_t head_bytes, saved_bytes, scratch_bytes, bytes;
 };
 
-static FtWs ft_carve(void *base, int64_t L, int64_t M, int lightattn, int n_layers, const int32_t *dims) {
+static FtWs ft_carve2(void *saved, void *scratch, bool split, int64_t L, int64_t M, int lightattn, int n_layers, const int32_t *dims) {
     FtWs w{};
-    char *p = (char *)base;
-    size_t off = 0;
-    auto take = [&](size_t nbytes) { void *r = base ? (void *)(p + off) : nullptr; off += ft_align(nbytes); return r; };
-    auto f = [&](int64_t n) { return (float *)take((size_t)n * 4); };
-    auto i32 = [&](int64_t n) { return (int32_t *)take((size_t)n * 4); };
+    size_t so = 0, co = 0;
+    auto take_s = [&](size_t nbytes) { void *r = saved ? (void *)((char *)saved + so) : nullptr; so += ft_align(nbytes); return r; };
+    auto take_c = [&](size_t nbytes) { void *r = scratch ? (void *)((char *)scratch + co) : nullptr; co += ft_align(nbytes); return r; };
+    auto f = [&](int64_t n) { return (float *)take_s((size_t)n * 4); };
+    auto i32 = [&](int64_t n) { return (int32_t *)take_s((size_t)n * 4); };
+    auto fc = [&](int64_t n) { return (float *)take_c((size_t)n * 4); };
+    auto ic = [&](int64_t n) { return (int32_t *)take_c((size_t)n * 4); };
     const int64_t K = L < TM_KS ? L : TM_KS, E = L * K, H = FT_H, D0 = dims[0];
-    w.offs = i32(2); w.E48 = i32(L * TM_KS); w.eidx = i32(E); w.cls = i32(E);
-    w.cnt = i32(L + 1); w.cur = i32(L + 1); w.coff = i32(L + 1); w.clist = i32(E);
-    w.mcnt = i32(L + 1); w.mcur = i32(L + 1); w.moff = i32(L + 1); w.mlist = i32(M); w.rows_id = i32(M); w.status = i32(1);
+    // saved
+    w.offs = i32(2); w.E48 = i32(L * TM_KS); w.eidx = i32(E); w.cls = i32(E); w.rows_id = i32(M); w.status = i32(1);
     w.D48 = f(L * TM_KS); w.Ein = f(E * 416); w.E0 = f(E * H); w.nemu = f(E); w.ners = f(E); w.En = f(E * H);
     for (int l = 0; l < 4; ++l) w.hE[l] = f(E * H);
-    w.hV0 = f(L * H); w.hS = f(L * H); w.headX = f(M * D0); w.dheadX = f(M * D0);
+    w.hV0 = f(L * H); w.hS = f(L * H); w.headX = f(M * D0);
     for (int l = 0; l < 3; ++l) {
         FtEncS &s = w.enc[l];
         s.a1 = f(E * H); s.a2 = f(E * H); s.b1 = f(E * H); s.b2 = f(E * H); s.x3 = f(E * H); s.mu3 = f(E); s.rs3 = f(E);
@@ -574,18 +581,36 @@ static FtWs ft_carve(void *base, int64_t L, int64_t M, int lightattn, int n_laye
         s.x1 = f(L * H); s.mu1 = f(L); s.rs1 = f(L); s.hV1 = f(L * H); s.fa = f(L * 4 * H); s.x2 = f(L * H); s.mu2 = f(L); s.rs2 = f(L);
         s.out = f(L * H);
     }
-    w.tm = f(E * H); w.t1 = f(E * H); w.t2 = f(E * H); w.dA = f(E * 4 * H); w.dE = f(E * H); w.dE2 = f(E * H); w.dEd = f(E * H);
-    w.gx = f(E * H); w.gb = f(E * H); w.dEp = f(E * 16);
-    w.dV = f(L * H); w.dV2 = f(L * H); w.dh1 = f(L * H); w.dF = f(L * H); w.dhS = f(L * H);
-    for (int l = 0; l < 3; ++l) w.dH[l] = f(L * H);
-    w.dG = f(L * 4 * H);
-    const int64_t pe = std::max(ft_parts(E), ft_parts(L));
-    w.P = f(pe * std::max<int64_t>(H * (4 * H + 1), 4 * H * (H + 1)));
-    w.CP = f((int64_t)FT_CLS_PARTS * std::max<int64_t>(66 * 16, TMPNN_VOCAB * H));
     w.head_bytes = tmpnn_head_train_workspace_bytes(M, n_layers >= 1 ? (int)(D0 / H - 1) : 0, lightattn, n_layers, dims);
-    w.head_ws = take(w.head_bytes);
-    w.bytes = off + 256;
+    w.head_ws = take_s(w.head_bytes);
+    if (split) { w.ftm = f(E * H); w.fdh = f(L * H); w.fdF = f(L * H); }
+    // scratch
+    w.cnt = ic(L + 1); w.cur = ic(L + 1); w.coff = ic(L + 1); w.clist = ic(E);
+    w.mcnt = ic(L + 1); w.mcur = ic(L + 1); w.moff = ic(L + 1); w.mlist = ic(M); w.dheadX = fc(M * D0);
+    w.tm = fc(E * H); w.t1 = fc(E * H); w.t2 = fc(E * H); w.dA = fc(E * 4 * H); w.dE = fc(E * H); w.dE2 = fc(E * H); w.dEd = fc(E * H);
+    w.gx = fc(E * H); w.gb = fc(E * H); w.dEp = fc(E * 16);
+    w.dV = fc(L * H); w.dV2 = fc(L * H); w.dh1 = fc(L * H); w.dF = fc(L * H); w.dhS = fc(L * H);
+    for (int l = 0; l < 3; ++l) w.dH[l] = fc(L * H);
+    w.dG = fc(L * 4 * H);
+    const int64_t pe = std::max(ft_parts(E), ft_parts(L));
+    w.P = fc(pe * std::max<int64_t>(H * (4 * H + 1), 4 * H * (H + 1)));
+    w.CP = fc((int64_t)FT_CLS_PARTS * std::max<int64_t>(66 * 16, TMPNN_VOCAB * H));
+    if (split) {
+        w.head_ws_b = take_c(w.head_bytes);
+    } else {
+        w.ftm = w.tm; w.fdh = w.dh1; w.fdF = w.dF;
+        w.head_ws_b = w.head_ws;
+    }
+    w.saved_bytes = so + (split ? 256 : 0);
+    w.scratch_bytes = co + 256;
+    w.bytes = so + co + 256;
     return w;
+}
+
+// the fused entries' one workspace: the saved part, then the scratch part
+static FtWs ft_carve(void *base, int64_t L, int64_t M, int lightattn, int n_layers, const int32_t *dims) {
+    const FtWs sz = ft_carve2(nullptr, nullptr, false, L, M, lightattn, n_layers, dims);
+    return ft_carve2(base, base ? (void *)((char *)base + sz.saved_bytes) : nullptr, false, L, M, lightattn, n_layers, dims);
 }
 
 static int ft_grid_items(int64_t wave_items) {
@@ -726,8 +751,8 @@ static void ft_node_fwd(const FtCtx &c, const float *hV, const float *dh, int si
     const int L = c.L;
     ft_ln_fwd(c, hV, dh, site1, n1w, n1b, nullptr, x1, hV1, mu1, rs1, L);
     ft_linear(c, ft_plain(hV1, FT_H, FT_H, L), Win, bin, fa, 4 * FT_H, L, 4 * FT_H);
-    ft_linear(c, ft_plain(fa, 4 * FT_H, 4 * FT_H, L, 2), Wout, bout, c.w.dF, FT_H, L, FT_H);
-    ft_ln_fwd(c, hV1, c.w.dF, site2, n2w, n2b, c.mask, x2, out, mu2, rs2, L);
+    ft_linear(c, ft_plain(fa, 4 * FT_H, 4 * FT_H, L, 2), Wout, bout, c.w.fdF, FT_H, L, FT_H);
+    ft_ln_fwd(c, hV1, c.w.fdF, site2, n2w, n2b, c.mask, x2, out, mu2, rs2, L);
 }
 // its backward: dout (grad of out) -> c.w.dV2 = grad of hV (residual path only) and c.w.dh1 = grad of dh (after dropout1's backward)
 static void ft_node_bwd(const FtCtx &c, const float *dout, int site1, int site2, int64_t on1w, int64_t on1b, int64_t oWin, int64_t obin,
@@ -755,7 +780,7 @@ static int ft_forward(const FtCtx &c) {
         FtGraph g{c.X, c.ridx, c.cenc, w.E48, w.D48, P + S.posw, P + S.posb, w.eidx, w.cls, w.Ein, L, c.K};
         ft_graph_kernel<<<ft_grid_threads(E), TM_THREADS, 0, c.st>>>(g);
         ft_linear(c, ft_plain(w.Ein, 416, 416, E), P + S.edgew, nullptr, w.E0, FT_H, E, FT_H);
-        FtLnF ln{w.E0, nullptr, 0, P + S.new_, P + S.neb, nullptr, w.t1, w.En, w.nemu, w.ners, E, c.drop};   // xs = E0 again (scratch)
+        FtLnF ln{w.E0, nullptr, 0, P + S.new_, P + S.neb, nullptr, w.ftm, w.En, w.nemu, w.ners, E, c.drop};   // xs = E0 again (temporary)
         ln.d.mode = 0;
         ft_ln_fwd_kernel<<<ft_grid_items(E), TM_THREADS, 0, c.st>>>(ln);
         ft_linear(c, ft_plain(w.En, FT_H, FT_H, E), P + S.Wew, P + S.Web, w.hE[0], FT_H, E, FT_H);
@@ -764,21 +789,21 @@ static int ft_forward(const FtCtx &c) {
         for (int l = 0; l < 3; ++l) {
             const FtEncP &p = S.enc[l];
             const FtEncS &s = w.enc[l];
-            ft_mlp3_fwd(c, ft_msg_in(c, hV, w.hE[l], nullptr), P + p.W1, P + p.b1, P + p.W2, P + p.b2, P + p.W3, P + p.b3, s.a1, s.a2, w.tm);
-            ft_msg_sum_kernel<<<ft_grid_threads((int64_t)L * FT_H), TM_THREADS, 0, c.st>>>(w.tm, c.mask, w.eidx, 1, L, c.K, w.dh1);
-            ft_node_fwd(c, hV, w.dh1, 3 * l, 3 * l + 1, P + p.n1w, P + p.n1b, P + p.Win, P + p.bin, P + p.Wout, P + p.bout, P + p.n2w, P + p.n2b,
+            ft_mlp3_fwd(c, ft_msg_in(c, hV, w.hE[l], nullptr), P + p.W1, P + p.b1, P + p.W2, P + p.b2, P + p.W3, P + p.b3, s.a1, s.a2, w.ftm);
+            ft_msg_sum_kernel<<<ft_grid_threads((int64_t)L * FT_H), TM_THREADS, 0, c.st>>>(w.ftm, c.mask, w.eidx, 1, L, c.K, w.fdh);
+            ft_node_fwd(c, hV, w.fdh, 3 * l, 3 * l + 1, P + p.n1w, P + p.n1b, P + p.Win, P + p.bin, P + p.Wout, P + p.bout, P + p.n2w, P + p.n2b,
                         s.x1, s.mu1, s.rs1, s.hV1, s.fa, s.x2, s.mu2, s.rs2, s.out);
             ft_mlp3_fwd(c, ft_msg_in(c, s.out, w.hE[l], nullptr), P + p.W11, P + p.b11, P + p.W12, P + p.b12, P + p.W13, P + p.b13, s.b1, s.b2,
-                        w.tm);
-            ft_ln_fwd(c, w.hE[l], w.tm, 3 * l + 2, P + p.n3w, P + p.n3b, nullptr, s.x3, w.hE[l + 1], s.mu3, s.rs3, E);
+                        w.ftm);
+            ft_ln_fwd(c, w.hE[l], w.ftm, 3 * l + 2, P + p.n3w, P + p.n3b, nullptr, s.x3, w.hE[l + 1], s.mu3, s.rs3, E);
             hV = s.out;
         }
         for (int l = 0; l < 3; ++l) {
             const FtDecP &p = S.dec[l];
             const FtDecS &s = w.dec[l];
-            ft_mlp3_fwd(c, ft_msg_in(c, hV, w.hE[3], w.hS), P + p.W1, P + p.b1, P + p.W2, P + p.b2, P + p.W3, P + p.b3, s.a1, s.a2, w.tm);
-            ft_msg_sum_kernel<<<ft_grid_threads((int64_t)L * FT_H), TM_THREADS, 0, c.st>>>(w.tm, c.mask, w.eidx, 0, L, c.K, w.dh1);
-            ft_node_fwd(c, hV, w.dh1, 9 + 2 * l, 10 + 2 * l, P + p.n1w, P + p.n1b, P + p.Win, P + p.bin, P + p.Wout, P + p.bout, P + p.n2w,
+            ft_mlp3_fwd(c, ft_msg_in(c, hV, w.hE[3], w.hS), P + p.W1, P + p.b1, P + p.W2, P + p.b2, P + p.W3, P + p.b3, s.a1, s.a2, w.ftm);
+            ft_msg_sum_kernel<<<ft_grid_threads((int64_t)L * FT_H), TM_THREADS, 0, c.st>>>(w.ftm, c.mask, w.eidx, 0, L, c.K, w.fdh);
+            ft_node_fwd(c, hV, w.fdh, 9 + 2 * l, 10 + 2 * l, P + p.n1w, P + p.n1b, P + p.Win, P + p.bin, P + p.Wout, P + p.bout, P + p.n2w,
                         P + p.n2b, s.x1, s.mu1, s.rs1, s.hV1, s.fa, s.x2, s.mu2, s.rs2, s.out);
             hV = s.out;
         }
@@ -923,6 +948,21 @@ static FtCtx ft_ctx(const float *X, const int32_t *S, const float *mask, const i
     return c;
 }
 
+// ProteinMPNN's dropout of one call: the injected masks (keep_in), the stated generator keyed on (seed, step) when p > 0, else none
+static void ft_set_drop(FtCtx &c, int64_t L, float p_mpnn, const float *keep_in, float *keep_out, uint64_t seed, uint64_t step) {
+    const uint32_t thr = (uint32_t)llround((double)p_mpnn * 16777216.0);
+    c.drop.mode = keep_in ? 1 : thr > 0 ? 2 : 0;
+    c.drop.keep_in = keep_in;
+    c.drop.keep_out = c.drop.mode == 2 ? keep_out : nullptr;
+    c.drop.thr = thr;
+    c.drop.scale = (float)(1.0 / (1.0 - (double)thr / 16777216.0));
+    ft_mask_offsets(L, c.drop.off);
+    {   // k2 of the stated generator, formed on the host in the same 64-bit arithmetic
+        auto mix = [](uint64_t x) { x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31; return x; };
+        c.drop.k2 = mix(mix(seed ^ 0x9E3779B97F4A7C15ull) + step);
+    }
+}
+
 extern "C" int tmpnn_finetune_step(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
                                    int64_t L, const int32_t *pos, const int32_t *mut, const int32_t *wt, const float *target, int64_t M,
                                    int n_final, int lightattn, int n_layers, const int32_t *dims, int subtract_mut, const float *params,
@@ -939,23 +979,13 @@ extern "C" int tmpnn_finetune_step(const float *X, const int32_t *S, const float
     FT_TRY(ft_check_ws("finetune_step", L, M, n_final, lightattn, n_layers, dims, workspace, workspace_bytes));
     FtCtx c = ft_ctx(X, S, mask, residue_idx, chain_enc, L, pos, mut, wt, M, n_final, lightattn, n_layers, dims, subtract_mut, params, grads,
                      workspace, (hipStream_t)stream);
-    const uint32_t thr = (uint32_t)llround((double)p_mpnn * 16777216.0);
-    c.drop.mode = keep_in ? 1 : thr > 0 ? 2 : 0;
-    c.drop.keep_in = keep_in;
-    c.drop.keep_out = c.drop.mode == 2 ? keep_out : nullptr;
-    c.drop.thr = thr;
-    c.drop.scale = (float)(1.0 / (1.0 - (double)thr / 16777216.0));
-    ft_mask_offsets(L, c.drop.off);
-    {   // k2 of the stated generator, formed on the host in the same 64-bit arithmetic
-        auto mix = [](uint64_t x) { x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31; return x; };
-        c.drop.k2 = mix(mix(seed ^ 0x9E3779B97F4A7C15ull) + step);
-    }
+    ft_set_drop(c, L, p_mpnn, keep_in, keep_out, seed, step);
     if (keep_out && c.drop.mode != 2) (void)hipMemsetAsync(keep_out, 0, (size_t)ft_mask_numel(L) * 4, c.st);
     FT_TRY(ft_forward(c));
     const int64_t D0 = dims[0];
     const int rc = tm_head_train_core(c.w.headX, M, c.w.rows_id, mut, wt, target, M, lightattn, n_layers, dims, subtract_mut,
                                       params + c.lay.head, grads + c.lay.head, p_head, head_keep_in, nullptr, seed, step, loss, pred_opt,
-                                      c.w.head_ws, c.st, c.w.dheadX);
+                                      c.w.head_ws, c.st, c.w.dheadX, nullptr);
     if (rc != TMPNN_OK) return rc;
     ft_backward(c);
     if (E_idx_opt) (void)hipMemcpyAsync(E_idx_opt, c.w.eidx, (size_t)c.E * 4, hipMemcpyDeviceToDevice, c.st);
@@ -981,4 +1011,80 @@ extern "C" int tmpnn_finetune_eval(const float *X, const int32_t *S, const float
     if (E_idx_opt) (void)hipMemcpyAsync(E_idx_opt, c.w.eidx, (size_t)c.E * 4, hipMemcpyDeviceToDevice, c.st);
     if (rows_opt) (void)hipMemcpyAsync(rows_opt, c.w.headX, (size_t)M * dims[0] * 4, hipMemcpyDeviceToDevice, c.st);
     return tm_check_launch("finetune_eval");
+}
+
+// ---- the step split in two: forward into a saved buffer, backward from any dL / dpred ---------------------------------------------
+extern "C" size_t tmpnn_finetune_saved_bytes(int64_t L, int64_t M, int n_final, int lightattn, int n_layers, const int32_t *dims) {
+    if (L < 2 || L > FT_L_MAX || M < 1 || M > FT_M_MAX || !ft_dims_ok(n_final, n_layers, dims)) return 0;
+    return ft_carve2(nullptr, nullptr, true, L, M, lightattn, n_layers, dims).saved_bytes;
+}
+
+extern "C" size_t tmpnn_finetune_scratch_bytes(int64_t L, int64_t M, int n_final, int lightattn, int n_layers, const int32_t *dims) {
+    if (L < 2 || L > FT_L_MAX || M < 1 || M > FT_M_MAX || !ft_dims_ok(n_final, n_layers, dims)) return 0;
+    return ft_carve2(nullptr, nullptr, true, L, M, lightattn, n_layers, dims).scratch_bytes;
+}
+
+static int ft_check_split(const char *what, int n_final, int lightattn, float p_mpnn, float p_head, const float *keep_in,
+                          const float *head_keep_in) {
+    FT_REQUIRE(p_mpnn >= 0.f && p_mpnn < 1.f && p_head >= 0.f && p_head < 1.f, "%s: dropout probability outside [0, 1)", what);
+    FT_REQUIRE(lightattn || (p_head == 0.f && !head_keep_in), "%s: head dropout needs LightAttention (lightattn)", what);
+    FT_REQUIRE(!keep_in || n_final > 0, "%s: num_final_layers 0 runs no ProteinMPNN layer", what);
+    return TMPNN_OK;
+}
+
+static int ft_check_buf(const char *what, const char *which, void *buf, size_t bytes, size_t need) {
+    if (!buf || bytes < need) return tm_set_error(TMPNN_E_WORKSPACE, "%s: %s buffer %zu < %zu bytes", what, which, bytes, need);
+    return TMPNN_OK;
+}
+
+extern "C" int tmpnn_finetune_forward(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
+                                      int64_t L, const int32_t *pos, const int32_t *mut, const int32_t *wt, int64_t M, int n_final, int lightattn,
+                                      int n_layers, const int32_t *dims, int subtract_mut, const float *params, int64_t slab_numel, float p_mpnn,
+                                      float p_head, const float *keep_in, float *keep_out, const float *head_keep_in, uint64_t seed, uint64_t step,
+                                      float *pred, int32_t *E_idx_opt, float *rows_opt, void *saved, size_t saved_bytes, tmpnn_stream_t stream) {
+    FT_TRY(ft_check("finetune_forward", X, S, mask, residue_idx, chain_enc, L, pos, mut, wt, M, n_final, lightattn, n_layers, dims, params,
+                    slab_numel));
+    FT_REQUIRE(pred, "finetune_forward: null pointer");
+    FT_TRY(ft_check_split("finetune_forward", n_final, lightattn, p_mpnn, p_head, keep_in, head_keep_in));
+    FT_REQUIRE(!(keep_in && keep_out), "finetune_forward: keep_in (injected masks) and keep_out (drawn masks) exclude each other");
+    FT_REQUIRE(!(E_idx_opt || keep_out) || n_final > 0, "finetune_forward: num_final_layers 0 runs no ProteinMPNN layer");
+    FT_TRY(ft_check_buf("finetune_forward", "saved", saved, saved_bytes,
+                        tmpnn_finetune_saved_bytes(L, M, n_final, lightattn, n_layers, dims)));
+    FtCtx c = ft_ctx(X, S, mask, residue_idx, chain_enc, L, pos, mut, wt, M, n_final, lightattn, n_layers, dims, subtract_mut, params, nullptr,
+                     nullptr, (hipStream_t)stream);
+    c.w = ft_carve2(saved, nullptr, true, L, M, lightattn, n_layers, dims);
+    ft_set_drop(c, L, p_mpnn, keep_in, keep_out, seed, step);
+    if (keep_out && c.drop.mode != 2) (void)hipMemsetAsync(keep_out, 0, (size_t)ft_mask_numel(L) * 4, c.st);
+    FT_TRY(ft_forward(c));
+    FT_TRY(tm_head_forward(c.w.headX, M, c.w.rows_id, mut, wt, M, lightattn, n_layers, dims, subtract_mut, params + c.lay.head, p_head,
+                           head_keep_in, nullptr, seed, step, pred, c.w.head_ws, c.st));
+    if (E_idx_opt) (void)hipMemcpyAsync(E_idx_opt, c.w.eidx, (size_t)c.E * 4, hipMemcpyDeviceToDevice, c.st);
+    if (rows_opt) (void)hipMemcpyAsync(rows_opt, c.w.headX, (size_t)M * dims[0] * 4, hipMemcpyDeviceToDevice, c.st);
+    return tm_check_launch("finetune_forward");
+}
+
+extern "C" int tmpnn_finetune_backward(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
+                                       int64_t L, const int32_t *pos, const int32_t *mut, const int32_t *wt, int64_t M, int n_final, int lightattn,
+                                       int n_layers, const int32_t *dims, int subtract_mut, const float *params, int64_t slab_numel, float p_mpnn,
+                                       float p_head, const float *keep_in, const float *head_keep_in, uint64_t seed, uint64_t step,
+                                       const float *dpred, float *grads, int mpnn_grads, const void *saved, size_t saved_bytes, void *scratch,
+                                       size_t scratch_bytes, tmpnn_stream_t stream) {
+    FT_TRY(ft_check("finetune_backward", X, S, mask, residue_idx, chain_enc, L, pos, mut, wt, M, n_final, lightattn, n_layers, dims, params,
+                    slab_numel));
+    FT_REQUIRE(dpred && grads, "finetune_backward: null pointer");
+    FT_TRY(ft_check_split("finetune_backward", n_final, lightattn, p_mpnn, p_head, keep_in, head_keep_in));
+    FT_TRY(ft_check_buf("finetune_backward", "saved", (void *)saved, saved_bytes,
+                        tmpnn_finetune_saved_bytes(L, M, n_final, lightattn, n_layers, dims)));
+    FT_TRY(ft_check_buf("finetune_backward", "scratch", scratch, scratch_bytes,
+                        tmpnn_finetune_scratch_bytes(L, M, n_final, lightattn, n_layers, dims)));
+    FtCtx c = ft_ctx(X, S, mask, residue_idx, chain_enc, L, pos, mut, wt, M, n_final, lightattn, n_layers, dims, subtract_mut, params, grads,
+                     nullptr, (hipStream_t)stream);
+    // the saved part is only read: its one writer is the forward
+    c.w = ft_carve2(const_cast<void *>(saved), scratch, true, L, M, lightattn, n_layers, dims);
+    ft_set_drop(c, L, p_mpnn, keep_in, nullptr, seed, step);
+    FT_TRY(tm_head_train_core(c.w.headX, M, c.w.rows_id, mut, wt, nullptr, M, lightattn, n_layers, dims, subtract_mut, params + c.lay.head,
+                              grads + c.lay.head, p_head, head_keep_in, nullptr, seed, step, nullptr, nullptr, c.w.head_ws_b, c.st,
+                              mpnn_grads ? c.w.dheadX : nullptr, dpred));
+    if (mpnn_grads) ft_backward(c);
+    return tm_check_launch("finetune_backward");
 }

@@ -128,7 +128,11 @@ int launch_head_generic(const float *const *hidden, int n_final, const float *Ws
 int tm_head_train_core(const float *feat, int64_t n_feat, const int32_t *rows, const int32_t *mut, const int32_t *wt,
                        const float *target, int64_t M, int lightattn, int n_layers, const int32_t *dims, int subtract_mut,
                        const float *params, float *grads, float p_drop, const float *keep_in, float *keep_out, uint64_t seed,
-                       uint64_t step, float *loss, float *pred_opt, void *workspace, hipStream_t st, float *dfeat);
+                       uint64_t step, float *loss, float *pred_opt, void *workspace, hipStream_t st, float *dfeat,
+                       const float *dpred);
+int tm_head_forward(const float *feat, int64_t n_feat, const int32_t *rows, const int32_t *mut, const int32_t *wt, int64_t M,
+                    int lightattn, int n_layers, const int32_t *dims, int subtract_mut, const float *params, float p_drop,
+                    const float *keep_in, float *keep_out, uint64_t seed, uint64_t step, float *pred, void *workspace, hipStream_t st);
 int launch_range_check(const float *x, int64_t n, int32_t *status, hipStream_t st, const int32_t *maxlen_probe = nullptr,
                        int64_t T = 0);   // ORs TMPNN_STATUS_RANGE if any x is inf / NaN (+ the MAXLEN probe of the fused forward)
 int launch_prep_tables(tmpnn_weights *w, hipStream_t st);

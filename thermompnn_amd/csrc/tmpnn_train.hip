@@ -210,6 +210,41 @@ __global__ __launch_bounds__(TM_THREADS) void tr_pred_kernel(TrResid a) {
     }
 }
 
+// The residual's backward half seeded from a caller's d_i = dpred[i] (= dL / dpred_i) instead of the MSE form: the same dZ, the same
+// per-thread sums and the same tree as tr_resid_kernel, so dpred[i] = 2 (pred_i - t_i) (1 / n) formed in fp32 gives its bits.
+__global__ __launch_bounds__(TM_THREADS) void tr_seed_kernel(TrResid a, const float *__restrict__ dpred) {
+    __shared__ float red[2][TM_THREADS];
+    const int tid = tm_tid();
+    const float dw = a.ddg_w[0], db = a.ddg_b[0];
+    float sw = 0.f, sb = 0.f;
+    for (int i = tid; i < a.M; i += TM_THREADS) {
+        float zm, zw;
+        (void)tr_pred(a.Z, i, a.mut[i], a.wt[i], dw, db, a.subtract, &zm, &zw);
+        const float d = dpred[i];
+        const int mut = min(max(a.mut[i], 0), TMPNN_VOCAB - 1), wt = min(max(a.wt[i], 0), TMPNN_VOCAB - 1);
+        for (int c = 0; c < TMPNN_VOCAB; ++c) {
+            float g = 0.f;
+            if (c == mut) g += dw * d;
+            if (a.subtract && c == wt) g -= dw * d;
+            a.dZ[(size_t)i * TMPNN_VOCAB + c] = g;
+        }
+        sw += a.subtract ? d * (zm - zw) : d * zm;
+        sb += d;
+    }
+    red[0][tid] = sw;
+    red[1][tid] = sb;
+    __syncthreads();
+    for (int s = TM_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s)
+            for (int j = 0; j < 2; ++j) red[j][tid] += red[j][tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        a.g_ddg_w[0] = red[0][0];
+        a.g_ddg_b[0] = a.subtract ? 0.f : red[1][0];
+    }
+}
+
 // ---- fused AdamW over one flat slab -----------------------------------------------------------------------------------------
 // torch/optim/adam.py with decoupled decay (AdamW), per element in torch's order: p *= 1 - lr wd; m = lerp(m, g, 1 - beta1);
 // v = v beta2 + (1 - beta2) g g; p += -lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps). The scalars are formed on the
@@ -383,15 +418,17 @@ extern "C" int tmpnn_head_train_step(const float *feat, int64_t n_feat, const in
     if (!workspace || workspace_bytes < need)
         return tm_set_error(TMPNN_E_WORKSPACE, "head_train_step: workspace %zu < %zu bytes", workspace_bytes, need);
     return tm_head_train_core(feat, n_feat, rows, mut, wt, target, M, lightattn, n_layers, dims, subtract_mut, params, grads, p_drop,
-                              keep_in, keep_out, seed, step, loss, pred_opt, workspace, (hipStream_t)stream, nullptr);
+                              keep_in, keep_out, seed, step, loss, pred_opt, workspace, (hipStream_t)stream, nullptr, nullptr);
 }
 
 // The launches of one head training step (arguments already validated). dfeat [M, D0] (may be null): d loss / d feature row of
 // every mutant, for a caller that back-propagates further (tmpnn_finetune.hip); it needs rows[i] == i (feat holds the mutants' rows).
+// dpred [M] (may be null): the backward starts from d_i = dpred[i] instead of the MSE residual; target, loss and pred_opt are then
+// not used.
 int tm_head_train_core(const float *feat, int64_t n_feat, const int32_t *rows, const int32_t *mut, const int32_t *wt,
                        const float *target, int64_t M, int lightattn, int n_layers, const int32_t *dims, int subtract_mut,
                        const float *params, float *grads, float p_drop, const float *keep_in, float *keep_out, uint64_t seed,
-                       uint64_t step, float *loss, float *pred_opt, void *workspace, hipStream_t st, float *dfeat) {
+                       uint64_t step, float *loss, float *pred_opt, void *workspace, hipStream_t st, float *dfeat, const float *dpred) {
     const TrLayout L = tr_layout(lightattn, n_layers, dims);
     const TrWs w = tr_carve(workspace, M, lightattn, n_layers, dims);
     const int D0 = dims[0], Mi = (int)M, nf = (int)n_feat;
@@ -404,7 +441,8 @@ int tm_head_train_core(const float *feat, int64_t n_feat, const int32_t *rows, c
     float *dY = w.dA, *dX = w.dB;
     TrResid r{w.H[n_layers], mut, wt, target, params + L.ddg_w, params + L.ddg_b, Mi, subtract_mut, dY, grads + L.ddg_w,
               grads + L.ddg_b, loss, pred_opt};
-    tr_resid_kernel<<<1, TM_THREADS, 0, st>>>(r);
+    if (dpred) tr_seed_kernel<<<1, TM_THREADS, 0, st>>>(r, dpred);
+    else tr_resid_kernel<<<1, TM_THREADS, 0, st>>>(r);
     for (int l = n_layers - 1; l >= 0; --l) {
         const bool raw_in = l == 0 && !lightattn;      // layer 0 reads the feature rows themselves
         const float *A = raw_in ? feat : w.H[l];
@@ -428,6 +466,25 @@ int tm_head_train_core(const float *feat, int64_t n_feat, const int32_t *rows, c
         tr_launch_dense(d, st);
     }
     return tm_check_launch("head_train_step");
+}
+
+// The training forward alone (arguments already validated): pred [M] with the head's dropout drawn or read as tm_head_train_core
+// does (same kernels, same order: the bits of its pred_opt). keep_out may be null.
+int tm_head_forward(const float *feat, int64_t n_feat, const int32_t *rows, const int32_t *mut, const int32_t *wt, int64_t M,
+                    int lightattn, int n_layers, const int32_t *dims, int subtract_mut, const float *params, float p_drop,
+                    const float *keep_in, float *keep_out, uint64_t seed, uint64_t step, float *pred, void *workspace, hipStream_t st) {
+    const TrLayout L = tr_layout(lightattn, n_layers, dims);
+    const TrWs w = tr_carve(workspace, M, lightattn, n_layers, dims);
+    const int drop = keep_in ? 1 : p_drop > 0.f ? 2 : 0;
+    const uint32_t thr = (uint32_t)llround((double)p_drop * 16777216.0);
+    const float scale = (float)(1.0 / (1.0 - (double)p_drop));
+    float *mask = drop == 2 ? (keep_out ? keep_out : w.mask) : nullptr;
+    tr_forward(feat, rows, (int)n_feat, (int)M, lightattn, n_layers, dims, params, L, w, drop, keep_in, mask, seed, step, thr, scale, st);
+    TrResid r{w.H[n_layers], mut, wt, nullptr, params + L.ddg_w, params + L.ddg_b, (int)M, subtract_mut, nullptr, nullptr, nullptr,
+              nullptr, pred};
+    const int64_t blocks = (M + TM_THREADS - 1) / TM_THREADS, cap = (int64_t)tm_num_cus() * 4;
+    tr_pred_kernel<<<(int)(blocks < cap ? blocks : cap), TM_THREADS, 0, st>>>(r);
+    return tm_check_launch("head_forward");
 }
 
 extern "C" int tmpnn_head_eval(const float *feat, int64_t n_feat, const int32_t *rows, const int32_t *mut, const int32_t *wt, int64_t M,

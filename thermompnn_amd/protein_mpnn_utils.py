@@ -39,7 +39,8 @@ class _EngineOwner(nn.Module):
     _engine = None
     _engine_key = None
     k_neighbors = 48
-    precision = None          # matrix-core path of the engine ("f16x2" | "bf16x3" | "fp32"; None = library default)
+    precision = None          # matrix-core path of the engine ("f16x2" | "bf16x3" | "fp32"; None = library default). The gradient
+                              # path of TransferModel (differentiable = True) always runs the exact fp32 training kernels instead
     retry_precision = "bf16x3"   # Engine reruns an f16x2 forward that left the fp16 range at this precision (None: raise)
     _engine_kwargs: dict = {}    # extra Engine(...) arguments of a subclass (TransferModel with a generic head: with_head=False)
 

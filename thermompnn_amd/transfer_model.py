@@ -46,6 +46,11 @@ def get_protein_mpnn(cfg, version="v_48_020.pt"):
 
 
 class TransferModel(_EngineOwner):
+    # Opt-in gradient path (thermompnn_amd/autograd.py): with differentiable = True, grad mode on and some parameter requiring grad,
+    # forward returns ddG values that carry a graph to the parameters, computed on the exact fp32 training kernels whatever
+    # `precision` says, with dropout where prot_mpnn / light_attention are in training mode. Otherwise forward is the inference path.
+    differentiable = False
+
     def __init__(self, cfg):
         super().__init__()
         self.cfg = cfg
@@ -103,6 +108,10 @@ class TransferModel(_EngineOwner):
             return ddg if self.subtract_mut else z * self.ddg_out.weight.view(()) + self.ddg_out.bias.view(())
 
     def forward(self, pdb, mutations, tied_feat=True):
+        if self.differentiable:
+            from . import autograd as _autograd
+            if _autograd.wants_grad(self):
+                return _autograd.transfer_forward(self, pdb, mutations)
         device = next(self.parameters()).device
         feats = tied_featurize([pdb[0]], device, None, None, None, None, None, None, ca_only=False)
         X, S, mask, chain_enc, residue_idx = feats[0], feats[1], feats[2], feats[5], feats[12]
