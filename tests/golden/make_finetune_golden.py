@@ -1,6 +1,6 @@
 """Golden gradients of one fine-tuning step (ProteinMPNN unfrozen), by IMPORTING THE REFERENCE (runs only in the build container).
 
-    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_finetune_golden.py
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_finetune_golden.py [2OCJ_A | 2OCJ_A_gap]
 
 The reference TransferModel (make_golden.build_reference_model: synthetic weights, seed 0, released head) runs in float64 and in
 train mode with every parameter trainable, over ~96 mutants of 2OCJ chain A (several sharing a position, a few with ddG None). Each
@@ -12,6 +12,11 @@ Stored: the E_idx the reference used, the loss per case, and per trainable tenso
 fixed sample of 2048 entries (seeded by the tensor's name and size, sample_index) with the float64 sum of squares, the dot with a
 seeded +-1 vector and max|g|. Full gradients up to 16 k entries and 4096-entry samples would make the file about 2.5 MB; these
 limits keep it under 1 MB. W_out has no gradient and is not stored. Only tensors are stored, nothing of the reference's source.
+
+2OCJ_A_gap runs the same recipe on tests/golden/2OCJ_gap_chainA.pdb (residue 120 without its N line: position 24 has mask 0 and keeps
+its letter; residues 150-152 removed: positions 54-56 are '-', token 20, mask 0). Its mutant positions are drawn from the residues
+that have a letter, position 24 always among them. The E_idx of a masked row is arbitrary (every candidate sits at the same adjusted
+distance) and does not reach the loss.
 """
 import os
 import sys
@@ -67,15 +72,24 @@ def sample_index(name, n):
     return np.sort(rng.choice(n, SAMPLE, replace=False)), rng.choice([-1.0, 1.0], n)
 
 
-def main():
+CASES = {"2OCJ_A": os.path.join(mg.REF, "examples", "2OCJ.pdb"), "2OCJ_A_gap": os.path.join(HERE, "2OCJ_gap_chainA.pdb")}
+GAP_MASKED = 24                                   # residue 120 without its N line
+
+
+def main(case="2OCJ_A"):
     rng = np.random.default_rng(7)
     with tempfile.TemporaryDirectory() as tmp:
         model = mg.build_reference_model(tmp)
-    pdb = mg.ref_utils.alt_parse_PDB(os.path.join(mg.REF, "examples", "2OCJ.pdb"), "A")
+    pdb = mg.ref_utils.alt_parse_PDB(CASES[case], "A")
     seq = pdb[0]["seq"]
     L = len(seq)
     K = min(48, L)
-    positions = np.sort(rng.choice([i for i in range(L) if seq[i] in AA20], 32, replace=False))
+    if case == "2OCJ_A":
+        positions = np.sort(rng.choice([i for i in range(L) if seq[i] in AA20], 32, replace=False))
+    else:
+        assert seq[GAP_MASKED] in AA20 and seq[54:57] == "---"
+        positions = np.sort(np.append(rng.choice([i for i in range(L) if seq[i] in AA20 and i != GAP_MASKED], 31, replace=False),
+                                      GAP_MASKED))
     muts = []
     for p in positions:
         for a in rng.choice([c for c in AA20 if c != seq[p]], 3, replace=False):
@@ -138,10 +152,10 @@ def main():
                 out[f"{tag}|{name}|dot"] = np.float64((g * sign).sum())
                 out[f"{tag}|{name}|absmax"] = np.float64(np.abs(g).max())
         print(f"{tag}: loss {loss.item():.8f}")
-    path = os.path.join(HERE, "finetune_2OCJ_A.npz")
+    path = os.path.join(HERE, f"finetune_{case}.npz")
     np.savez_compressed(path, **out)
-    print(f"finetune_2OCJ_A: {len(muts)} mutants -> {os.path.getsize(path) / 1024:.0f} KiB")
+    print(f"finetune_{case}: {len(muts)} mutants -> {os.path.getsize(path) / 1024:.0f} KiB")
 
 
 if __name__ == "__main__":
-    main()
+    main(*sys.argv[1:2])

@@ -139,3 +139,24 @@ def test_documented_learning_rate_override_is_read_as_a_number(tmp_path):
     for bad in ("fast", "nan", "-1e-4", "true"):
         with pytest.raises(ValueError, match="mpnn_learn_rate"):
             check_finetune_config(load_config([str(base)], ["model.freeze_weights=false", f"training.mpnn_learn_rate={bad}"]))
+
+
+@pytest.mark.parametrize("name", ["msk_L40", "msk_L56"])
+def test_masked_backbones_parse_to_the_intended_mask_and_gaps(tmp_path, name):
+    """tests/masked_backbones.py: a missing N line keeps the letter with mask 0, a removed residue becomes '-' (token 20)."""
+    from masked_backbones import LAYOUTS, expected, write_layout
+    from thermompnn_amd.pdb_io import alt_parse_PDB, tied_featurize
+    from thermompnn_amd.synthetic import synthetic_backbone
+    L, seed, missing_n, gaps = LAYOUTS[name]
+    pdb = alt_parse_PDB(write_layout(name, tmp_path), ["A"])
+    want_mask, want_gaps = expected(name)
+    seq = pdb[0]["seq"]
+    _, full = synthetic_backbone(L, seed)
+    assert len(seq) == L and [i for i, c in enumerate(seq) if c == "-"] == want_gaps
+    assert all(seq[i] == full[i] for i in range(L) if i not in gaps)
+    f = tied_featurize(pdb, "cpu", None, None, None, None, None, None, ca_only=False)
+    X, S, mask = f[0][0], f[1][0], f[2][0]
+    assert mask.tolist() == want_mask
+    assert [i for i in range(L) if int(S[i]) == 20] == want_gaps
+    assert {0, L - 1} <= set(missing_n) | set(gaps) and sum(want_mask) < L
+    assert bool(np.isfinite(X.numpy()).all())                      # NaN coordinates are zeroed once the mask holds them

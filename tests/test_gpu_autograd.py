@@ -11,7 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import GOLDEN, REPO, load_golden
-from test_gpu_finetune import AA20, CASES, RELEASED, _golden_sample_index, _mutants, _pdb
+from test_gpu_finetune import AA20, CASES, RELEASED, _case_mutants, _golden_sample_index, _mutants, _pdb, restate
 
 pytestmark = pytest.mark.gpu
 
@@ -160,14 +160,17 @@ def test_loss_backward_matches_the_reference_golden(tmp_path):
         assert model.prot_mpnn.W_out.weight.grad is None and model.prot_mpnn.W_out.bias.grad is None
 
 
-@pytest.mark.parametrize("case,head,subtract,dropout", CASES, ids=[f"{c[0]}-nf{c[1]['num_final_layers']}-la{int(c[1]['lightattn'])}"
-                                                                  for c in CASES])
+SPLIT_CASES = CASES + [("2OCJ_A_gap", RELEASED, True, True), ("msk_L40", RELEASED, True, True), ("syn_L17", RELEASED, True, True)]
+
+
+@pytest.mark.parametrize("case,head,subtract,dropout", SPLIT_CASES,
+                         ids=[f"{c[0]}-nf{c[1]['num_final_layers']}-la{int(c[1]['lightattn'])}" for c in SPLIT_CASES])
 def test_split_forward_backward_equals_the_fused_step_bit_for_bit(tmp_path, case, head, subtract, dropout):
     from thermompnn_amd.finetune import MPNNTrainer
     model = _model(tmp_path, head, subtract)
     tr = MPNNTrainer(model, seed=7)
     pdb = _pdb(case, tmp_path)
-    prot = tr.prepare([(pdb, _mutants(pdb, 40))])[0]
+    prot = tr.prepare([(pdb, _case_mutants(case, pdb))])[0]
     ph = 0.25 if head["lightattn"] else 0.0
     seed, step = 7, 3
     pred_f = torch.empty(prot.M, dtype=torch.float32, device="cuda")
@@ -187,6 +190,37 @@ def test_split_forward_backward_equals_the_fused_step_bit_for_bit(tmp_path, case
     diff = (g1 != tr.grad).nonzero()
     assert diff.numel() == 0, (diff[:5].tolist(), [k for k, o in tr.offsets.items() if o <= int(diff[0])][-1])
     assert torch.equal(g1, g2)
+
+
+def test_loss_backward_on_a_gapped_chain_matches_the_float64_restatement(tmp_path):
+    """TransferModel.differentiable on 2OCJ chain A with residue 120 missing its N (position 24, mask 0, mutants on it) and residues
+    150-152 missing ('-' at 54-56): every .grad against restate() on the device's own k-NN graph."""
+    from thermompnn_amd.finetune import MPNNTrainer
+    model = _model(tmp_path)
+    model.differentiable = True
+    model.eval()
+    pdb = _pdb("2OCJ_A_gap", tmp_path)
+    muts = _mutants(pdb, 40, seed=3, with_none=False, at=(24, 24, 53, 57))
+    pred, _ = model(pdb, muts)
+    loss = _loss(pred, muts)
+    loss.backward()
+    tr = MPNNTrainer(model)
+    prot = tr.prepare([(pdb, muts)])[0]
+    assert float(prot.mask[24]) == 0.0 and int((prot.pos == 24).sum()) >= 2 and int((prot.S == 20).sum()) == 3
+    E_idx = torch.empty((prot.L, 48), dtype=torch.int32, device="cuda")
+    tr.forward_backward(prot, p_mpnn=0.0, p_head=0.0, E_idx_out=E_idx)
+    torch.cuda.synchronize()
+    ones = [np.ones((prot.L * (48 if s < 9 and s % 3 == 2 else 1), 128), np.float32) for s in range(15)]
+    ref_loss, ref, _ = restate(model.state_dict(), list(tr.shapes), prot, E_idx.cpu().numpy(), ones, None, 2, True, True)
+    assert abs(float(loss.detach()) - ref_loss) <= 1e-5 * max(abs(ref_loss), 1e-3), (float(loss.detach()), ref_loss)
+    params = dict(model.named_parameters())
+    # the '-' positions (token 20) are masked and no unmasked row of this chain has them among its 48 nearest: W_s[20] gets nothing
+    assert float(ref["prot_mpnn.W_s.weight"][20].abs().max()) == 0.0 == float(params["prot_mpnn.W_s.weight"].grad[20].abs().max())
+    for k in tr.shapes:
+        g, r = params[k].grad.cpu().double(), ref[k]
+        gmax, err = float(r.abs().max()), float((g - r).abs().max())
+        assert err <= 1e-4 * gmax or err <= 1e-12, (k, err, gmax)
+    assert model.prot_mpnn.W_out.weight.grad is None
 
 
 def test_arbitrary_upstream_gradient_and_finite_differences(tmp_path):

@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import GOLDEN
+from masked_backbones import LAYOUTS, write_layout
 
 pytestmark = pytest.mark.gpu
 AA20 = "ACDEFGHIKLMNPQRSTVWY"
@@ -40,6 +41,10 @@ def _pdb(case, tmp_path):
         return alt_parse_PDB(os.path.join(GOLDEN, "2OCJ.pdb"), ["A"])
     if case == "2OCJ_AB":
         return alt_parse_PDB(os.path.join(GOLDEN, "2OCJ.pdb"), ["A", "B"])
+    if case == "2OCJ_A_gap":                       # residue 120 without N (position 24), 150-152 removed (positions 54-56 are '-')
+        return alt_parse_PDB(os.path.join(GOLDEN, "2OCJ_gap_chainA.pdb"), ["A"])
+    if case in LAYOUTS:
+        return alt_parse_PDB(write_layout(case, tmp_path), ["A"])
     L = int(case.split("_L")[1])
     X, seq = synthetic_backbone(L, 5)
     path = os.path.join(str(tmp_path), f"{case}.pdb")
@@ -48,12 +53,15 @@ def _pdb(case, tmp_path):
     return alt_parse_PDB(path, ["A"])
 
 
-def _mutants(pdb, n, seed=0, with_none=True):
+def _mutants(pdb, n, seed=0, with_none=True, at=()):
+    """n mutants on residues that have a letter ('-' has no wild type), the first quarter on one residue, then one on each of ``at``."""
     from thermompnn_amd.datasets import Mutation
     seq = pdb[0]["seq"]
     rng = np.random.default_rng(seed)
-    pos = rng.integers(0, len(seq), n)
+    letters = np.array([i for i, c in enumerate(seq) if c != "-"])
+    pos = letters[rng.integers(0, len(letters), n)]
     pos[: n // 4] = pos[0]                          # several mutants share a residue
+    pos[n // 4: n // 4 + len(at)] = at
     out = []
     for i, p in enumerate(pos):
         t = None if with_none and i % 17 == 5 else torch.tensor([float(rng.normal())])
@@ -165,16 +173,44 @@ CASES = [("2OCJ_A", RELEASED, True, True), ("2OCJ_AB", RELEASED, True, False), (
          ("syn_L32", dict(hidden_dims=[64, 32], num_final_layers=0, lightattn=True), True, True),
          ("syn_L40", dict(hidden_dims=[48], num_final_layers=1, lightattn=False), True, True),
          ("syn_L32", dict(hidden_dims=[32], num_final_layers=3, lightattn=True), False, True)]
+NF0 = dict(hidden_dims=[64, 32], num_final_layers=0, lightattn=True)
+# masked residues (mask 0 with a letter, and '-' gaps), chains shorter than a 16-row tile or off the multiples of 4 / 16, K = 48 < L from
+# L = 49 on, and ~1900 labelled mutants crowded onto two residues (long mutant-CSR bins, the head core's 16 parts of > 64 rows)
+EDGE_CASES = [("2OCJ_A_gap", RELEASED, True, True), ("msk_L40", RELEASED, False, True), ("msk_L40", NF0, True, True),
+              ("msk_L56", RELEASED, True, True), ("syn_L2", RELEASED, True, True), ("syn_L3", RELEASED, False, True),
+              ("syn_L5", dict(hidden_dims=[48], num_final_layers=1, lightattn=False), True, True), ("syn_L17", NF0, True, True),
+              ("syn_L17", RELEASED, True, True), ("syn_L47", dict(hidden_dims=[32], num_final_layers=3, lightattn=True), True, True),
+              ("syn_L49", RELEASED, True, True), ("many_L24", RELEASED, True, True)]
+# mutants placed on masked residues (a missing N line: mask 0, the letter kept) and next to the gaps
+AT = {"2OCJ_A_gap": (24, 24, 53, 57), "msk_L40": (0, 12, 30, 39, 23), "msk_L56": (0, 9, 41, 55, 33)}
+GAPPED = ("2OCJ_A_gap", "msk_L40", "msk_L56")
 
 
-@pytest.mark.parametrize("case,head,subtract,dropout", CASES, ids=[f"{c[0]}-nf{c[1]['num_final_layers']}-la{int(c[1]['lightattn'])}-d{int(c[3])}"
-                                                                  for c in CASES])
+def _case_mutants(case, pdb, n=40, seed=0):
+    from thermompnn_amd.datasets import Mutation
+    if not case.startswith("many_"):
+        return _mutants(pdb, n, seed, at=AT.get(case, ()))
+    seq = pdb[0]["seq"]
+    rng = np.random.default_rng(seed)
+    n = 2000
+    pos = np.where(rng.random(n) < 0.9, np.where(rng.random(n) < 0.5, 3, 17), rng.integers(0, len(seq), n))
+    return [Mutation(int(p), seq[p], AA20[int(rng.integers(0, 20))], None if i % 17 == 5 else torch.tensor([float(rng.normal())]), "x")
+            for i, p in enumerate(pos)]
+
+
+def _case_id(c):
+    return f"{c[0]}-nf{c[1]['num_final_layers']}-la{int(c[1]['lightattn'])}-s{int(c[2])}-d{int(c[3])}"
+
+
+@pytest.mark.parametrize("case,head,subtract,dropout", CASES + EDGE_CASES,
+                         ids=[f"{c[0]}-nf{c[1]['num_final_layers']}-la{int(c[1]['lightattn'])}-d{int(c[3])}" for c in CASES]
+                         + [_case_id(c) for c in EDGE_CASES])
 def test_every_gradient_matches_a_float64_restatement(tmp_path, case, head, subtract, dropout):
     from thermompnn_amd.finetune import MPNNTrainer
     model = _model(tmp_path, head, subtract)
     tr = MPNNTrainer(model, seed=7)
     pdb = _pdb(case, tmp_path)
-    prot = tr.prepare([(pdb, _mutants(pdb, 40))])[0]
+    prot = tr.prepare([(pdb, _case_mutants(case, pdb))])[0]
     L, K = prot.L, min(48, prot.L)
     nf, la = head["num_final_layers"], head["lightattn"]
     E_idx = torch.empty((L, K), dtype=torch.int32, device="cuda")
@@ -189,6 +225,7 @@ def test_every_gradient_matches_a_float64_restatement(tmp_path, case, head, subt
     if nf:
         Ei = E_idx.cpu().numpy()
         assert ((Ei >= 0) & (Ei < L)).all()
+        _check_neighbour_sets(prot, Ei)
     else:
         from oracle import thermompnn_oracle as O
         X = prot.X.cpu().double()[None]
@@ -209,7 +246,38 @@ def test_every_gradient_matches_a_float64_restatement(tmp_path, case, head, subt
         err = float((g - r).abs().max())
         worst[k] = err / gmax if gmax > 1e-12 else err
         assert err <= 1e-4 * gmax or err <= 1e-12, (k, err, gmax)      # 1e-12: a structural zero the float64 side rounds to ~1e-17
+    if case in GAPPED and nf:
+        assert int((prot.S == 20).sum()) > 0 and float(prot.mask.min()) == 0.0
+        mask = prot.mask.cpu().numpy()
+        reached = bool((mask[Ei[mask > 0]] == 0).any())
+        g20 = float(ref["prot_mpnn.W_s.weight"][20].abs().max())
+        if case == "2OCJ_A_gap":            # 194 residues, 4 masked: no masked residue is among an unmasked row's 48 nearest
+            assert not reached and g20 == 0.0
+            assert float(tr.tensor("prot_mpnn.W_s.weight", "grad")[20].abs().max()) == 0.0
+        else:                               # masked j feed unmasked rows through h_E_ij and h_S_j (W_s[20] at a '-' position)
+            assert reached and g20 > 0.0
+    if case.startswith("many_"):
+        assert prot.M > 1024 and int((prot.pos == 3).sum()) > 400 and int((prot.pos == 17).sum()) > 400
     print(case, "worst gradient error / max|g|:", max(worst.values()), max(worst, key=worst.get))
+
+
+def _check_neighbour_sets(prot, Ei):
+    """The device's k-NN on the unmasked rows equals the oracle's, up to exact ties at the K-th adjusted distance (the device takes
+    the lower index; torch.topk leaves tie order unspecified). A masked row's candidates all sit at its D_max: its
+    neighbour order is arbitrary and reaches nothing."""
+    from oracle import thermompnn_oracle as O
+    from test_gpu_parity import topk_rows_differing
+    X, mask = prot.X.cpu()[None], prot.mask.cpu()[None]
+    D_adj = O.adjusted_distances(X[:, :, 1], mask)[0].numpy()
+    ref = O.knn(X[:, :, 1], mask, Ei.shape[1])[1][0].numpy()
+    live = np.flatnonzero(prot.mask.cpu().numpy() > 0)
+    topk_rows_differing(Ei, ref, D_adj, live)
+    masked = set(np.flatnonzero(prot.mask.cpu().numpy() == 0).tolist())
+    if prot.L > Ei.shape[1] and masked and len(live) < Ei.shape[1]:
+        # fewer unmasked residues than K: every unmasked row's top K holds masked neighbours, at its D_max
+        for i in live:
+            nb = [j for j in Ei[i] if j in masked]
+            assert nb and all(D_adj[i, j] == D_adj[i].max() for j in nb), i
 
 
 def test_eval_rows_match_the_engine_and_predictions_match_transfer_model(tmp_path):
@@ -404,20 +472,25 @@ def _golden_sample_index(name, n, k=2048):
     return np.sort(rng.choice(n, k, replace=False)), rng.choice([-1.0, 1.0], n)
 
 
-def test_loss_and_gradients_match_the_reference_golden(tmp_path):
-    """The imported reference in float64 (tests/golden/make_finetune_golden.py), all-ones and generator-drawn dropout masks."""
+@pytest.mark.parametrize("golden,src", [("finetune_2OCJ_A", "2OCJ.pdb"), ("finetune_2OCJ_A_gap", "2OCJ_gap_chainA.pdb")],
+                         ids=["2OCJ_A", "2OCJ_A_gap"])
+def test_loss_and_gradients_match_the_reference_golden(tmp_path, golden, src):
+    """The imported reference in float64 (tests/golden/make_finetune_golden.py), all-ones and generator-drawn dropout masks. On the
+    gapped chain the reference also settles how mask_attend / mask_bw enter the gradients (the kernel and restate() share one reading)."""
     from conftest import load_golden
     from thermompnn_amd.datasets import Mutation
     from thermompnn_amd.finetune import MPNNTrainer
     from thermompnn_amd.pdb_io import alt_parse_PDB
-    g = load_golden("finetune_2OCJ_A")
-    pdb = alt_parse_PDB(os.path.join(GOLDEN, "2OCJ.pdb"), ["A"])
+    g = load_golden(golden)
+    pdb = alt_parse_PDB(os.path.join(GOLDEN, src), ["A"])
     muts = [Mutation(int(p), AA20[w], AA20[m], None if np.isnan(t) else torch.tensor([float(t)]), "2OCJ")
             for p, w, m, t in zip(g["positions"], g["wildtype"], g["mutation"], g["targets"])]
     tr = MPNNTrainer(_model(tmp_path), seed=int(g["seed"]))
     prot = tr.prepare([(pdb, muts)])[0]
     L, K = prot.L, min(48, prot.L)
     assert prot.M == int(np.isfinite(g["targets"]).sum())
+    if golden.endswith("_gap"):
+        assert 24 in g["positions"] and float(prot.mask[24]) == 0.0 and pdb[0]["seq"][54:57] == "---"
     drawn = np.concatenate([numpy_site_mask(int(g["seed"]), int(g["step"]), s, L * K if s < 9 and s % 3 == 2 else L).reshape(-1)
                             for s in range(15)])
     for tag in ("ones", "drawn"):
@@ -425,7 +498,8 @@ def test_loss_and_gradients_match_the_reference_golden(tmp_path):
         E_idx = torch.empty((L, K), dtype=torch.int32, device="cuda")
         kw = dict(keep_in=torch.from_numpy(drawn).cuda(), p_mpnn=0.1) if tag == "drawn" else dict(p_mpnn=0.0)
         loss = tr.forward_backward(prot, p_head=0.0, step=int(g["step"]), E_idx_out=E_idx, **kw)
-        assert np.array_equal(E_idx.cpu().numpy(), g["E_idx"]), "the device's k-NN graph differs from the reference's"
+        live = prot.mask.cpu().numpy() > 0           # a masked row's neighbour order is arbitrary and does not reach the loss
+        assert np.array_equal(E_idx.cpu().numpy()[live], g["E_idx"][live]), "the device's k-NN graph differs from the reference's"
         ref_loss = float(g[f"{tag}_loss"])
         assert abs(float(loss) - ref_loss) <= 1e-6 * abs(ref_loss), (tag, float(loss), ref_loss)
         for name in tr.shapes:

@@ -144,6 +144,52 @@ def test_gradients_match_a_float64_restatement(tmp_path, head, subtract):
     print(f"head {head} subtract {subtract}: loss {float(loss):.6g}, worst gradient error / max|g| = {worst:.2e}")
 
 
+def _many_mutants(seq, M, seed, site=None):
+    """M labelled mutants of ``seq``: random positions (all on ``site`` when given), the first five repeated verbatim further on, one
+    whose wild type equals its mutation."""
+    from thermompnn_amd.datasets import Mutation
+    rng = np.random.default_rng(seed)
+    pos = np.full(M, site) if site is not None else rng.integers(0, len(seq), M)
+    aa = rng.integers(0, 20, M)
+    out = [Mutation(int(p), seq[p], AA20[int(a)], torch.tensor([float(rng.normal())]), "x") for p, a in zip(pos, aa)]
+    for i in range(min(5, M // 2)):
+        out[M - 1 - i] = out[i]                                    # duplicated mutants (same position, letter and target)
+    if M > 1:
+        out[M // 3] = Mutation(int(pos[M // 3]), seq[pos[M // 3]], seq[pos[M // 3]], torch.tensor([0.3]), "x")   # wild type = mutation
+    return out
+
+
+NO_HIDDEN = dict(hidden_dims=[], num_final_layers=2, lightattn=False)
+M_CASES = [(M, RELEASED, None) for M in (1, 17, 1024, 1025, 1100, 5000)] + [(M, NO_HIDDEN, None) for M in (1, 17, 1025, 5000)] \
+    + [(1100, RELEASED, 7), (2000, NO_HIDDEN, 90)]
+
+
+@pytest.mark.parametrize("M,head,site", M_CASES, ids=[f"M{c[0]}-{'released' if c[1] is RELEASED else 'nohidden'}"
+                                                      + ("" if c[2] is None else f"-site{c[2]}") for c in M_CASES])
+def test_gradients_match_a_float64_restatement_at_mutant_count_edges(tmp_path, M, head, site):
+    """M = 1, 17 (one short 16-row tile), 1024 (16 parts of 64 rows), 1025 .. 5000 (16 parts of more than 64 rows, TR_MAX_PARTS), all
+    mutants on one residue: every weight gradient within 1e-5 of the float64 restatement."""
+    from thermompnn_amd.train import HeadTrainer
+    _, pdb, _ = _golden_item()
+    tr = HeadTrainer(_model(tmp_path, head, subtract=True), seed=3)
+    split = tr.build_cache([(pdb, _many_mutants(pdb[0]["seq"], M, M, site))])
+    assert split.counts == [M]
+    keep = torch.empty((M, tr.dims[0]), device="cuda") if tr.lightattn else None
+    loss = tr.forward_backward(split, 0, keep_out=keep, step=5)
+    ref_loss, ref = _float64_grads(tr, split, keep)
+    assert float(ref["ddg_out.bias"].abs().max()) <= 1e-12
+    ref["ddg_out.bias"] = torch.zeros_like(ref["ddg_out.bias"])
+    assert abs(float(loss) - ref_loss) <= 1e-5 * ref_loss
+    for name, r in ref.items():
+        got = tr.tensor(name, "grad").double()
+        scale = float(r.abs().max())
+        if scale == 0.0:
+            assert float(got.abs().max()) == 0.0, name
+            continue
+        rel = float((got - r).abs().max()) / scale
+        assert rel <= 1e-5, (name, rel)
+
+
 def test_fused_adamw_matches_torch():
     from thermompnn_amd import _lib
     lib = _lib.load()
