@@ -294,6 +294,34 @@ int tmpnn_ssm_forward(const tmpnn_weights_t *w, const float *X, const int32_t *S
                       float *log_probs_opt, int32_t *E_idx_opt, int32_t *status_opt, void *workspace,
                       size_t workspace_bytes, tmpnn_stream_t stream);
 
+/* ---- many sequence variants over one backbone --------------------------------------------------------
+ * The k-NN graph, the edge features and the three encoder layers never read the sequence (it enters at decoder layer 0,
+ * protein_mpnn_utils.py:1268). tmpnn_encode runs that part of tmpnn_ssm_forward once for a ragged batch — the same launches,
+ * small-launch forms included, so the encoder state has the fused forward's bits — and leaves in the caller's ctx buffer
+ * (tmpnn_encode_bytes(T) bytes, 256-byte aligned, opaque) what the decoder reads: E_idx [T,48], the final h_E [T,48,128], the
+ * encoder's h_V [T,128] and decoder layer 0's node projection without its sequence term [T,256]. status_opt is zeroed on the
+ * stream and receives TMPNN_STATUS_MAXLEN / TMPNN_STATUS_RANGE (a non-finite encoder state). The ctx belongs to the handle's
+ * precision: decode it with a handle of the same precision. */
+size_t tmpnn_encode_bytes(int64_t T);
+size_t tmpnn_encode_workspace_bytes(int64_t T);
+int tmpnn_encode(const tmpnn_weights_t *w, const float *X, const float *mask, const int32_t *residue_idx,
+                 const int32_t *chain_enc, const int32_t *offsets, int n_proteins, int64_t T, int max_len, int K,
+                 void *ctx, size_t ctx_bytes, int32_t *status_opt, void *workspace, size_t workspace_bytes,
+                 tmpnn_stream_t stream);
+/* The three decoder layers, the ddG head and the log-probabilities for V full sequences over the encoded batch: S_var [V,T]
+ * (variant v = one sequence over the packed residue axis), mask [T] as given to tmpnn_encode. Outputs (each may be NULL, not all):
+ * ddg [V,T,21] with ddg[v,t,a] relative to the variant's OWN residue S_var[v,t], as tmpnn_ssm_forward defines it for S;
+ * hidden_opt [V,3,T,128]; log_probs_opt [V,T,21]. The decoder message pass fetches a residue's h_E tile and multiplies it by
+ * W1's edge block once per chunk of variants, not once per variant. A variant's result has the same bits whatever V is and
+ * whichever slot it takes (callers may chunk V freely); with an fp32 handle it is tmpnn_ssm_forward's result for that sequence bit
+ * for bit, with the split precisions it is held to the same tolerances but sums in another order. V * T is bounded by the
+ * kernels' 32-bit row arithmetic: TMPNN_E_UNSUPPORTED beyond it (decode in chunks), and tmpnn_decode_variants_workspace_bytes
+ * returns 0. status_opt is zeroed on the stream and receives TMPNN_STATUS_RANGE. */
+size_t tmpnn_decode_variants_workspace_bytes(int64_t T, int64_t V);
+int tmpnn_decode_variants(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const int32_t *S_var, int64_t V,
+                          const float *mask, int64_t T, float *ddg, float *hidden_opt, float *log_probs_opt,
+                          int32_t *status_opt, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream);
+
 /* ---- host side: native PDB reader + packer ------------------------------------------
  * Replaces alt_parse_PDB (protein_mpnn_utils.py:183-350) + the packing of tied_featurize (:353-605) for one
  * structure: one pass over the file, all requested chains. `chains` = string of one-letter chain ids in the

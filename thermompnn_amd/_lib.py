@@ -90,6 +90,11 @@ SIGNATURES = {
     "tmpnn_csv_close": (_i, [_p, C.POINTER(_i64), C.POINTER(_i64)]),
     "tmpnn_csv_format_double": (_i, [C.c_double, C.c_char_p]),
     "tmpnn_ssm_forward": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i64, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "tmpnn_encode_bytes": (_sz, [_i64]),
+    "tmpnn_encode_workspace_bytes": (_sz, [_i64]),
+    "tmpnn_encode": (_i, [_p, _p, _p, _p, _p, _p, _i, _i64, _i, _i, _p, _sz, _p, _p, _sz, _p]),
+    "tmpnn_decode_variants_workspace_bytes": (_sz, [_i64, _i64]),
+    "tmpnn_decode_variants": (_i, [_p, _p, _sz, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _sz, _p]),
 }
 # include/tmpnn_debug.h: measurement / experiment hooks (bench.py's per-kernel timing, tools/); not the operator boundary
 DEBUG_SIGNATURES = {

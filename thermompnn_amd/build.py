@@ -15,7 +15,8 @@ LIB = os.path.join(HERE, "libtmpnn.so")
 # and tools/phase_prof.py load it through TMPNN_LIB.
 DEBUG_LIB = os.path.join(HERE, "libtmpnn_debug.so")
 SOURCES = ["tmpnn_api.hip", "tmpnn_graph.hip", "tmpnn_layers.hip", "tmpnn_head.hip", "tmpnn_split.hip", "tmpnn_edge.hip", "tmpnn_msg.hip",
-           "tmpnn_edge_msg.hip", "tmpnn_node.hip", "tmpnn_train.hip", "tmpnn_finetune.hip", "tmpnn_pdb.cpp", "tmpnn_csv.cpp"]
+           "tmpnn_edge_msg.hip", "tmpnn_node.hip", "tmpnn_variants.hip", "tmpnn_train.hip", "tmpnn_finetune.hip", "tmpnn_pdb.cpp",
+           "tmpnn_csv.cpp"]
 HEADERS = ["tmpnn_common.h", "tmpnn_split.h", "tmpnn_internal.h", "tmpnn_head_body.h", os.path.join("..", "..", "include", "tmpnn.h"),
            os.path.join("..", "..", "include", "tmpnn_debug.h"), "tmpnn_host_guard.hpp"]
 # -mcode-object-version=5: tm_nblk() / tm_bdim() (tmpnn_common.h) read gridDim / blockDim at fixed offsets of the v5
@@ -26,10 +27,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # relies on NaNs (range checks test the exponent bits); the host-side PDB reader (.cpp) does and keeps IEEE semantics.
 DEVICE_FLAGS = ["-mno-amdgpu-ieee", "-fno-honor-nans"]
 # ... except the f16x2 per-edge / node kernels (tmpnn_edge / _msg / _edge_msg / _node.hip, and tmpnn_split.hip with the device self-test
-# of exactly this property): their GELU clamps are gfx950's NaN-PROPAGATING v_minimum3_f32 /
+# of exactly this property, and the variant decoder's message kernel, tmpnn_variants.hip): their GELU clamps are gfx950's NaN-PROPAGATING v_minimum3_f32 /
 # v_maximum3_f32 (IEEE-754-2019; no canonicalising op in front of them either), which hipcc emits from __builtin_elementwise_minimum /
 # maximum only in a translation unit that honours NaNs (under -fno-honor-nans they degrade to v_min / v_max). See gelu2, TM_GELU_NAN3.
-NAN3_FILES = ("tmpnn_split.hip", "tmpnn_edge.hip", "tmpnn_msg.hip", "tmpnn_edge_msg.hip", "tmpnn_node.hip")
+NAN3_FILES = ("tmpnn_split.hip", "tmpnn_edge.hip", "tmpnn_msg.hip", "tmpnn_edge_msg.hip", "tmpnn_node.hip", "tmpnn_variants.hip")
 FILE_FLAGS = {f: ["-DTM_GELU_NAN3=1"] for f in NAN3_FILES}
 
 

@@ -460,6 +460,61 @@ static int run_dec_layer(const tmpnn_weights *w, int l, const float *hV_in, floa
     return TMPNN_OK;
 }
 
+// k-NN graph, edge features and the three encoder layers of a ragged batch: the part of a forward that never reads the sequence.
+// The k-NN kernel writes the zero node state (:1228) and its message projection [b1 | 0] as it goes and zeroes the status word (no
+// memset launch: hipMemsetAsync of 4 bytes is a 5.4 us fill kernel in front of a 180 us single-protein forward); node_update of every
+// layer writes the projection the next message pass needs into ws.P — 18 launches per forward (28 when every projection and the zero
+// state are launches of their own). The last node update writes decoder layer 0's projection into P_dec0:
+//   S != nullptr (tmpnn_ssm_forward): with the sequence term, and small launches run the last edge update and decoder message pass 0
+//                as one launch (*dec_msg0_done; P_dec0 must be ws.P);
+//   S == nullptr (tmpnn_encode): without it, and the last edge update runs alone — same kernels, same bits in h_E and h_V.
+static int run_encoder(const tmpnn_weights *w, const float *X, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
+                       const int32_t *offsets, int n_proteins, int64_t T, int max_len, int K, const LayerWs &ws, int32_t *E_idx,
+                       float *D_nb, float *hE, float *hV, const int32_t *S, float *P_dec0, int32_t *status_opt, bool *dec_msg0_done,
+                       hipStream_t st) {
+    static const bool fuse_small = TM_DBG_FLAG("TMPNN_FUSE_SMALL", true);     // (A/B switch in the debug library only)
+    *dec_msg0_done = false;
+    const DecW &d0 = w->dec[0];
+    const NodeProj dec0{d0.W1, 512, d0.b1, d0.W1 + 384, 512, P_dec0, S ? w->seq_table[0] : nullptr, S};
+    const KnnInit kinit{hV, ws.P, w->enc[0].b1, status_opt};
+    if (fuse_small && max_len <= 256 && featurize_fusable(tm_matmul_mode(), T)) {             // one tile per workgroup: k-NN inside the featurizer launch
+        const KnnFuse kf{mask, offsets, n_proteins, max_len, K, E_idx, D_nb, kinit};
+        TRY(launch_featurize(w, X, residue_idx, chain_enc, E_idx, D_nb, T, hE, nullptr, st, &kf));
+    } else {
+        TRY(launch_knn(X, mask, offsets, n_proteins, T, max_len, K, E_idx, D_nb, nullptr, st, kinit));
+        TRY(launch_featurize(w, X, residue_idx, chain_enc, E_idx, D_nb, T, hE, nullptr, st));
+    }
+    if (fuse_small && edge_msg_fusable(tm_matmul_mode(), T)) {
+        // One tile per workgroup (a single protein, a few short ones): the edge update of encoder layer l and the message pass of
+        // the layer after it are ONE launch (edge_msg_fused_kernel: no grid-wide dependency between them; 16 launches instead
+        // of 19, bit-identical results). Launch order: msg0, node0, [edge0 + msg1], node1, [edge1 + msg2], node2,
+        // [edge2 + dec msg0], dnode0, dmsg1, dnode1, dmsg2, dnode2.
+        for (int l = 0; l < 3; ++l) {
+            const EncW &e = w->enc[l];
+            if (l == 0) TRY(launch_msg(false, e.W1 + 128, 384, e.W2, e.b2, ws.P, hE, E_idx, mask, T, ws.Ssum, ws.cnt, st));
+            const NodeProj next = l < 2 ? enc_msg_proj(w, l + 1, ws.P) : dec0;
+            const NodeProj ep{e.W11, 384, e.b11, e.W11 + 256, 384, ws.P2, nullptr, nullptr};
+            TRY(launch_node_update(e.W3, e.b3, e.norm1_w, e.norm1_b, e.Win, e.bin, e.Wout, e.bout, e.norm2_w, e.norm2_b, hV,
+                                   ws.Ssum, ws.cnt, mask, T, hV, &ep, &next, st));
+            if (l < 2) {
+                const EncW &n = w->enc[l + 1];
+                TRY(launch_edge_msg_fused(e, ws.P2, hE, E_idx, false, n.W1 + 128, 384, n.W2, n.b2, ws.P, mask, T, ws.Ssum, ws.cnt, st));
+            } else if (S) {
+                TRY(launch_edge_msg_fused(e, ws.P2, hE, E_idx, true, d0.W1 + 128, 512, d0.W2, d0.b2, ws.P, mask, T, ws.Ssum, ws.cnt, st));
+                *dec_msg0_done = true;
+            } else {
+                TRY(launch_enc_edge(e, ws.P2, hE, E_idx, T, st));
+            }
+        }
+    } else {
+        for (int l = 0; l < 3; ++l) {
+            const NodeProj next = l < 2 ? enc_msg_proj(w, l + 1, ws.P) : dec0;
+            TRY(run_enc_layer(w, l, hV, hE, E_idx, mask, T, ws, true, &next, st));
+        }
+    }
+    return TMPNN_OK;
+}
+
 // ---- entry points ---------------------------------------------------------------------------------
 extern "C" int tmpnn_knn_topk(const float *X, const float *mask, const int32_t *offsets, int n_proteins, int64_t T,
                               int max_len, int K, int32_t *E_idx, float *D_nb, int32_t *status_opt, tmpnn_stream_t stream) {
@@ -651,8 +706,7 @@ extern "C" int tmpnn_ssm_forward(const tmpnn_weights_t *w, const float *X, const
     if (max_len > 8192) return tm_set_error(TMPNN_E_UNSUPPORTED, "ssm_forward: max_len %d > 8192", max_len);
     hipStream_t st = (hipStream_t)stream;
     const TmModeScope scope(w);
-    // (no memset launch for status_opt — hipMemsetAsync of 4 bytes is a 5.4 us fill kernel in front of a 180 us single-protein
-    //  forward: the k-NN kernel zeroes the word, and the LAST kernel flags what the k-NN kernel found, see KnnInit / HeadArgs)
+    // (status_opt: the k-NN kernel zeroes the word, and the LAST kernel flags what the k-NN kernel found, see KnnInit / HeadArgs)
 
     LayerWs ws;
     Carver c{nullptr, 0};
@@ -667,39 +721,11 @@ extern "C" int tmpnn_ssm_forward(const tmpnn_weights_t *w, const float *X, const
     if (E_idx_opt) E_idx = E_idx_opt;
     if (hidden_opt) for (int l = 0; l < 3; ++l) hV[1 + l] = hidden_opt + (size_t)l * T * TMPNN_HID;
 
-    // h_V starts at zero (:1228): the k-NN kernel writes that state and its message projection [b1 | 0] as it goes, and
-    // node_update of every layer writes the projection the next message pass needs into ws.P — 18 launches per forward
-    // (28 when every projection and the zero state are launches of their own)
-    static const bool fuse_small = TM_DBG_FLAG("TMPNN_FUSE_SMALL", true);     // (A/B switch in the debug library only)
-    bool head_done = false;                                                   // the ddG head ran inside the last node update's launch
-    const KnnInit kinit{hV[0], ws.P, w->enc[0].b1, status_opt};
-    if (fuse_small && max_len <= 256 && featurize_fusable(tm_matmul_mode(), T)) {             // one tile per workgroup: k-NN inside the featurizer launch
-        const KnnFuse kf{mask, offsets, n_proteins, max_len, K, E_idx, D_nb, kinit};
-        TRY(launch_featurize(w, X, residue_idx, chain_enc, E_idx, D_nb, T, hE, nullptr, st, &kf));
-    } else {
-        TRY(launch_knn(X, mask, offsets, n_proteins, T, max_len, K, E_idx, D_nb, nullptr, st, kinit));
-        TRY(launch_featurize(w, X, residue_idx, chain_enc, E_idx, D_nb, T, hE, nullptr, st));
-    }
-    if (fuse_small && edge_msg_fusable(tm_matmul_mode(), T)) {
-        // One tile per workgroup (a single protein, a few short ones): the edge update of encoder layer l and the message pass of
-        // the layer after it are ONE launch (edge_msg_fused_kernel: no grid-wide dependency between them; 16 launches instead
-        // of 19, bit-identical results). Launch order: msg0, node0, [edge0 + msg1], node1, [edge1 + msg2], node2,
-        // [edge2 + dec msg0], dnode0, dmsg1, dnode1, dmsg2, dnode2.
-        for (int l = 0; l < 3; ++l) {
-            const EncW &e = w->enc[l];
-            if (l == 0) TRY(launch_msg(false, e.W1 + 128, 384, e.W2, e.b2, ws.P, hE, E_idx, mask, T, ws.Ssum, ws.cnt, st));
-            const NodeProj next = l < 2 ? enc_msg_proj(w, l + 1, ws.P) : dec_msg_proj(w, 0, ws.P, S);
-            const NodeProj ep{e.W11, 384, e.b11, e.W11 + 256, 384, ws.P2, nullptr, nullptr};
-            TRY(launch_node_update(e.W3, e.b3, e.norm1_w, e.norm1_b, e.Win, e.bin, e.Wout, e.bout, e.norm2_w, e.norm2_b, hV[0],
-                                   ws.Ssum, ws.cnt, mask, T, hV[0], &ep, &next, st));
-            if (l < 2) {
-                const EncW &n = w->enc[l + 1];
-                TRY(launch_edge_msg_fused(e, ws.P2, hE, E_idx, false, n.W1 + 128, 384, n.W2, n.b2, ws.P, mask, T, ws.Ssum, ws.cnt, st));
-            } else {
-                const DecW &d = w->dec[0];
-                TRY(launch_edge_msg_fused(e, ws.P2, hE, E_idx, true, d.W1 + 128, 512, d.W2, d.b2, ws.P, mask, T, ws.Ssum, ws.cnt, st));
-            }
-        }
+    bool dec_msg0_done = false;      // small launches: decoder message pass 0 ran inside the last edge update's launch
+    bool head_done = false;          // the ddG head ran inside the last node update's launch
+    TRY(run_encoder(w, X, mask, residue_idx, chain_enc, offsets, n_proteins, T, max_len, K, ws, E_idx, D_nb, hE, hV[0], S, ws.P,
+                    status_opt, &dec_msg0_done, st));
+    if (dec_msg0_done) {
         for (int l = 0; l < 3; ++l) {
             const DecW &d = w->dec[l];
             if (l > 0) TRY(launch_msg(true, d.W1 + 128, 512, d.W2, d.b2, ws.P, hE, E_idx, mask, T, ws.Ssum, ws.cnt, st));
@@ -714,10 +740,6 @@ extern "C" int tmpnn_ssm_forward(const tmpnn_weights_t *w, const float *X, const
         }
     } else {
         for (int l = 0; l < 3; ++l) {
-            const NodeProj next = l < 2 ? enc_msg_proj(w, l + 1, ws.P) : dec_msg_proj(w, 0, ws.P, S);
-            TRY(run_enc_layer(w, l, hV[0], hE, E_idx, mask, T, ws, true, &next, st));
-        }
-        for (int l = 0; l < 3; ++l) {
             const NodeProj next = dec_msg_proj(w, l < 2 ? l + 1 : 2, ws.P, S);
             TRY(run_dec_layer(w, l, hV[l], hV[l + 1], hE, E_idx, S, mask, T, ws, true, l < 2 ? &next : nullptr, st));
         }
@@ -727,5 +749,112 @@ extern "C" int tmpnn_ssm_forward(const tmpnn_weights_t *w, const float *X, const
     // hidden states only: neither of the kernels above has looked at the last decoder state (a poisoned value anywhere upstream
     // has reached it through its neighbours by now)
     if (!ddg && !log_probs_opt && hidden_opt) TRY(launch_range_check(hV[3], T * TMPNN_HID, status_opt, st, E_idx, T));
+    return TMPNN_OK;
+}
+
+// ---- many sequence variants over one encoded backbone ------------------------------------------------
+// The encoded backbone in the caller's ctx buffer: what the decoder reads and no sequence changes.
+struct EncCtx { int32_t *E_idx; float *hE, *hV, *P0; };      // [T,48], [T,48,128], [T,128], [T,256] (decoder layer 0's projection, no sequence term)
+
+extern "C" size_t tmpnn_encode_bytes(int64_t T) {
+    if (T < 0) return 0;
+    return align256((size_t)T * TMPNN_KS * 4) + align256((size_t)T * TMPNN_KS * TMPNN_HID * 4) + align256((size_t)T * TMPNN_HID * 4) +
+           align256((size_t)T * 256 * 4);
+}
+extern "C" size_t tmpnn_encode_workspace_bytes(int64_t T) {
+    if (T < 0) return 0;
+    return tmpnn_layer_workspace_bytes(T) + align256((size_t)T * TMPNN_KS * 4);
+}
+extern "C" size_t tmpnn_decode_variants_workspace_bytes(int64_t T, int64_t V) {
+    if (T < 0 || V < 0 || (V > 0 && T > T_MAX / V)) return 0;
+    const size_t R = (size_t)T * (size_t)V;
+    return align256(R * 256 * 4) + 5 * align256(R * TMPNN_HID * 4) + 2 * align256(R * 4) + 256;
+}
+
+static int carve_ctx(const char *what, void *ctx, size_t ctx_bytes, int64_t T, EncCtx *c) {
+    if (!ctx || ((uintptr_t)ctx & 255) != 0) return tm_set_error(TMPNN_E_INVALID, "%s: ctx is null or not 256-byte aligned", what);
+    if (ctx_bytes < tmpnn_encode_bytes(T))
+        return tm_set_error(TMPNN_E_WORKSPACE, "%s: ctx %zu < %zu bytes", what, ctx_bytes, tmpnn_encode_bytes(T));
+    Carver cv{(char *)ctx, ctx_bytes};
+    c->E_idx = (int32_t *)cv.take((size_t)T * TMPNN_KS * 4);
+    c->hE = (float *)cv.take((size_t)T * TMPNN_KS * TMPNN_HID * 4);
+    c->hV = (float *)cv.take((size_t)T * TMPNN_HID * 4);
+    c->P0 = (float *)cv.take((size_t)T * 256 * 4);
+    return TMPNN_OK;
+}
+
+extern "C" int tmpnn_encode(const tmpnn_weights_t *w, const float *X, const float *mask, const int32_t *residue_idx,
+                            const int32_t *chain_enc, const int32_t *offsets, int n_proteins, int64_t T, int max_len, int K,
+                            void *ctx, size_t ctx_bytes, int32_t *status_opt, void *workspace, size_t workspace_bytes,
+                            tmpnn_stream_t stream) {
+    REQUIRE(w, "encode: null weight handle");
+    REQUIRE(n_proteins >= 0 && T >= 0 && T <= T_MAX, "encode: bad sizes");
+    REQUIRE(K >= 1 && K <= TMPNN_KS, "encode: K=%d outside [1, %d]", K, TMPNN_KS);
+    if (T == 0 || n_proteins == 0) return TMPNN_OK;
+    REQUIRE(X && mask && residue_idx && chain_enc && offsets, "encode: null input pointer");
+    REQUIRE(max_len >= 1, "encode: max_len must be >= 1 (the longest protein of the batch)");
+    if (max_len > 8192) return tm_set_error(TMPNN_E_UNSUPPORTED, "encode: max_len %d > 8192", max_len);
+    EncCtx c;
+    TRY(carve_ctx("encode", ctx, ctx_bytes, T, &c));
+    LayerWs ws;
+    Carver rest{nullptr, 0};
+    TRY(carve_layer_ws(workspace, workspace_bytes, T, &ws, &rest));
+    float *D_nb = (float *)rest.take((size_t)T * TMPNN_KS * 4);
+    if (!D_nb)
+        return tm_set_error(TMPNN_E_WORKSPACE, "encode: workspace %zu < %zu bytes", workspace_bytes, tmpnn_encode_workspace_bytes(T));
+    hipStream_t st = (hipStream_t)stream;
+    const TmModeScope scope(w);
+    bool unused = false;
+    TRY(run_encoder(w, X, mask, residue_idx, chain_enc, offsets, n_proteins, T, max_len, K, ws, c.E_idx, D_nb, c.hE, c.hV, nullptr,
+                    c.P0, status_opt, &unused, st));
+    // the encoder state is this call's output: a value that left the f16x2 range upstream has reached it, and rows of an over-long
+    // protein have an empty neighbour list (the MAXLEN probe of the fused forward's last kernel)
+    return launch_range_check(c.hV, T * TMPNN_HID, status_opt, st, c.E_idx, T);
+}
+
+extern "C" int tmpnn_decode_variants(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const int32_t *S_var, int64_t V,
+                                     const float *mask, int64_t T, float *ddg, float *hidden_opt, float *log_probs_opt,
+                                     int32_t *status_opt, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream) {
+    REQUIRE(w, "decode_variants: null weight handle");
+    REQUIRE(T >= 0 && T <= T_MAX && V >= 0, "decode_variants: bad sizes (T=%lld, V=%lld)", (long long)T, (long long)V);
+    REQUIRE(!ddg || w->n_tensors == TMPNN_N_TENSORS, "decode_variants: ddg requested but the handle has no head tensors");
+    if (T == 0 || V == 0) return TMPNN_OK;            // nothing to decode (pointers may be null)
+    if (T > T_MAX / V)
+        return tm_set_error(TMPNN_E_UNSUPPORTED, "decode_variants: V * T = %lld * %lld rows exceed %lld (decode the variants in chunks)",
+                            (long long)V, (long long)T, (long long)T_MAX);
+    REQUIRE(S_var && mask, "decode_variants: null input pointer");
+    REQUIRE(ddg || hidden_opt || log_probs_opt, "decode_variants: no output requested");
+    EncCtx c;
+    TRY(carve_ctx("decode_variants", const_cast<void *>(ctx), ctx_bytes, T, &c));
+    const int64_t R = V * T;
+    const size_t need = tmpnn_decode_variants_workspace_bytes(T, V);
+    uintptr_t base = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
+    if (!workspace || workspace_bytes < need)
+        return tm_set_error(TMPNN_E_WORKSPACE, "decode_variants: workspace %zu < %zu bytes", workspace_bytes, need);
+    Carver cv{(char *)base, workspace_bytes - (base - (uintptr_t)workspace)};
+    float *P = (float *)cv.take((size_t)R * 256 * 4);
+    float *Ssum = (float *)cv.take((size_t)R * TMPNN_HID * 4);
+    float *cnt = (float *)cv.take((size_t)R * 4);
+    float *mask_rep = (float *)cv.take((size_t)R * 4);
+    float *hV[4];
+    for (int i = 0; i < 4; ++i) hV[i] = (float *)cv.take((size_t)R * TMPNN_HID * 4);
+    if (!P || !Ssum || !cnt || !mask_rep || !hV[3])
+        return tm_set_error(TMPNN_E_WORKSPACE, "decode_variants: workspace %zu < %zu bytes", workspace_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    const TmModeScope scope(w);
+    // rows r = v T + t. The row-wise kernels (node update + the next layer's projection, head, log-probabilities) run over all V T
+    // rows as they run over a ragged batch; the message pass shares the backbone's h_E tile between the variants of a workgroup.
+    TRY(launch_variant_expand(c.hV, c.P0, mask, w->seq_table[0], S_var, T, V, hV[0], P, mask_rep, status_opt, st));
+    for (int l = 0; l < 3; ++l) {
+        const DecW &d = w->dec[l];
+        TRY(launch_variant_msg(d.W1 + 128, 512, d.W2, d.b2, P, c.hE, c.E_idx, mask, T, V, Ssum, cnt, st));
+        const NodeProj next = dec_msg_proj(w, l < 2 ? l + 1 : 2, P, S_var);
+        TRY(launch_node_update(d.W3, d.b3, d.norm1_w, d.norm1_b, d.Win, d.bin, d.Wout, d.bout, d.norm2_w, d.norm2_b, hV[l], Ssum, cnt,
+                               mask_rep, R, hV[l + 1], l < 2 ? &next : nullptr, nullptr, st));
+    }
+    if (ddg) TRY(launch_head(w, hV[3], hV[2], S_var, R, ddg, nullptr, status_opt, st));
+    if (log_probs_opt) TRY(launch_log_probs(w, hV[3], R, log_probs_opt, status_opt, st));
+    if (!ddg && !log_probs_opt) TRY(launch_range_check(hV[3], R * TMPNN_HID, status_opt, st));
+    if (hidden_opt) TRY(launch_variant_hidden(hV + 1, T, V, hidden_opt, st));
     return TMPNN_OK;
 }

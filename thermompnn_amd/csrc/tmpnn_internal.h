@@ -149,6 +149,12 @@ bool edge_msg_fusable(int mode, int64_t T);
 int launch_edge_msg_fused(const EncW &e, const float *P_edge, float *hE, const int32_t *E_idx, bool dec, const float *W1e, int ld1,
                           const float *W2, const float *b2, const float *P_msg, const float *mask, int64_t T, float *Ssum, float *cnt,
                           hipStream_t st);
+// tmpnn_variants.hip: V sequence variants over one encoded backbone, rows r = v T + t (tmpnn_decode_variants)
+int launch_variant_expand(const float *hV, const float *P0, const float *mask, const float *tab, const int32_t *S_var, int64_t T,
+                          int64_t V, float *hV_rep, float *P, float *mask_rep, int32_t *status, hipStream_t st);
+int launch_variant_msg(const float *W1e, int ld1, const float *W2, const float *b2, const float *P, const float *hE,
+                       const int32_t *E_idx, const float *mask, int64_t T, int64_t V, float *Ssum, float *cnt, hipStream_t st);
+int launch_variant_hidden(const float *const *h, int64_t T, int64_t V, float *out, hipStream_t st);
 int launch_selftest(int32_t *status, hipStream_t st);
 int tm_num_cus();
 // Kernel-form switches (TMPNN_KNN_REG, TMPNN_NODE_DEEP, TMPNN_FUSE_SMALL ...) and the per-phase timers (TMPNN_*_PROF, which

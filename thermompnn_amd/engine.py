@@ -95,6 +95,21 @@ class Weights:
             self.handle = None
 
 
+class EncodedBackbone:
+    """What ``Engine.encode`` leaves on the device for ``Engine.decode_variants``: the opaque ctx buffer of tmpnn_encode (k-NN
+    graph, final edge features, encoder node state, decoder layer 0's sequence-free projection), the mask and offsets of the
+    packed batch, its length T and the precision it was made at (a ctx is decoded by a handle of the same precision). ``inputs``
+    keeps the backbone tensors for the range retry, which has to encode again at another precision."""
+
+    def __init__(self, ctx: torch.Tensor, mask: torch.Tensor, offsets: torch.Tensor, T: int, precision: str, inputs: tuple):
+        self.ctx, self.mask, self.offsets, self.T, self.precision, self.inputs = ctx, mask, offsets, int(T), precision, inputs
+
+    @property
+    def E_idx(self) -> torch.Tensor:
+        """The k-NN graph [T,48] (global rows of the packed batch, -1 = no neighbour): the first array of the ctx."""
+        return self.ctx[: self.T * KS * 4].view(torch.int32).view(self.T, KS)
+
+
 class Engine:
     """One weight set on one GPU. All tensors are packed along the residue axis (T = sum of lengths)."""
 
@@ -329,6 +344,83 @@ class Engine:
                 st = self._raise_status("tmpnn_ssm_forward", status)
                 if st:
                     check(self.lib.tmpnn_status_error(st), f"tmpnn_ssm_forward[{retry}]")
+        return res
+
+    # -- many sequence variants over one backbone ----------------------------------------------------
+    def encode(self, X, mask, residue_idx, chain_enc, offsets, max_len: Optional[int] = None,
+               precision: Optional[str] = None) -> "EncodedBackbone":
+        """The part of a forward that never reads the sequence — k-NN graph, edge features, three encoder layers — once for a
+        packed batch (tmpnn_encode: the launches ``ssm_forward`` makes for that part). -> an EncodedBackbone for
+        ``decode_variants``. Raises if a protein is longer than ``max_len`` (one 4-byte read-back)."""
+        max_len = self._max_len(offsets, max_len)
+        X, mask = self._f32(X), self._f32(mask)
+        ridx, cenc, offsets = self._i32(residue_idx), self._i32(chain_enc), self._i32(offsets)
+        _need_cuda(X, mask)
+        T, N = X.shape[0], offsets.numel() - 1
+        used = precision or self.precision
+        ctx = torch.empty(max(self.lib.tmpnn_encode_bytes(T), 256), dtype=torch.uint8, device=self.device)
+        ws = self._workspace(self.lib.tmpnn_encode_workspace_bytes(T))
+        self._status.zero_()
+        check(self.lib.tmpnn_encode(self.weights_for(used).handle, _ptr(X), _ptr(mask), _ptr(ridx), _ptr(cenc), _ptr(offsets), N, T,
+                                    max_len, self.K, _ptr(ctx), ctx.numel(), _ptr(self._status), _ptr(ws), ws.numel(), _stream()),
+              "tmpnn_encode")
+        if T > 0 and N > 0:
+            self._raise_status("tmpnn_encode")      # a RANGE bit is left to decode_variants, which sees it again and may retry
+        return EncodedBackbone(ctx, mask, offsets, T, used, (X, ridx, cenc, max_len))
+
+    def decode_variants(self, enc: "EncodedBackbone", S_variants, want_ddg: bool = True, want_hidden: bool = False,
+                        want_log_probs: bool = False, max_rows: Optional[int] = None, check_status: bool = True):
+        """Decoder + ddG head for V full sequences over an encoded batch: ``S_variants`` [V,T] (a variant is one sequence over the
+        packed residue axis) -> dict(ddg [V,T,21], hidden [V,3,T,128], log_probs [V,T,21]); ddg[v,t,a] is relative to the variant's
+        own residue S_variants[v,t]. V is decoded in chunks of at most ``max_rows`` rows (V * T; default 2**18) — a variant's
+        result does not depend on the chunking. Status handling as ``ssm_forward``: a non-finite result of an f16x2 decode
+        re-encodes the backbone and reruns everything at ``retry_precision`` with a warning, or raises TmpnnRangeError."""
+        if not (want_ddg or want_hidden or want_log_probs):
+            raise TmpnnError("decode_variants: no output requested")
+        S = self._i32(S_variants)
+        T = enc.T
+        if S.dim() != 2 or S.shape[1] != T:
+            raise TmpnnError(f"decode_variants: S_variants must be [V, {T}], got {tuple(S.shape)}")
+        if S.numel() and (int(S.min()) < 0 or int(S.max()) >= VOCAB):
+            raise TmpnnError(f"decode_variants: residue indices must lie in [0, {VOCAB})")
+        V, dev = S.shape[0], self.device
+        res = {}
+        if want_ddg:
+            res["ddg"] = torch.empty((V, T, VOCAB), dtype=torch.float32, device=dev)
+        if want_hidden:
+            res["hidden"] = torch.empty((V, 3, T, HID), dtype=torch.float32, device=dev)
+        if want_log_probs:
+            res["log_probs"] = torch.empty((V, T, VOCAB), dtype=torch.float32, device=dev)
+        if V == 0 or T == 0:
+            return res
+        rows = int(max_rows) if max_rows is not None else 1 << 18
+        per = max(1, rows // T)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)     # per call: OR of the chunks' words
+
+        def run(e: "EncodedBackbone") -> int:
+            w = self.weights_for(e.precision)
+            ws = self._workspace(self.lib.tmpnn_decode_variants_workspace_bytes(T, min(per, V)))
+            status.zero_()
+            for v0 in range(0, V, per):
+                v1 = min(V, v0 + per)
+                part = lambda k: _ptr(res[k][v0:v1]) if k in res else None
+                check(self.lib.tmpnn_decode_variants(w.handle, _ptr(e.ctx), e.ctx.numel(), _ptr(S[v0:v1]), v1 - v0, _ptr(e.mask), T,
+                                                     part("ddg"), part("hidden"), part("log_probs"), _ptr(self._status), _ptr(ws),
+                                                     ws.numel(), _stream()), "tmpnn_decode_variants")
+                status.bitwise_or_(self._status)
+            return int(status.item()) if check_status else 0
+
+        st = run(enc)
+        if st & _lib.STATUS_RANGE:
+            retry, used = self.retry_precision, enc.precision
+            if used != "f16x2" or not retry or retry == used:
+                check(self.lib.tmpnn_status_error(st), f"tmpnn_decode_variants[{used}]")
+            warnings.warn(f"ThermoMPNN HIP engine: non-finite result in {used} (an operand left the fp16 range); "
+                          f"rerunning this batch at precision {retry}", RuntimeWarning, stacklevel=2)
+            X, ridx, cenc, max_len = enc.inputs
+            st = run(self.encode(X, enc.mask, ridx, cenc, enc.offsets, max_len=max_len, precision=retry))
+        if st:
+            check(self.lib.tmpnn_status_error(st), "tmpnn_decode_variants")
         return res
 
     def capture_graph(self, X, S, mask, residue_idx, chain_enc, offsets, max_len: int, out: Optional[dict] = None, **want):

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import os
 
+import numpy as np
 import torch
 
 from . import weights as _weights
@@ -106,6 +107,42 @@ class TransferModel(_EngineOwner):
             else:
                 ddg, z = res["ddg"], eng.ddg_head(res["hidden"][2], res["hidden"][1], S[0], want_z=True)[1]
             return ddg if self.subtract_mut else z * self.ddg_out.weight.view(()) + self.ddg_out.bias.view(())
+
+    def variant_tables(self, pdb, variants) -> torch.Tensor:
+        """``ssm_table`` of the same backbone under V other sequences, [V, L, 21] on the model's device: the encoder runs once, the
+        decoder and the head once per variant (Engine.encode + Engine.decode_variants). A variant is a full one-letter sequence of
+        length L, a list of ``Mutation`` applied to the parsed sequence (ValueError on a wrong length, a position out of range, a
+        stated wild type that differs from the parsed residue, a substitution at a '-' position), or — all variants at once — an
+        integer matrix [V, L] of ALPHABET indices. Entry [v, pos, a] is relative to the variant's own residue at pos;
+        ``subtract_mut=False`` models return the un-subtracted head output, as ``ssm_table`` does."""
+        from .variant_scan import variant_matrix
+        entry = pdb[0] if isinstance(pdb, (list, tuple)) else pdb
+        device = next(self.parameters()).device
+        feats = tied_featurize([entry], device, None, None, None, None, None, None, ca_only=False)
+        X, mask, chain_enc, residue_idx = feats[0], feats[2], feats[5], feats[12]
+        if isinstance(variants, (np.ndarray, torch.Tensor)):
+            Sv = torch.as_tensor(variants)
+        else:
+            Sv = torch.from_numpy(variant_matrix(entry["seq"], list(variants)))
+        eng = self.engine()
+        L = X.shape[1]
+        if Sv.dim() != 2 or Sv.shape[1] != L:
+            raise ValueError(f"variants: expected [V, {L}] sequences, got {tuple(Sv.shape)}")
+        V = Sv.shape[0]
+        with torch.cuda.device(eng.device):
+            enc = eng.encode(X[0], mask[0], residue_idx[0], chain_enc[0], torch.tensor([0, L], dtype=torch.int32), max_len=L)
+            std = self.subtract_mut and not self.generic_head
+            res = eng.decode_variants(enc, Sv, want_ddg=not self.generic_head, want_hidden=not std)
+            if std:
+                return res["ddg"]
+            Sf = Sv.reshape(-1).to(device=eng.device, dtype=torch.int32)
+            hid = res["hidden"].permute(1, 0, 2, 3).reshape(3, V * L, HIDDEN_DIM).contiguous()      # the head runs over V L rows
+            if self.generic_head:
+                ddg, z = self._generic_tables(eng, hid, Sf)
+            else:
+                ddg, z = res["ddg"].view(V * L, VOCAB_DIM), eng.ddg_head(hid[2], hid[1], Sf, want_z=True)[1]
+            out = ddg if self.subtract_mut else z * self.ddg_out.weight.view(()) + self.ddg_out.bias.view(())
+            return out.view(V, L, VOCAB_DIM)
 
     def forward(self, pdb, mutations, tied_feat=True):
         if self.differentiable:

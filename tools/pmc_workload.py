@@ -16,6 +16,17 @@ from thermompnn_amd.weights import synthetic_state_dict  # noqa: E402
 dev = torch.device("cuda:0")
 eng = Engine(synthetic_state_dict(0), dev, 48)
 b = build_batch(64, 256, 0, dev)
+if sys.argv[1:] == ["variants"]:      # a pass of its own: its single-protein encode must not enter the bench batch's per-kernel means
+    # the variant decoder on the bench protein: 64 sequences over one encoded backbone (its message kernel reads a residue's h_E tile once
+    # per chunk of variants; the per-variant figure is the launch's FETCH_SIZE / 64)
+    enc = eng.encode(b["X"][:256], b["mask"][:256], b["ridx"][:256], b["cenc"][:256], b["offsets"][:2], max_len=256)
+    Sv = b["S"][:256].repeat(64, 1)
+    Sv[torch.arange(64), torch.arange(64)] = (Sv[torch.arange(64), torch.arange(64)] + 1) % 20
+    for _ in range(3):
+        eng.decode_variants(enc, Sv)
+    torch.cuda.synchronize()
+    print("ok variants")
+    raise SystemExit(0)
 out = {"ddg": torch.empty((b["T"], 21), device=dev)}
 for _ in range(3):
     eng.ssm_forward(b["X"], b["S"], b["mask"], b["ridx"], b["cenc"], b["offsets"], max_len=256, out=out)
