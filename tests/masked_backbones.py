@@ -8,16 +8,39 @@ Indices here are 0-based residue positions; the PDB numbers residues from 1.
 """
 import os
 
-from thermompnn_amd.synthetic import backbone_pdb_text, synthetic_backbone
+import numpy as np
 
-# name -> (L, backbone seed, residues without their N line, residues removed entirely). Each layout has a masked first residue,
-# a masked last residue, isolated masked residues and a run of 3.
+from thermompnn_amd.synthetic import AA20, backbone_pdb_text, synthetic_backbone
+
+# name -> (L, backbone seed, residues without their N line, residues removed entirely). msk_L40 and msk_L56 have a masked first
+# residue, a masked last residue, isolated masked residues and a run of 3. In EVERY layout the protein has fewer than 48 unmasked
+# residues, so every unmasked row's neighbour list holds masked residues (all of them at that row's D_max, behind the unmasked ones).
 LAYOUTS = {
+    # one unmasked row whose whole list is itself plus one masked residue
+    "msk_L2": (2, 5, (1,), ()),
+    # less than one 48-row tile, 31 of the 48 slots are j < 0: first, last and a gap run of 2 masked
+    "msk_L17": (17, 9, (0, 16), (8, 9)),
+    # one j < 0 slot
+    "msk_L47": (47, 11, (0, 46), (20,)),
+    # 45 unmasked residues: an unmasked row takes 3 of the 4 masked ones, all tied at D_max
+    "msk_L49": (49, 10, (0, 48), (17, 18)),
     # K = L: every row has masked neighbours (10 of 40 masked)
     "msk_L40": (40, 5, (0, 12, 30, 31, 39), (7, 20, 21, 22, 26)),
     # K = 48 < L with 46 unmasked residues: every unmasked row's top 48 holds masked neighbours at that row's D_max
     "msk_L56": (56, 5, (0, 9, 40, 41, 55), (18, 30, 31, 32, 47)),
+    # msk_L56 cut into two chains (CHAIN_CUT): chain_enc changes and residue_idx jumps by 100 at the cut
+    "msk_L56_2ch": (56, 5, (0, 9, 40, 41, 55), (18, 30, 31, 32, 47)),
 }
+CHAIN_CUT = {"msk_L56_2ch": 28}            # first residue of the second chain; layout_arrays only (write_layout writes one chain)
+# name -> (a masked residue that unmasked rows list on the oracle's graph and on the device's, the letter that replaces its own in the
+# "seen_masked_substitution" variant). The device's k-NN breaks the D_max tie towards the lowest index, torch.topk as it likes; in
+# msk_L49 / msk_L56 the residue is among the lowest-indexed masked ones (3 resp. 2 are taken) and torch lists it in 21 rows or more.
+# Residue and letter are the pair that moves the oracle's ddG of some unmasked row most, over every masked residue and all 20
+# letters, on both graphs (a neighbour at D_max moves it by 0.004 .. 0.013 kcal/mol): 1.26e-2, 1.34e-2, 1.27e-2, 1.18e-2, 1.008e-2,
+# 1.05e-2 and 1.29e-2 in the order below, against the 1e-2 the tests ask for. The backbone seeds of the four small layouts were
+# chosen for that margin; msk_L40 keeps the seed the training tests use, and with it the thinnest margin.
+SEEN = {"msk_L2": (1, 19), "msk_L17": (0, 10), "msk_L47": (46, 19), "msk_L49": (0, 7), "msk_L40": (30, 19), "msk_L56": (9, 19),
+        "msk_L56_2ch": (9, 19)}
 
 
 def masked_pdb_text(L, seed, missing_n=(), gaps=()):
@@ -37,6 +60,7 @@ def masked_pdb_text(L, seed, missing_n=(), gaps=()):
 
 def write_layout(name, directory):
     """Writes LAYOUTS[name] as <directory>/<name>.pdb -> its path."""
+    assert name not in CHAIN_CUT, "one chain per file"
     L, seed, missing_n, gaps = LAYOUTS[name]
     path = os.path.join(str(directory), f"{name}.pdb")
     with open(path, "w") as fh:
@@ -49,3 +73,85 @@ def expected(name):
     L, _, missing_n, gaps = LAYOUTS[name]
     masked = set(missing_n) | set(gaps)
     return [0 if i in masked else 1 for i in range(L)], sorted(gaps)
+
+
+def layout_arrays(name):
+    """-> X [L,4,3] float32, S [L] int64, mask [L] float32, residue_idx [L] int64, chain_enc [L] int64 of LAYOUTS[name], as
+    alt_parse_PDB + tied_featurize give them for write_layout's file: coordinates with the three decimals of the PDB text, missing
+    atoms zeroed (a residue without its N line keeps its other atoms and its letter), gaps carry token 20."""
+    L, seed, missing_n, gaps = LAYOUTS[name]
+    X, seq = synthetic_backbone(L, seed)
+    X = np.array([float(f"{v:8.3f}") for v in X.ravel()]).reshape(L, 4, 3)
+    S = np.array([AA20.index(c) for c in seq], dtype=np.int64)
+    mask = np.ones(L, np.float32)
+    for i in missing_n:
+        X[i, 0] = 0.0
+        mask[i] = 0
+    for i in gaps:
+        X[i] = 0.0
+        S[i] = 20
+        mask[i] = 0
+    chain = np.ones(L, np.int64)
+    if name in CHAIN_CUT:
+        chain[CHAIN_CUT[name]:] += 1
+    return X.astype(np.float32), S, mask, 100 * (chain - 1) + np.arange(L), chain
+
+
+def variants_of(name):
+    """name -> sequence [L] int64 of the variants the masked-form tests decode: the wild type; a substitution at an unmasked
+    residue; one at the layout's SEEN masked residue; a gap token 20 replaced by a letter (where the layout has a gap) together with
+    a letter of an unmasked residue replaced by 20; a fully redrawn sequence (tokens 0..20)."""
+    _, S, mask, _, _ = layout_arrays(name)
+    live = np.nonzero(mask > 0)[0]
+    out = {"wild_type": S.copy()}
+    one = S.copy()
+    p = int(live[len(live) // 2])
+    one[p] = (one[p] + 3) % 20
+    out["unmasked_substitution"] = one
+    seen = S.copy()
+    seen[SEEN[name][0]] = SEEN[name][1]
+    out["seen_masked_substitution"] = seen
+    swap = S.copy()
+    gaps = np.nonzero(S == 20)[0]
+    if len(gaps):
+        swap[gaps[0]] = 7
+    swap[int(live[len(live) // 3])] = 20
+    out["gap_and_letter_swapped"] = swap
+    out["redrawn"] = np.random.default_rng(7).integers(0, 21, len(S))
+    return out
+
+
+_ORACLE = {}
+
+
+def oracle_trace(name, S=None, E_idx=None, f64=False, weight_seed=0):
+    """The CPU oracle's trace {tensor name: array} of layout ``name`` with sequence ``S`` (default: its own) and synthetic weights
+    ``weight_seed``, on the neighbour graph ``E_idx`` [L, K] (default: the oracle's own top-48), in fp32 or evaluated in float64.
+    Cached per (layout, sequence, graph); callers leave the arrays unchanged."""
+    import torch
+    from oracle import thermompnn_oracle as orc
+    from thermompnn_amd.weights import synthetic_state_dict
+    X, S0, mask, ridx, cenc = layout_arrays(name)
+    S = S0 if S is None else np.asarray(S, dtype=np.int64)
+    key = (name, S.tobytes(), None if E_idx is None else np.ascontiguousarray(E_idx).astype(np.int64).tobytes(), f64, weight_seed)
+    if key in _ORACLE:
+        return _ORACLE[key]
+    t = torch.from_numpy
+    dt = torch.float64 if f64 else torch.float32
+    orig_float, orig_default = torch.Tensor.float, torch.get_default_dtype()
+    if f64:                                                    # the oracle's explicit .float() casts -> float64 (conftest.oracle_trace_f64)
+        torch.Tensor.float = lambda self, *a, **k: self.double()
+        torch.set_default_dtype(torch.float64)
+    try:
+        W = {k: v.to(dt) for k, v in synthetic_state_dict(weight_seed).items()}
+        m = t(mask).to(dt)[None]
+        ov = None if E_idx is None else t(np.ascontiguousarray(E_idx).astype(np.int64))[None]
+        tr = {}
+        with torch.no_grad():
+            orc.ssm_table(W, t(X).to(dt)[None], t(S)[None], m, torch.ones_like(m), t(ridx)[None], t(cenc)[None], 48, trace=tr,
+                          E_idx_override=ov)
+    finally:
+        torch.Tensor.float = orig_float
+        torch.set_default_dtype(orig_default)
+    _ORACLE[key] = {k: v[0].numpy() for k, v in tr.items()}
+    return _ORACLE[key]
