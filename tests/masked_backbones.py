@@ -33,7 +33,8 @@ LAYOUTS = {
 }
 CHAIN_CUT = {"msk_L56_2ch": 28}            # first residue of the second chain; layout_arrays only (write_layout writes one chain)
 # name -> (a masked residue that unmasked rows list on the oracle's graph and on the device's, the letter that replaces its own in the
-# "seen_masked_substitution" variant). The device's k-NN breaks the D_max tie towards the lowest index, torch.topk as it likes; in
+# "seen_masked_substitution" variant). The device's k-NN breaks the D_max tie towards the lowest index (its documented rule, DESIGN.md
+# "Ties", pinned on exact lattices by test_gpu_knn_exact.py), torch.topk as it likes; in
 # msk_L49 / msk_L56 the residue is among the lowest-indexed masked ones (3 resp. 2 are taken) and torch lists it in 21 rows or more.
 # Residue and letter are the pair that moves the oracle's ddG of some unmasked row most, over every masked residue and all 20
 # letters, on both graphs (a neighbour at D_max moves it by 0.004 .. 0.013 kcal/mol): 1.26e-2, 1.34e-2, 1.27e-2, 1.18e-2, 1.008e-2,

@@ -263,8 +263,8 @@ def test_every_gradient_matches_a_float64_restatement(tmp_path, case, head, subt
 
 def _check_neighbour_sets(prot, Ei):
     """The device's k-NN on the unmasked rows equals the oracle's, up to exact ties at the K-th adjusted distance (the device takes
-    the lower index; torch.topk leaves tie order unspecified). A masked row's candidates all sit at its D_max: its
-    neighbour order is arbitrary and reaches nothing."""
+    the lower index; torch.topk leaves tie order unspecified). A masked row's candidates all sit at distance 0: the device
+    lists 0 .. K-1 (test_gpu_knn_exact.py), torch.topk whatever it likes, and the row reaches nothing, so it is not compared here."""
     from oracle import thermompnn_oracle as O
     from test_gpu_parity import topk_rows_differing
     X, mask = prot.X.cpu()[None], prot.mask.cpu()[None]
@@ -498,7 +498,7 @@ def test_loss_and_gradients_match_the_reference_golden(tmp_path, golden, src):
         E_idx = torch.empty((L, K), dtype=torch.int32, device="cuda")
         kw = dict(keep_in=torch.from_numpy(drawn).cuda(), p_mpnn=0.1) if tag == "drawn" else dict(p_mpnn=0.0)
         loss = tr.forward_backward(prot, p_head=0.0, step=int(g["step"]), E_idx_out=E_idx, **kw)
-        live = prot.mask.cpu().numpy() > 0           # a masked row's neighbour order is arbitrary and does not reach the loss
+        live = prot.mask.cpu().numpy() > 0           # a masked row's order in the REFERENCE's graph is torch.topk's choice; it does not reach the loss
         assert np.array_equal(E_idx.cpu().numpy()[live], g["E_idx"][live]), "the device's k-NN graph differs from the reference's"
         ref_loss = float(g[f"{tag}_loss"])
         assert abs(float(loss) - ref_loss) <= 1e-6 * abs(ref_loss), (tag, float(loss), ref_loss)

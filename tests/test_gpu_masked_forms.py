@@ -1,8 +1,8 @@
 """Masked neighbours in unmasked rows and short chains (j < 0 slots), in every form of the inference forward: the layouts of
 tests/masked_backbones.py (fewer than 48 unmasked residues each, so every unmasked row lists masked residues; checked on the host by
 test_masked_forms_host.py) through the single operators, the fused forward at its three launch bands and the variant decoder, in
-fp32, bf16x3 and f16x2, against the CPU oracle on the device's own neighbour graph (which masked residue wins the D_max tie is
-implementation-defined). No row is left out: ddG, log-probabilities and node states on all rows, per-edge tensors on unmasked rows,
+fp32, bf16x3 and f16x2, against the CPU oracle on the device's own neighbour graph (torch.topk leaves open which masked residue wins
+the D_max tie; the device takes the lower index, DESIGN.md "Ties", pinned by test_gpu_knn_exact.py). No row is left out: ddG, log-probabilities and node states on all rows, per-edge tensors on unmasked rows,
 decoder states of masked rows exactly 0. The worst error per (precision, quantity) goes to masked_forms_worst.json in the directory
 TMPNN_EVIDENCE_DIR names (default: a temporary directory)."""
 import json
