@@ -321,6 +321,20 @@ size_t tmpnn_decode_variants_workspace_bytes(int64_t T, int64_t V);
 int tmpnn_decode_variants(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const int32_t *S_var, int64_t V,
                           const float *mask, int64_t T, float *ddg, float *hidden_opt, float *log_probs_opt,
                           int32_t *status_opt, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream);
+/* The same decode under a decoding order per variant: the reference's masked decoder (protein_mpnn_utils.py:1247-1272 without the
+ * overwrite of :1259) as ProteinMPNN.conditional_probs / unconditional_probs run it (:1496-1587). rank [V,T]: residue i of variant
+ * v sees neighbour j's identity and decoder state when rank[v][j] < rank[v][i]; of every other neighbour it sees the encoder
+ * state alone (mask_bw / mask_fw of the reference; h_E is always present, everything times mask[i]). rank is the inverse
+ * permutation of the reference's decoding_order; ranks are only compared between a residue and its listed neighbours, any int32
+ * is legal, equal ranks mean "not visible" (all ranks equal: unconditional_probs). Arguments, outputs, error codes, the no-op on
+ * T == 0 or V == 0 and status_opt as tmpnn_decode_variants; additionally (V + 1) * T < 2^24 (32-bit offsets into the projection
+ * table of V variants + the encoder state): TMPNN_E_UNSUPPORTED beyond it, and tmpnn_decode_ordered_workspace_bytes returns 0.
+ * A variant's result has the same bits whatever V is and whichever slot it takes. */
+size_t tmpnn_decode_ordered_workspace_bytes(int64_t T, int64_t V);
+int tmpnn_decode_ordered(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const int32_t *S_var,
+                         const int32_t *rank, int64_t V, const float *mask, int64_t T, float *ddg_opt,
+                         float *hidden_opt, float *log_probs_opt, int32_t *status_opt,
+                         void *workspace, size_t workspace_bytes, tmpnn_stream_t stream);
 
 /* ---- host side: native PDB reader + packer ------------------------------------------
  * Replaces alt_parse_PDB (protein_mpnn_utils.py:183-350) + the packing of tied_featurize (:353-605) for one

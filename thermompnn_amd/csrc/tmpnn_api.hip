@@ -858,3 +858,75 @@ extern "C" int tmpnn_decode_variants(const tmpnn_weights_t *w, const void *ctx, 
     if (hidden_opt) TRY(launch_variant_hidden(hV + 1, T, V, hidden_opt, st));
     return TMPNN_OK;
 }
+
+// ---- order-masked decoding over one encoded backbone --------------------------------------------------
+// (V + 1) T rows of 256 floats are addressed with 32-bit offsets inside the order-masked message kernel
+static const int64_t ORD_ROWS_MAX = ((int64_t)1 << 24) - 1;
+
+extern "C" size_t tmpnn_decode_ordered_workspace_bytes(int64_t T, int64_t V) {
+    if (T < 0 || V < 0 || (V > 0 && (T > T_MAX / V || T > ORD_ROWS_MAX / (V + 1)))) return 0;
+    const size_t R = (size_t)T * (size_t)V;
+    return align256((R + (size_t)T) * 256 * 4) + 5 * align256(R * TMPNN_HID * 4) + 2 * align256(R * 4) + align256(R * 8) +
+           align256((size_t)T * TMPNN_KS * 4) + 256;
+}
+
+extern "C" int tmpnn_decode_ordered(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const int32_t *S_var,
+                                    const int32_t *rank, int64_t V, const float *mask, int64_t T, float *ddg, float *hidden_opt,
+                                    float *log_probs_opt, int32_t *status_opt, void *workspace, size_t workspace_bytes,
+                                    tmpnn_stream_t stream) {
+    REQUIRE(w, "decode_ordered: null weight handle");
+    REQUIRE(T >= 0 && T <= T_MAX && V >= 0, "decode_ordered: bad sizes (T=%lld, V=%lld)", (long long)T, (long long)V);
+    REQUIRE(!ddg || w->n_tensors == TMPNN_N_TENSORS, "decode_ordered: ddg requested but the handle has no head tensors");
+    if (T == 0 || V == 0) return TMPNN_OK;            // nothing to decode (pointers may be null)
+    if (T > T_MAX / V)
+        return tm_set_error(TMPNN_E_UNSUPPORTED, "decode_ordered: V * T = %lld * %lld rows exceed %lld (decode the variants in chunks)",
+                            (long long)V, (long long)T, (long long)T_MAX);
+    if (T > ORD_ROWS_MAX / (V + 1))
+        return tm_set_error(TMPNN_E_UNSUPPORTED, "decode_ordered: (V + 1) * T = %lld * %lld rows exceed %lld (decode the variants in chunks)",
+                            (long long)(V + 1), (long long)T, (long long)ORD_ROWS_MAX);
+    REQUIRE(S_var && rank && mask, "decode_ordered: null input pointer");
+    REQUIRE(ddg || hidden_opt || log_probs_opt, "decode_ordered: no output requested");
+    EncCtx c;
+    TRY(carve_ctx("decode_ordered", const_cast<void *>(ctx), ctx_bytes, T, &c));
+    const int64_t R = V * T;
+    const size_t need = tmpnn_decode_ordered_workspace_bytes(T, V);
+    uintptr_t base = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
+    if (!workspace || workspace_bytes < need)
+        return tm_set_error(TMPNN_E_WORKSPACE, "decode_ordered: workspace %zu < %zu bytes", workspace_bytes, need);
+    Carver cv{(char *)base, workspace_bytes - (base - (uintptr_t)workspace)};
+    float *P = (float *)cv.take((size_t)(R + T) * 256 * 4);         // [V + 1, T, 256]: slot V = Penc_l, the encoder state's projection
+    float *Ssum = (float *)cv.take((size_t)R * TMPNN_HID * 4);
+    float *cnt = (float *)cv.take((size_t)R * 4);
+    float *mask_rep = (float *)cv.take((size_t)R * 4);
+    void *vis = cv.take((size_t)R * 8);
+    int32_t *remap = (int32_t *)cv.take((size_t)T * TMPNN_KS * 4);
+    float *hV[4];
+    for (int i = 0; i < 4; ++i) hV[i] = (float *)cv.take((size_t)R * TMPNN_HID * 4);
+    if (!P || !Ssum || !cnt || !mask_rep || !vis || !remap || !hV[3])
+        return tm_set_error(TMPNN_E_WORKSPACE, "decode_ordered: workspace %zu < %zu bytes", workspace_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    const TmModeScope scope(w);
+    float *Penc = P + (size_t)R * 256;
+    // As tmpnn_decode_variants, but the message pass of every layer picks each neighbour's row by rank: the variant's own
+    // projection (this layer's state + sequence term) for a neighbour decoded earlier, Penc_l (no sequence) for the others.
+    TRY(launch_variant_expand(c.hV, c.P0, mask, w->seq_table[0], S_var, T, V, hV[0], P, mask_rep, status_opt, st));
+    TRY(launch_variant_penc0(c.P0, T, Penc, st));               // Penc_0 = P0 (its neighbour half is W1c_0 h_V_enc)
+    TRY(launch_variant_vis(rank, c.E_idx, T, V, vis, st));
+    for (int l = 0; l < 3; ++l) {
+        const DecW &d = w->dec[l];
+        TRY(launch_variant_msg(d.W1 + 128, 512, d.W2, d.b2, P, c.hE, c.E_idx, mask, T, V, Ssum, cnt, st, vis, remap));
+        const NodeProj next = dec_msg_proj(w, l < 2 ? l + 1 : 2, P, S_var);
+        TRY(launch_node_update(d.W3, d.b3, d.norm1_w, d.norm1_b, d.Win, d.bin, d.Wout, d.bout, d.norm2_w, d.norm2_b, hV[l], Ssum, cnt,
+                               mask_rep, R, hV[l + 1], l < 2 ? &next : nullptr, nullptr, st));
+        if (l < 2) {                                  // T rows, not V T: the next layer's projection of the ENCODER state
+            const DecW &n = w->dec[l + 1];
+            const NodeProj pe{n.W1, 512, n.b1, n.W1 + 384, 512, Penc, nullptr, nullptr};
+            TRY(launch_node_proj(c.hV, pe, T, st));
+        }
+    }
+    if (ddg) TRY(launch_head(w, hV[3], hV[2], S_var, R, ddg, nullptr, status_opt, st));
+    if (log_probs_opt) TRY(launch_log_probs(w, hV[3], R, log_probs_opt, status_opt, st));
+    if (!ddg && !log_probs_opt) TRY(launch_range_check(hV[3], R * TMPNN_HID, status_opt, st));
+    if (hidden_opt) TRY(launch_variant_hidden(hV + 1, T, V, hidden_opt, st));
+    return TMPNN_OK;
+}

@@ -153,7 +153,11 @@ int launch_edge_msg_fused(const EncW &e, const float *P_edge, float *hE, const i
 int launch_variant_expand(const float *hV, const float *P0, const float *mask, const float *tab, const int32_t *S_var, int64_t T,
                           int64_t V, float *hV_rep, float *P, float *mask_rep, int32_t *status, hipStream_t st);
 int launch_variant_msg(const float *W1e, int ld1, const float *W2, const float *b2, const float *P, const float *hE,
-                       const int32_t *E_idx, const float *mask, int64_t T, int64_t V, float *Ssum, float *cnt, hipStream_t st);
+                       const int32_t *E_idx, const float *mask, int64_t T, int64_t V, float *Ssum, float *cnt, hipStream_t st,
+                       const void *vis = nullptr, int32_t *remap = nullptr);
+// order-masked decode (tmpnn_decode_ordered): visibility words [V T] x 8 bytes from rank [V,T]; P0 -> slot V of the table (layer 0)
+int launch_variant_vis(const int32_t *rank, const int32_t *E_idx, int64_t T, int64_t V, void *vis, hipStream_t st);
+int launch_variant_penc0(const float *P0, int64_t T, float *Penc, hipStream_t st);
 int launch_variant_hidden(const float *const *h, int64_t T, int64_t V, float *out, hipStream_t st);
 int launch_selftest(int32_t *status, hipStream_t st);
 int tm_num_cus();

@@ -1,5 +1,6 @@
-// Decoder message pass of MANY sequence variants over ONE encoded backbone (tmpnn_decode_variants), split-precision forms (f16x2 and
-// bf16x3): var_msg8_kernel. Plus the two row-wise helpers of that entry (variant_expand_kernel, variant_hidden_kernel).
+// Decoder message pass of MANY sequence variants over ONE encoded backbone (tmpnn_decode_variants, tmpnn_decode_ordered),
+// split-precision forms (f16x2 and bf16x3): var_msg8_kernel<SP, ORD>. Plus the row-wise
+// helpers of those entries (variant_expand_kernel, variant_hidden_kernel, variant_vis_kernel, variant_penc0_kernel, variant_remap_kernel).
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -22,6 +23,14 @@
 // every wavefront left before it reached the barrier of variant v. The next variant's gathers ride behind the first MFMA steps of
 // GEMM 2 (their rows differ per variant; the addresses do not, up to the uniform base).
 // f16x2 reads the K-permuted fragment images of W1e / W2 and writes its planes in that K order (perm_c4), as every message kernel.
+//
+// Order-masked form (ORD, tmpnn_decode_ordered; protein_mpnn_utils.py:1247-1272 without the overwrite of :1259, as conditional_probs
+// :1496-1587 decodes): neighbour j of residue i is VISIBLE to variant v when rank[v][j] < rank[v][i]. A visible neighbour gives
+// the variant's own projection row (decoder state of this layer + sequence term), an invisible one the row of the ENCODER state's
+// projection Penc_l[j] = W1c_l h_V_enc[j], which knows neither the variant nor the sequence. P is then a [V + 1, T, 256] table
+// whose slot V is Penc_l, and the only change to the loop is where a gather points: one 64-bit visibility word per (variant,
+// residue) — bit k = slot k visible, made by variant_vis_kernel — is read wave-uniformly with the next variant's prefetch, and
+// each lane picks between the two slot bases with its bits 16 rb + m. All offsets stay 32-bit: the launcher bounds (V + 1) T.
 // ------------------------------------------------------------------------------------------------
 struct VarMsgArgs {
     const float *W1e; int ld1;
@@ -32,9 +41,18 @@ struct VarMsgArgs {
     float *Ssum, *cnt;                      // [V T, 128], [V T]
     int T, V, VC, n_chunks;                 // workgroup b: residue b / n_chunks, variants [VC (b % n_chunks), + VC)
     const char *imgp1, *imgp2;              // f16x2: K-permuted fragment images of W1e / W2
+    const uint2 *vis;                       // ORD: [V T] visibility words, bit k of (x | y << 32) = slot k of the residue is visible
+    unsigned enc_off;                       // ORD: V T 256, the float offset of slot V (Penc_l) inside P
 };
 
-template <typename SP>
+// ORD: a lane's gather of row block rb goes to the variant's slot (float offset var_off) or to slot V (enc_off), by bit
+// 16 rb + m of the residue's visibility word
+__device__ __forceinline__ unsigned var_ord_off(unsigned goff, int rb, int m, uint2 wd, unsigned var_off, unsigned enc_off) {
+    const unsigned bit = ((rb < 2 ? wd.x : wd.y) >> (16 * (rb & 1) + m)) & 1u;
+    return goff + (bit ? var_off : enc_off);
+}
+
+template <typename SP, bool ORD = false>
 __global__ __launch_bounds__(512, 2) void var_msg8_kernel(VarMsgArgs a) {
     constexpr int TILEB = SP::NP * SPLIT_PLANE_BYTES;
     __shared__ __attribute__((aligned(16))) char tA[2][TILEB];     // activation planes; [1] holds the e planes until GEMM 1 is through
@@ -87,15 +105,27 @@ __global__ __launch_bounds__(512, 2) void var_msg8_kernel(VarMsgArgs a) {
     }
     const unsigned soff = (unsigned)i * 256u + ucol;
     const size_t vstride = (size_t)a.T * 256;
+    auto vis_word = [&](int v) {                                // wave-uniform: one word per (variant, residue)
+        const uint2 wd = a.vis[(size_t)v * a.T + i];
+        return uint2{(unsigned)__builtin_amdgcn_readfirstlane((int)wd.x), (unsigned)__builtin_amdgcn_readfirstlane((int)wd.y)};
+    };
     f4 g0, gj[3];
     {
         const float *Pv = a.P + (size_t)v0 * vstride;           // wave-uniform base + 32-bit lane offsets
         g0 = ld4(Pv + soff);
+        if constexpr (ORD) {
+            const uint2 wd = vis_word(v0);
 #pragma unroll
-        for (int rb = 0; rb < 3; ++rb) gj[rb] = ld4(Pv + goff[rb]);
+            for (int rb = 0; rb < 3; ++rb) gj[rb] = ld4(a.P + var_ord_off(goff[rb], rb, m, wd, (unsigned)v0 * (unsigned)vstride, a.enc_off));
+        } else {
+#pragma unroll
+            for (int rb = 0; rb < 3; ++rb) gj[rb] = ld4(Pv + goff[rb]);
+        }
     }
     int buf = 0;
     for (int v = v0; v < v1; ++v) {
+        uint2 wn = uint2{0u, 0u};
+        if constexpr (ORD) wn = vis_word(v + 1 < v1 ? v + 1 : v);      // the next variant's word, on its way through the GELU below
 #pragma unroll
         for (int rb = 0; rb < 3; ++rb) store_split<SP>(tA[buf], 16 * rb + m, c4s, gelu4(g0 + mi * (e1[rb][0] + gj[rb])));
         __syncthreads();                                        // the one barrier of a variant: tA[buf] complete
@@ -106,7 +136,11 @@ __global__ __launch_bounds__(512, 2) void var_msg8_kernel(VarMsgArgs a) {
         mma_tile_split_ride<SP, 4, 3, TM_MSG_PF>(tA[buf], w2, acc, lane, [&](auto S) {
             constexpr int s = decltype(S)::value;
             if constexpr (s == 0) g0 = ld4(Pn + soff);
-            if constexpr (s >= 1 && s <= 3) gj[s - 1] = ld4(Pn + goff[s - 1]);
+            if constexpr (s >= 1 && s <= 3) {
+                if constexpr (ORD)        // (V + 1) T 256 < 2^32 (launcher)
+                    gj[s - 1] = ld4(a.P + var_ord_off(goff[s - 1], s - 1, m, wn, (unsigned)(v + 1 < v1 ? v + 1 : v) * (unsigned)vstride, a.enc_off));
+                else gj[s - 1] = ld4(Pn + goff[s - 1]);
+            }
         });
         f4 tot = f4{0.f, 0.f, 0.f, 0.f};                        // masked sum over the 48 neighbours, as msg8_rp_kernel forms it
 #pragma unroll
@@ -131,6 +165,47 @@ __global__ __launch_bounds__(512, 2) void var_msg8_kernel(VarMsgArgs a) {
         if (m == 15) st4(a.Ssum + row * TM_H + ucol, tot);
         if (tid == 0) a.cnt[row] = cntv;
         buf ^= 1;
+    }
+}
+
+// Rows of an ordered decode: one wavefront per row r = v T + i makes the row's visibility word — bit k is set when slot k of
+// residue i holds a neighbour j with rank[v][j] < rank[v][i] (equal ranks: not visible; empty slots: 0).
+__global__ __launch_bounds__(TM_THREADS) void variant_vis_kernel(const int32_t *__restrict__ rank, const int32_t *__restrict__ E_idx,
+                                                                 int T, int64_t R, uint2 *__restrict__ vis) {
+    const int lane = tm_tid() & 63;
+    const int64_t wpb = TM_THREADS / 64, nw = (int64_t)tm_nblk() * wpb;
+    for (int64_t r = (int64_t)tm_bid() * wpb + (tm_tid() >> 6); r < R; r += nw) {
+        const int64_t v = r / T;
+        const int i = (int)(r - v * T);
+        const int32_t *rk = rank + v * T;
+        bool see = false;
+        if (lane < TM_KS) {
+            const int j = E_idx[(size_t)i * TM_KS + lane];
+            see = j >= 0 && rk[j] < rk[i];
+        }
+        const unsigned long long word = __ballot(see);
+        if (lane == 0) vis[r] = uint2{(unsigned)word, (unsigned)(word >> 32)};
+    }
+}
+
+// Slot V of an ordered decode's [V + 1, T, 256] table for decoder layer 0: the sequence-free projection the encode context holds
+// (its neighbour half is W1c_0 h_V_enc). The later layers' slot V is a node_proj of the encoder state.
+__global__ __launch_bounds__(TM_THREADS) void variant_penc0_kernel(const float *__restrict__ P0, int64_t T, float *__restrict__ Penc) {
+    const int64_t n = T * 64;
+    for (int64_t k = (int64_t)tm_bid() * TM_THREADS + tm_tid(); k < n; k += (int64_t)tm_nblk() * TM_THREADS) st4(Penc + 4 * k, ld4(P0 + 4 * k));
+}
+
+// fp32 form: variant v's neighbour list for the fused forward's message kernel run on the rows [v T, (V + 1) T) of the table — a
+// visible neighbour keeps its row j of the variant's slot, an invisible one becomes row j + delta (delta = (V - v) T: slot V).
+__global__ __launch_bounds__(TM_THREADS) void variant_remap_kernel(const uint2 *__restrict__ vis, const int32_t *__restrict__ E_idx,
+                                                                   int T, int delta, int32_t *__restrict__ out) {
+    const int64_t n = (int64_t)T * TM_KS;
+    for (int64_t k = (int64_t)tm_bid() * TM_THREADS + tm_tid(); k < n; k += (int64_t)tm_nblk() * TM_THREADS) {
+        const int64_t i = k / TM_KS;
+        const int s = (int)(k - i * TM_KS), j = E_idx[k];
+        const uint2 wd = vis[i];
+        const unsigned bit = ((s < 32 ? wd.x : wd.y) >> (s & 31)) & 1u;
+        out[k] = j < 0 || bit ? j : j + delta;
     }
 }
 
@@ -192,12 +267,40 @@ int launch_variant_hidden(const float *const *h, int64_t T, int64_t V, float *ou
     return tm_check_launch("variant_hidden");
 }
 
+int launch_variant_vis(const int32_t *rank, const int32_t *E_idx, int64_t T, int64_t V, void *vis, hipStream_t st) {
+    const int64_t R = V * T;
+    tm_prof_begin("variant_vis", st);
+    variant_vis_kernel<<<rowwise_grid(R * 64), TM_THREADS, 0, st>>>(rank, E_idx, (int)T, R, (uint2 *)vis);
+    tm_prof_end(st);
+    return tm_check_launch("variant_vis");
+}
+
+int launch_variant_penc0(const float *P0, int64_t T, float *Penc, hipStream_t st) {
+    tm_prof_begin("variant_penc0", st);
+    variant_penc0_kernel<<<rowwise_grid(T * 64), TM_THREADS, 0, st>>>(P0, T, Penc);
+    tm_prof_end(st);
+    return tm_check_launch("variant_penc0");
+}
+
+// vis == nullptr: every neighbour visible, P [V T, 256] (tmpnn_decode_variants). Otherwise P [(V + 1) T, 256] with Penc_l in slot V,
+// (V + 1) T 256 < 2^32 (checked by the caller); remap [T,48]: scratch of the fp32 form.
 int launch_variant_msg(const float *W1e, int ld1, const float *W2, const float *b2, const float *P, const float *hE,
-                       const int32_t *E_idx, const float *mask, int64_t T, int64_t V, float *Ssum, float *cnt, hipStream_t st) {
+                       const int32_t *E_idx, const float *mask, int64_t T, int64_t V, float *Ssum, float *cnt, hipStream_t st,
+                       const void *vis, int32_t *remap) {
     const int mode = tm_matmul_mode();
     if (mode == TM_MM_FP32) {       // the fused forward's own kernel, variant after variant: its arithmetic exactly
         for (int64_t v = 0; v < V; ++v) {
-            const int rc = launch_msg(true, W1e, ld1, W2, b2, P + (size_t)v * T * 256, hE, E_idx, mask, T, Ssum + (size_t)v * T * TM_H,
+            const int32_t *list = E_idx;
+            if (vis) {              // (stream order keeps the one remapped list safe between the variants)
+                tm_prof_begin("variant_remap", st);
+                variant_remap_kernel<<<rowwise_grid(T * TM_KS), TM_THREADS, 0, st>>>((const uint2 *)vis + (size_t)v * T, E_idx, (int)T,
+                                                                                   (int)((V - v) * T), remap);
+                tm_prof_end(st);
+                const int rc = tm_check_launch("variant_remap");
+                if (rc != TMPNN_OK) return rc;
+                list = remap;
+            }
+            const int rc = launch_msg(true, W1e, ld1, W2, b2, P + (size_t)v * T * 256, hE, list, mask, T, Ssum + (size_t)v * T * TM_H,
                                       cnt + (size_t)v * T, st);
             if (rc != TMPNN_OK) return rc;
         }
@@ -205,7 +308,7 @@ int launch_variant_msg(const float *W1e, int ld1, const float *W2, const float *
     }
     const bool h2 = mode == TM_MM_F16X2;
     VarMsgArgs a{W1e, ld1, W2, b2, P, hE, E_idx, mask, Ssum, cnt, (int)T, (int)V, 0, 0, h2 ? tm_find_wimgp(W1e) : nullptr,
-                 h2 ? tm_find_wimgp(W2) : nullptr};
+                 h2 ? tm_find_wimgp(W2) : nullptr, (const uint2 *)vis, (unsigned)((uint64_t)V * (uint64_t)T * 256u)};
     if (h2 && !(a.imgp1 && a.imgp2))
         return tm_set_error(TMPNN_E_INVALID, "variant_msg: f16x2 handle without the K-permuted fragment images of W1e / W2");
     // Variants per workgroup: all of them once the residues alone fill the chip four times over; below that the variant axis is cut
@@ -216,6 +319,13 @@ int launch_variant_msg(const float *W1e, int ld1, const float *W2, const float *
     a.VC = (int)vc;
     a.n_chunks = (int)((V + vc - 1) / vc);
     const int grid = (int)(T * a.n_chunks);
+    if (vis) {
+        tm_prof_begin("dec_msg_ordered", st);
+        if (h2) var_msg8_kernel<SplitH2, true><<<grid, 512, 0, st>>>(a);
+        else var_msg8_kernel<SplitBF3, true><<<grid, 512, 0, st>>>(a);
+        tm_prof_end(st);
+        return tm_check_launch("dec_msg_ordered");
+    }
     tm_prof_begin("dec_msg_variants", st);
     if (h2) var_msg8_kernel<SplitH2><<<grid, 512, 0, st>>>(a);
     else var_msg8_kernel<SplitBF3><<<grid, 512, 0, st>>>(a);

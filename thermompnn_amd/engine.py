@@ -375,14 +375,32 @@ class Engine:
         own residue S_variants[v,t]. V is decoded in chunks of at most ``max_rows`` rows (V * T; default 2**18) — a variant's
         result does not depend on the chunking. Status handling as ``ssm_forward``: a non-finite result of an f16x2 decode
         re-encodes the backbone and reruns everything at ``retry_precision`` with a warning, or raises TmpnnRangeError."""
+        return self._decode("decode_variants", enc, S_variants, None, want_ddg, want_hidden, want_log_probs, max_rows, check_status)
+
+    def decode_ordered(self, enc: "EncodedBackbone", S_variants, ranks, want_ddg: bool = False, want_hidden: bool = False,
+                       want_log_probs: bool = True, max_rows: Optional[int] = None, check_status: bool = True):
+        """``decode_variants`` under a decoding order per variant (tmpnn_decode_ordered, ProteinMPNN's masked decoder): ``ranks``
+        [V,T] int32, residue i of variant v sees the identity and decoder state of neighbour j when ranks[v,j] < ranks[v,i] and
+        only its encoder state otherwise (equal ranks: not visible; all equal: the structure-only distribution). Same dict,
+        chunking and range contract as ``decode_variants``."""
+        R = self._i32(ranks)
+        if R.dim() != 2 or R.shape[1] != enc.T:
+            raise TmpnnError(f"decode_ordered: ranks must be [V, {enc.T}], got {tuple(R.shape)}")
+        return self._decode("decode_ordered", enc, S_variants, R, want_ddg, want_hidden, want_log_probs, max_rows, check_status)
+
+    def _decode(self, what: str, enc: "EncodedBackbone", S_variants, R: Optional[torch.Tensor], want_ddg: bool, want_hidden: bool,
+                want_log_probs: bool, max_rows: Optional[int], check_status: bool):
+        """The body of decode_variants (R is None) and decode_ordered (R = ranks [V,T])."""
         if not (want_ddg or want_hidden or want_log_probs):
-            raise TmpnnError("decode_variants: no output requested")
+            raise TmpnnError(f"{what}: no output requested")
         S = self._i32(S_variants)
         T = enc.T
         if S.dim() != 2 or S.shape[1] != T:
-            raise TmpnnError(f"decode_variants: S_variants must be [V, {T}], got {tuple(S.shape)}")
+            raise TmpnnError(f"{what}: S_variants must be [V, {T}], got {tuple(S.shape)}")
+        if R is not None and R.shape != S.shape:
+            raise TmpnnError(f"{what}: ranks {tuple(R.shape)} and S_variants {tuple(S.shape)} differ in shape")
         if S.numel() and (int(S.min()) < 0 or int(S.max()) >= VOCAB):
-            raise TmpnnError(f"decode_variants: residue indices must lie in [0, {VOCAB})")
+            raise TmpnnError(f"{what}: residue indices must lie in [0, {VOCAB})")
         V, dev = S.shape[0], self.device
         res = {}
         if want_ddg:
@@ -396,17 +414,23 @@ class Engine:
         rows = int(max_rows) if max_rows is not None else 1 << 18
         per = max(1, rows // T)
         status = torch.zeros(1, dtype=torch.int32, device=dev)     # per call: OR of the chunks' words
+        sizer = self.lib.tmpnn_decode_variants_workspace_bytes if R is None else self.lib.tmpnn_decode_ordered_workspace_bytes
 
         def run(e: "EncodedBackbone") -> int:
             w = self.weights_for(e.precision)
-            ws = self._workspace(self.lib.tmpnn_decode_variants_workspace_bytes(T, min(per, V)))
+            ws = self._workspace(sizer(T, min(per, V)))
             status.zero_()
             for v0 in range(0, V, per):
                 v1 = min(V, v0 + per)
                 part = lambda k: _ptr(res[k][v0:v1]) if k in res else None
-                check(self.lib.tmpnn_decode_variants(w.handle, _ptr(e.ctx), e.ctx.numel(), _ptr(S[v0:v1]), v1 - v0, _ptr(e.mask), T,
-                                                     part("ddg"), part("hidden"), part("log_probs"), _ptr(self._status), _ptr(ws),
-                                                     ws.numel(), _stream()), "tmpnn_decode_variants")
+                if R is None:
+                    check(self.lib.tmpnn_decode_variants(w.handle, _ptr(e.ctx), e.ctx.numel(), _ptr(S[v0:v1]), v1 - v0, _ptr(e.mask), T,
+                                                         part("ddg"), part("hidden"), part("log_probs"), _ptr(self._status), _ptr(ws),
+                                                         ws.numel(), _stream()), "tmpnn_decode_variants")
+                else:
+                    check(self.lib.tmpnn_decode_ordered(w.handle, _ptr(e.ctx), e.ctx.numel(), _ptr(S[v0:v1]), _ptr(R[v0:v1]), v1 - v0,
+                                                        _ptr(e.mask), T, part("ddg"), part("hidden"), part("log_probs"),
+                                                        _ptr(self._status), _ptr(ws), ws.numel(), _stream()), "tmpnn_decode_ordered")
                 status.bitwise_or_(self._status)
             return int(status.item()) if check_status else 0
 
@@ -414,13 +438,13 @@ class Engine:
         if st & _lib.STATUS_RANGE:
             retry, used = self.retry_precision, enc.precision
             if used != "f16x2" or not retry or retry == used:
-                check(self.lib.tmpnn_status_error(st), f"tmpnn_decode_variants[{used}]")
+                check(self.lib.tmpnn_status_error(st), f"tmpnn_{what}[{used}]")
             warnings.warn(f"ThermoMPNN HIP engine: non-finite result in {used} (an operand left the fp16 range); "
-                          f"rerunning this batch at precision {retry}", RuntimeWarning, stacklevel=2)
+                          f"rerunning this batch at precision {retry}", RuntimeWarning, stacklevel=3)
             X, ridx, cenc, max_len = enc.inputs
             st = run(self.encode(X, enc.mask, ridx, cenc, enc.offsets, max_len=max_len, precision=retry))
         if st:
-            check(self.lib.tmpnn_status_error(st), "tmpnn_decode_variants")
+            check(self.lib.tmpnn_status_error(st), f"tmpnn_{what}")
         return res
 
     def capture_graph(self, X, S, mask, residue_idx, chain_enc, offsets, max_len: int, out: Optional[dict] = None, **want):

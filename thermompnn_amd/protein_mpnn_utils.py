@@ -3,6 +3,7 @@
 Same names, signatures and return conventions; the arithmetic runs in libtmpnn.so
 (hand-written HIP for gfx950) — this module only packs arguments. Out-of-scope symbols of the
 reference file (CA_ProteinFeatures, sample/tied_sample, StructureDataset*, loss_*) are not provided.
+``ProteinMPNN.conditional_probs`` / ``unconditional_probs`` (:1496-1587) are: the masked decoder runs in tmpnn_decode_ordered.
 """
 from __future__ import annotations
 
@@ -12,6 +13,15 @@ import torch.nn as nn
 from . import weights as _weights
 from .engine import Engine, cat_neighbors_nodes, gather_edges, gather_nodes  # noqa: F401  (API surface)
 from .pdb_io import alt_parse_PDB, featurize, tied_featurize  # noqa: F401  (API surface)
+
+
+def decoding_ranks(order_mask, randn) -> torch.Tensor:
+    """int32 ranks [..., L] for ``Engine.decode_ordered``: the inverse permutation of the reference's
+    ``decoding_order = argsort((order_mask + 0.0001) * abs(randn))`` (protein_mpnn_utils.py:1533), computed with that expression —
+    rank[..., p] is the step at which residue p is decoded, and a residue sees the neighbours of lower rank."""
+    order = torch.argsort((order_mask + 0.0001) * (torch.abs(randn)))
+    steps = torch.arange(order.shape[-1], device=order.device).expand_as(order)
+    return torch.empty_like(order).scatter_(-1, order, steps).to(torch.int32)
 
 
 def _register_tree(root: nn.Module, shapes) -> None:
@@ -96,3 +106,47 @@ class ProteinMPNN(_EngineOwner):
             h_S = eng.seq_embed(S.reshape(-1)).view(B, L, -1)
         hidden = res["hidden"].view(3, B, L, -1)
         return [hidden[2], hidden[1], hidden[0]], h_S, res["log_probs"].view(B, L, -1)
+
+    def _encode_padded(self, eng, X, mask, residue_idx, chain_encoding_all):
+        """The padded batch [B,L,...] as ``forward`` lays it out: B proteins of L rows each on the packed residue axis."""
+        B, L = X.shape[0], X.shape[1]
+        offsets = torch.arange(B + 1, dtype=torch.int32) * L
+        return eng.encode(X.reshape(B * L, 4, 3), mask.reshape(-1), residue_idx.reshape(-1), chain_encoding_all.reshape(-1),
+                          offsets, max_len=L)
+
+    def conditional_probs(self, X, S, mask, chain_M, residue_idx, chain_encoding_all, randn, backbone_only=False):
+        """-> log p(aa at idx | structure, every other residue) [B,L,21] for every idx with chain_M * mask == 1, rows of the other
+        positions exactly 0 (reference :1496-1555): one encode, then one full decode per looped position under the order that
+        puts that position last and the others in |randn| order — all of them variants of ONE ``decode_ordered`` call.
+        ``backbone_only=True`` puts the position first instead; its logits then only ever read encoder states of its neighbours,
+        so every looped row equals the all-invisible decode's (``unconditional_probs``): one decode, rows copied."""
+        B, L = X.shape[0], X.shape[1]
+        if B != 1:
+            raise NotImplementedError("conditional_probs: one structure per call (the reference takes the positions to loop over "
+                                      "from batch member 0 for every member)")
+        eng = self.engine()
+        out = torch.zeros((B, L, 21), dtype=torch.float32, device=eng.device)
+        idx = torch.nonzero((chain_M * mask)[0] == 1)[:, 0].to(eng.device)
+        if idx.numel() == 0:
+            return out
+        with torch.cuda.device(eng.device):
+            enc = self._encode_padded(eng, X, mask, residue_idx, chain_encoding_all)
+            if backbone_only:
+                lp = eng.decode_ordered(enc, torch.zeros((1, L), dtype=torch.int32), torch.zeros((1, L), dtype=torch.int32))["log_probs"]
+                out[0, idx] = lp[0, idx]
+            else:
+                order_mask = torch.zeros((idx.numel(), L), device=eng.device)
+                order_mask[torch.arange(idx.numel(), device=eng.device), idx] = 1.0
+                ranks = decoding_ranks(order_mask, randn.to(eng.device).reshape(1, L))
+                lp = eng.decode_ordered(enc, S.reshape(1, L).expand(idx.numel(), L), ranks)["log_probs"]
+                out[0, idx] = lp[torch.arange(idx.numel(), device=eng.device), idx]
+        return out
+
+    def unconditional_probs(self, X, mask, residue_idx, chain_encoding_all):
+        """-> log p(aa | structure alone) [B,L,21] (reference :1557-1587): the decode in which no residue sees another's identity."""
+        eng = self.engine()
+        B, L = X.shape[0], X.shape[1]
+        with torch.cuda.device(eng.device):
+            enc = self._encode_padded(eng, X, mask, residue_idx, chain_encoding_all)
+            zeros = torch.zeros((1, B * L), dtype=torch.int32)
+            return eng.decode_ordered(enc, zeros, zeros)["log_probs"].view(B, L, 21)

@@ -38,27 +38,40 @@ def compute_centrality(xyz, basis_atom: str = "CA", radius: float = 10.0, core_t
 
 
 class ProteinMPNNBaseline(_EngineOwner):
-    """ProteinMPNN as a ddG proxy: ddG = -log p(mutant aa | structure) (reference :38-65)."""
+    """ProteinMPNN as a ddG proxy: ddG = -log p(mutant aa | structure) (reference :38-65). ``scoring`` picks the p:
+    "visible" (the reference baseline's forward: every residue sees every neighbour's identity and, through its own state, its
+    own), "conditional" (ProteinMPNN.conditional_probs: structure + every OTHER residue; the order among the others is drawn
+    from a generator seeded with ``seed``) or "unconditional" (structure alone)."""
 
-    def __init__(self, cfg, version="v_48_020.pt"):
+    SCORINGS = ("visible", "conditional", "unconditional")
+
+    def __init__(self, cfg, version="v_48_020.pt", scoring="visible", seed=0):
         super().__init__()
+        if scoring not in self.SCORINGS:
+            raise ValueError(f"scoring={scoring!r}: expected one of {self.SCORINGS}")
+        self.scoring, self.seed = scoring, int(seed)
         self.prot_mpnn = get_protein_mpnn(cfg, version=version)
         self.k_neighbors = self.prot_mpnn.k_neighbors
+
+    def _log_probs(self, pdb) -> torch.Tensor:
+        device = next(self.parameters()).device
+        feats = tied_featurize([pdb], device, None, None, None, None, None, None, ca_only=False)
+        X, S, mask, chain_M, chain_enc, residue_idx = feats[0], feats[1], feats[2], feats[4], feats[5], feats[12]
+        if self.scoring == "conditional":
+            randn = torch.randn(chain_M.shape, generator=torch.Generator().manual_seed(self.seed)).to(device)
+            return self.prot_mpnn.conditional_probs(X, S, mask, chain_M, residue_idx, chain_enc, randn)
+        if self.scoring == "unconditional":
+            return self.prot_mpnn.unconditional_probs(X, mask, residue_idx, chain_enc)
+        *_, log_probs = self.prot_mpnn(X, S, mask, chain_M, residue_idx, chain_enc, None)
+        return log_probs
 
     def ssm_table(self, pdb) -> torch.Tensor:
         """[L, 21] on the model's device: entry [pos, a] = the ddG ``forward`` returns for a mutation to ALPHABET[a] at pos
         (= -log p), the whole scan from the one forward the reference also runs (:47-53)."""
-        device = next(self.parameters()).device
-        feats = tied_featurize([pdb[0] if isinstance(pdb, (list, tuple)) else pdb], device, None, None, None, None, None, None, ca_only=False)
-        X, S, mask, chain_M, chain_enc, residue_idx = feats[0], feats[1], feats[2], feats[4], feats[5], feats[12]
-        *_, log_probs = self.prot_mpnn(X, S, mask, chain_M, residue_idx, chain_enc, None)
-        return -log_probs[0]
+        return -self._log_probs(pdb[0] if isinstance(pdb, (list, tuple)) else pdb)[0]
 
     def forward(self, pdb, mutations, tied_feat=True):
-        device = next(self.parameters()).device
-        feats = tied_featurize([pdb[0]], device, None, None, None, None, None, None, ca_only=False)
-        X, S, mask, chain_M, chain_enc, residue_idx = feats[0], feats[1], feats[2], feats[4], feats[5], feats[12]
-        *_, log_probs = self.prot_mpnn(X, S, mask, chain_M, residue_idx, chain_enc, None)
+        log_probs = self._log_probs(pdb[0])
         live = [m for m in mutations if m is not None]
         if not live:
             return [None for _ in mutations], log_probs
