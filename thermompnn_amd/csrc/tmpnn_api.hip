@@ -5,7 +5,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <algorithm>
 #include <map>
 #include <new>
 #include <string>
@@ -121,35 +120,8 @@ static int default_mode() {                  // TMPNN_PRECISION, read once; an u
     static const int v = parse_mode(getenv("TMPNN_PRECISION"));
     return v;
 }
-static thread_local int g_mode = -1;         // mode of the API call in progress (TmModeScope), -1 = none
-static thread_local const tmpnn_weights *g_cur_w = nullptr;
-const tmpnn_weights *tm_cur_weights() { return g_cur_w; }
-const char *tm_find_wimg(const float *base) {       // wimg[] is sorted by base address at create time: binary search
-    const tmpnn_weights *w = g_cur_w;
-    if (!w || !base) return nullptr;
-    int lo = 0, hi = w->n_wimg;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (w->wimg[mid].base < base) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < w->n_wimg && w->wimg[lo].base == base ? w->wimg[lo].img : nullptr;
-}
-const char *tm_find_wimgp(const float *base) {
-    const tmpnn_weights *w = g_cur_w;
-    if (!w || !base) return nullptr;
-    for (int i = 0; i < w->n_wimgp; ++i)
-        if (w->wimgp[i].base == base) return w->wimgp[i].img;
-    return nullptr;
-}
-int tm_matmul_mode() {
-    if (g_mode >= 0) return g_mode;
-    const int d = default_mode();
-    return d < 0 ? (int)TM_MM_F16X2 : d;
-}
-TmModeScope::TmModeScope(const tmpnn_weights *w) : saved(g_mode), saved_w(g_cur_w) { g_mode = w->mode; g_cur_w = w; }
-TmModeScope::~TmModeScope() { g_mode = saved; g_cur_w = saved_w; }
-extern "C" const char *tmpnn_matmul_mode(void) { return mode_name(tm_matmul_mode()); }
+// the process default (a handle's own precision is tmpnn_weights_precision); an unknown TMPNN_PRECISION reads as f16x2 here
+extern "C" const char *tmpnn_matmul_mode(void) { return mode_name(default_mode() < 0 ? (int)TM_MM_F16X2 : default_mode()); }
 extern "C" const char *tmpnn_weights_precision(const tmpnn_weights_t *w) { return w ? mode_name(w->mode) : nullptr; }
 
 extern "C" int tmpnn_status_error(int32_t status) {
@@ -235,7 +207,7 @@ static const size_t POS_TABLE_FLOATS = 66 * TMPNN_HID, SEQ_TABLE_FLOATS = TMPNN_
                     CONV_CENTER_FLOATS = 384 * 384;
 static size_t packed_bytes_for(int mode) {    // the f16 fragment images exist for f16x2 handles only (nothing else reads them)
     return (POS_TABLE_FLOATS + 3 * SEQ_TABLE_FLOATS + CONV_CENTER_FLOATS) * sizeof(float) +
-           (mode == TM_MM_F16X2 ? (size_t)(TM_N_WIMG + TM_N_WIMGP) * TM_WIMG_BYTES : 0);
+           (mode == TM_MM_F16X2 ? (size_t)TM_N_IMG * TM_WIMG_BYTES : 0);
 }
 extern "C" size_t tmpnn_weights_packed_bytes(void) { return packed_bytes_for(TM_MM_F16X2); }   // upper bound over the precisions
 extern "C" size_t tmpnn_weights_packed_bytes_p(const char *precision) {
@@ -286,29 +258,33 @@ extern "C" int tmpnn_weights_create_p(tmpnn_weights_t **out, const float *const 
     w->We_w = get("W_e.weight");
     w->We_b = get("W_e.bias");
     w->Ws_w = get("W_s.weight");
+    auto node = [&](const std::string &p) {
+        return NodeW{get(p + "W3.weight"), get(p + "W3.bias"), get(p + "norm1.weight"), get(p + "norm1.bias"),
+                     get(p + "dense.W_in.weight"), get(p + "dense.W_in.bias"), get(p + "dense.W_out.weight"), get(p + "dense.W_out.bias"),
+                     get(p + "norm2.weight"), get(p + "norm2.bias"), {}};
+    };
+    // W [128, ld]: the h_i block is columns [0:128), the h_j block starts at column c_off
+    auto proj = [](const float *W, int ld, int c_off, const float *b) {
+        return NodeProj{ProjSpec{W, ld, b, W + c_off, ld, nullptr, nullptr, nullptr}, {}};
+    };
     for (int l = 0; l < 3; ++l) {
+        // encoder, W1 and W11 columns: [0:128) h_i | [128:256) e_ij | [256:384) h_j
         const std::string p = "encoder_layers." + std::to_string(l) + ".";
+        const float *W1 = get(p + "W1.weight"), *W11 = get(p + "W11.weight");
         EncW &e = w->enc[l];
-        e.norm1_w = get(p + "norm1.weight"); e.norm1_b = get(p + "norm1.bias");
-        e.norm2_w = get(p + "norm2.weight"); e.norm2_b = get(p + "norm2.bias");
-        e.norm3_w = get(p + "norm3.weight"); e.norm3_b = get(p + "norm3.bias");
-        e.W1 = get(p + "W1.weight"); e.b1 = get(p + "W1.bias");
-        e.W2 = get(p + "W2.weight"); e.b2 = get(p + "W2.bias");
-        e.W3 = get(p + "W3.weight"); e.b3 = get(p + "W3.bias");
-        e.W11 = get(p + "W11.weight"); e.b11 = get(p + "W11.bias");
-        e.W12 = get(p + "W12.weight"); e.b12 = get(p + "W12.bias");
-        e.W13 = get(p + "W13.weight"); e.b13 = get(p + "W13.bias");
-        e.Win = get(p + "dense.W_in.weight"); e.bin = get(p + "dense.W_in.bias");
-        e.Wout = get(p + "dense.W_out.weight"); e.bout = get(p + "dense.W_out.bias");
+        e.node = node(p);
+        e.msg = MsgW{W1 + 128, 384, get(p + "W2.weight"), get(p + "W2.bias"), false, {}};
+        e.edge = EdgeW{W11 + 128, get(p + "W12.weight"), get(p + "W12.bias"), get(p + "W13.weight"), get(p + "W13.bias"),
+                       get(p + "norm3.weight"), get(p + "norm3.bias"), {}};
+        e.msg_proj = proj(W1, 384, 256, get(p + "W1.bias"));
+        e.edge_proj = proj(W11, 384, 256, get(p + "W11.bias"));
+        // decoder, W1 columns: [0:128) h_i | [128:256) e_ij | [256:384) W_s[S_j] (folded into seq_table, added to the h_j term) | [384:512) h_j
         const std::string d = "decoder_layers." + std::to_string(l) + ".";
+        const float *D1 = get(d + "W1.weight");
         DecW &c = w->dec[l];
-        c.norm1_w = get(d + "norm1.weight"); c.norm1_b = get(d + "norm1.bias");
-        c.norm2_w = get(d + "norm2.weight"); c.norm2_b = get(d + "norm2.bias");
-        c.W1 = get(d + "W1.weight"); c.b1 = get(d + "W1.bias");
-        c.W2 = get(d + "W2.weight"); c.b2 = get(d + "W2.bias");
-        c.W3 = get(d + "W3.weight"); c.b3 = get(d + "W3.bias");
-        c.Win = get(d + "dense.W_in.weight"); c.bin = get(d + "dense.W_in.bias");
-        c.Wout = get(d + "dense.W_out.weight"); c.bout = get(d + "dense.W_out.bias");
+        c.node = node(d);
+        c.msg = MsgW{D1 + 128, 512, get(d + "W2.weight"), get(d + "W2.bias"), true, {}};
+        c.msg_proj = proj(D1, 512, 384, get(d + "W1.bias"));
     }
     w->Wout_w = get("W_out.weight");
     w->Wout_b = get("W_out.bias");
@@ -328,44 +304,40 @@ extern "C" int tmpnn_weights_create_p(tmpnn_weights_t **out, const float *const 
     for (int l = 0; l < 3; ++l) { w->seq_table[l] = p; p += SEQ_TABLE_FLOATS; }
     w->conv_center = p; p += CONV_CENTER_FLOATS;
     int rc = launch_prep_tables(w, (hipStream_t)stream);
-    if (mode == TM_MM_F16X2) {   // fragment images of every 128 x 128 block the f16x2 kernels multiply by (see WImg); no other mode reads them
-        char *img = (char *)p;
-        auto add = [&](const float *base, int ld, int n_rows = 128, int k_valid = 128, int k_wrap = 0) {
-            if (rc != TMPNN_OK || w->n_wimg >= TM_N_WIMG) return;
-            w->wimg[w->n_wimg++] = WImg{base, img};
-            rc = launch_prep_wimg(base, ld, img, (hipStream_t)stream, n_rows, k_valid, k_wrap);
+    if (mode == TM_MM_F16X2) {   // fragment images of every 128 x 128 block the f16x2 kernels multiply by (the image rule, tmpnn_internal.h)
+        char *img = (char *)p, *const img_end = img + (size_t)TM_N_IMG * TM_WIMG_BYTES;       // (inside `packed`: checked above)
+        auto image = [&](const float *base, int ld, int n_rows = 128, int k_valid = 128, int k_wrap = 0, bool perm = false) -> const char * {
+            if (rc != TMPNN_OK || img == img_end) return nullptr;
+            const char *at = img;
+            rc = launch_prep_wimg(base, ld, img, (hipStream_t)stream, n_rows, k_valid, k_wrap, perm);
             img += TM_WIMG_BYTES;
+            return at;
         };
+        auto node_images = [&](NodeW &n) {
+            n.img[0] = image(n.W3, 128);
+            for (int c = 0; c < 4; ++c) { n.img[1 + 2 * c] = image(n.Win + (size_t)128 * c * 128, 128); n.img[2 + 2 * c] = image(n.Wout + 128 * c, 512); }
+        };
+        auto proj_images = [&](NodeProj &np) { np.img = {image(np.spec.Wa, np.spec.lda), image(np.spec.Wc, np.spec.ldc)}; };
+        auto msg_images = [&](MsgW &m) { m.img.w1 = image(m.W1e, m.ld1); m.img.w2 = image(m.W2, 128); };
+        auto msg_images_kperm = [&](MsgW &m) { m.img.p1 = image(m.W1e, m.ld1, 128, 128, 0, true); m.img.p2 = image(m.W2, 128, 128, 128, 0, true); };
         // RBF columns 16..415 (K padded to 416 + 96), then — K positions 400..415 — the 16 positional columns 0..15 of the same rows
-        for (int b = 0; b < 4; ++b) add(w->edge_w + 16 + 128 * b, 416, 128, b < 3 ? 128 : 16, b < 3 ? 0 : 16);
-        add(w->We_w, 128);
+        for (int b = 0; b < 4; ++b) w->feat_img.edge[b] = image(w->edge_w + 16 + 128 * b, 416, 128, b < 3 ? 128 : 16, b < 3 ? 0 : 16);
+        w->feat_img.we = image(w->We_w, 128);
         if (n_tensors == TMPNN_N_TENSORS) {          // ddG head: centre tap (derived just above, on the same stream) + both_out.1
-            for (int u = 0; u < 9; ++u) add(w->conv_center + (size_t)128 * (u / 3) * 384 + 128 * (u % 3), 384);
-            for (int u = 0; u < 3; ++u) add(w->mlp_w[0] + 128 * u, 384, 64);
+            for (int u = 0; u < 9; ++u) w->head_img.unit[u] = image(w->conv_center + (size_t)128 * (u / 3) * 384 + 128 * (u % 3), 384);
+            for (int u = 0; u < 3; ++u) w->head_img.unit[9 + u] = image(w->mlp_w[0] + 128 * u, 384, 64);
         }
         for (int l = 0; l < 3; ++l) {
-            const EncW &e = w->enc[l];
-            add(e.W3, 128);
-            for (int c = 0; c < 4; ++c) { add(e.Win + (size_t)128 * c * 128, 128); add(e.Wout + 128 * c, 512); }
-            add(e.W1, 384); add(e.W1 + 256, 384); add(e.W11, 384); add(e.W11 + 256, 384);
-            add(e.W1 + 128, 384); add(e.W2, 128); add(e.W11 + 128, 384); add(e.W12, 128); add(e.W13, 128);   // per-edge kernels
-            const DecW &d = w->dec[l];
-            add(d.W3, 128);
-            for (int c = 0; c < 4; ++c) { add(d.Win + (size_t)128 * c * 128, 128); add(d.Wout + 128 * c, 512); }
-            add(d.W1, 512); add(d.W1 + 384, 512);
-            add(d.W1 + 128, 512); add(d.W2, 128);
+            EncW &e = w->enc[l];
+            node_images(e.node); proj_images(e.msg_proj); proj_images(e.edge_proj); msg_images(e.msg);
+            e.edge.img = {image(e.edge.W11e, 384), image(e.edge.W12, 128), image(e.edge.W13, 128)};
+            DecW &d = w->dec[l];
+            node_images(d.node); proj_images(d.msg_proj); msg_images(d.msg);
         }
-        std::sort(w->wimg, w->wimg + w->n_wimg, [](const WImg &x, const WImg &y) { return x.base < y.base; });   // tm_find_wimg searches it
-        auto addp = [&](const float *base, int ld) {     // K-permuted images (msg8_wave_kernel)
-            if (rc != TMPNN_OK || w->n_wimgp >= TM_N_WIMGP) return;
-            w->wimgp[w->n_wimgp++] = WImg{base, img};
-            rc = launch_prep_wimg(base, ld, img, (hipStream_t)stream, 128, 128, 0, true);
-            img += TM_WIMG_BYTES;
-        };
-        for (int l = 0; l < 3; ++l) {
-            addp(w->enc[l].W1 + 128, 384); addp(w->enc[l].W2, 128);
-            addp(w->dec[l].W1 + 128, 512); addp(w->dec[l].W2, 128);
-        }
+        for (int l = 0; l < 3; ++l) { msg_images_kperm(w->enc[l].msg); msg_images_kperm(w->dec[l].msg); }   // (behind the others: the order of the packed buffer is kept)
+        // every image member above is filled exactly once: the count the structs declare is the count built
+        const int n_built = (int)((img - (char *)p) / TM_WIMG_BYTES), n_want = TM_N_IMG - (n_tensors == TMPNN_N_TENSORS ? 0 : TM_N_HEAD_IMG);
+        if (rc == TMPNN_OK && n_built != n_want) rc = tm_set_error(TMPNN_E_INVALID, "weights_create: built %d fragment images, expected %d", n_built, n_want);
     }
     if (rc != TMPNN_OK) { delete w; return rc; }
     *out = w;
@@ -417,47 +389,50 @@ static int carve_layer_ws(void *workspace, size_t bytes, int64_t T, LayerWs *ws,
 }
 
 // Which node projection the NEXT consumer of h_V needs (fused into node_update): encoder layer l+1's message
-// pass, or decoder layer 0's after the last encoder layer; decoder layer l+1's after decoder layer l.
-static NodeProj enc_msg_proj(const tmpnn_weights *w, int l, float *P) {
-    const EncW &e = w->enc[l];
-    return NodeProj{e.W1, 384, e.b1, e.W1 + 256, 384, P, nullptr, nullptr};
-}
-static NodeProj dec_msg_proj(const tmpnn_weights *w, int l, float *P, const int32_t *S) {
-    // W1 columns: [0:128) h_i | [128:256) e_ij | [256:384) W_s[S_j] (folded into seq_table, added to the h_j term) | [384:512) h_j
-    const DecW &d = w->dec[l];
-    return NodeProj{d.W1, 512, d.b1, d.W1 + 384, 512, P, w->seq_table[l], S};
+// pass, or decoder layer 0's after the last encoder layer; decoder layer l+1's after decoder layer l. The handle holds the
+// weights and images of each; the destination (and the decoder's sequence term) is the call's.
+static NodeProj proj_into(NodeProj np, float *P) { np.spec.P = P; return np; }
+static NodeProj enc_msg_proj(const tmpnn_weights *w, int l, float *P) { return proj_into(w->enc[l].msg_proj, P); }
+static NodeProj enc_edge_proj(const tmpnn_weights *w, int l, float *P) { return proj_into(w->enc[l].edge_proj, P); }
+static NodeProj dec_msg_proj(const tmpnn_weights *w, int l, float *P, const int32_t *S) {   // S == nullptr: without the sequence term
+    NodeProj np = proj_into(w->dec[l].msg_proj, P);
+    if (S) { np.spec.add_tab = w->seq_table[l]; np.spec.add_idx = S; }
+    return np;
 }
 
-// have_P: ws.P already holds this layer's message projection (written by the previous node_update)
+// One encoder layer (EncLayer :819-838): message pass, node update, edge update with the NEW node states.
+// have_P:   ws.P already holds this layer's message projection (written by the previous node update);
+// have_msg: ws.Ssum / ws.cnt already hold this layer's message sums (the previous layer's edge update ran them in its launch);
+// next:     the node update also writes this projection of the new state (besides the edge update's, into ws.P2);
+// then:     small launches — the message pass that follows (over ws.P, which `next` must fill) runs inside the edge update's launch.
 static int run_enc_layer(const tmpnn_weights *w, int l, float *hV, float *hE, const int32_t *E_idx, const float *mask,
-                         int64_t T, const LayerWs &ws, bool have_P, const NodeProj *next, hipStream_t st) {
+                         int64_t T, const LayerWs &ws, bool have_P, bool have_msg, const NodeProj *next, const MsgW *then,
+                         hipStream_t st) {
     const EncW &e = w->enc[l];
     if (!have_P) {
         const NodeProj mp = enc_msg_proj(w, l, ws.P);
         TRY(launch_node_proj(hV, mp, T, st));
     }
-    // message + node update (EncLayer :819-832); the update also projects the NEW state for the edge update
-    TRY(launch_msg(false, e.W1 + 128, 384, e.W2, e.b2, ws.P, hE, E_idx, mask, T, ws.Ssum, ws.cnt, st));
-    const NodeProj ep{e.W11, 384, e.b11, e.W11 + 256, 384, ws.P2, nullptr, nullptr};
-    TRY(launch_node_update(e.W3, e.b3, e.norm1_w, e.norm1_b, e.Win, e.bin, e.Wout, e.bout, e.norm2_w, e.norm2_b, hV,
-                           ws.Ssum, ws.cnt, mask, T, hV, &ep, next, st));
-    // edge update with the NEW node states (:834-838)
-    TRY(launch_enc_edge(e, ws.P2, hE, E_idx, T, st));
-    return TMPNN_OK;
+    if (!have_msg) TRY(launch_msg(w->mode, e.msg, ws.P, hE, E_idx, mask, T, ws.Ssum, ws.cnt, st));
+    const NodeProj ep = enc_edge_proj(w, l, ws.P2);
+    TRY(launch_node_update(w->mode, e.node, hV, ws.Ssum, ws.cnt, mask, T, hV, &ep, next, st));
+    if (then) return launch_edge_msg_fused(e.edge, ws.P2, hE, E_idx, *then, ws.P, mask, T, ws.Ssum, ws.cnt, st);
+    return launch_enc_edge(w->mode, e.edge, ws.P2, hE, E_idx, T, st);
 }
 
+// One decoder layer; have_P, have_msg and next as above. head: the ddG head of the same rows may ride in the node update's launch
+// (launch_node_update; the caller asked node_head_fusable).
 static int run_dec_layer(const tmpnn_weights *w, int l, const float *hV_in, float *hV_out, const float *hE,
                          const int32_t *E_idx, const int32_t *S, const float *mask, int64_t T, const LayerWs &ws,
-                         bool have_P, const NodeProj *next, hipStream_t st) {
+                         bool have_P, bool have_msg, const NodeProj *next, hipStream_t st, const HeadArgs *head = nullptr,
+                         bool *head_ran = nullptr) {
     const DecW &d = w->dec[l];
     if (!have_P) {
         const NodeProj mp = dec_msg_proj(w, l, ws.P, S);
         TRY(launch_node_proj(hV_in, mp, T, st));
     }
-    TRY(launch_msg(true, d.W1 + 128, 512, d.W2, d.b2, ws.P, hE, E_idx, mask, T, ws.Ssum, ws.cnt, st));
-    TRY(launch_node_update(d.W3, d.b3, d.norm1_w, d.norm1_b, d.Win, d.bin, d.Wout, d.bout, d.norm2_w, d.norm2_b, hV_in,
-                           ws.Ssum, ws.cnt, mask, T, hV_out, next, nullptr, st));
-    return TMPNN_OK;
+    if (!have_msg) TRY(launch_msg(w->mode, d.msg, ws.P, hE, E_idx, mask, T, ws.Ssum, ws.cnt, st));
+    return launch_node_update(w->mode, d.node, hV_in, ws.Ssum, ws.cnt, mask, T, hV_out, next, nullptr, st, head, head_ran);
 }
 
 // k-NN graph, edge features and the three encoder layers of a ragged batch: the part of a forward that never reads the sequence.
@@ -473,44 +448,24 @@ static int run_encoder(const tmpnn_weights *w, const float *X, const float *mask
                        float *D_nb, float *hE, float *hV, const int32_t *S, float *P_dec0, int32_t *status_opt, bool *dec_msg0_done,
                        hipStream_t st) {
     static const bool fuse_small = TM_DBG_FLAG("TMPNN_FUSE_SMALL", true);     // (A/B switch in the debug library only)
-    *dec_msg0_done = false;
-    const DecW &d0 = w->dec[0];
-    const NodeProj dec0{d0.W1, 512, d0.b1, d0.W1 + 384, 512, P_dec0, S ? w->seq_table[0] : nullptr, S};
-    const KnnInit kinit{hV, ws.P, w->enc[0].b1, status_opt};
-    if (fuse_small && max_len <= 256 && featurize_fusable(tm_matmul_mode(), T)) {             // one tile per workgroup: k-NN inside the featurizer launch
+    const KnnInit kinit{hV, ws.P, w->enc[0].msg_proj.spec.ba, status_opt};
+    if (fuse_small && max_len <= 256 && featurize_fusable(w->mode, T)) {             // one tile per workgroup: k-NN inside the featurizer launch
         const KnnFuse kf{mask, offsets, n_proteins, max_len, K, E_idx, D_nb, kinit};
         TRY(launch_featurize(w, X, residue_idx, chain_enc, E_idx, D_nb, T, hE, nullptr, st, &kf));
     } else {
         TRY(launch_knn(X, mask, offsets, n_proteins, T, max_len, K, E_idx, D_nb, nullptr, st, kinit));
         TRY(launch_featurize(w, X, residue_idx, chain_enc, E_idx, D_nb, T, hE, nullptr, st));
     }
-    if (fuse_small && edge_msg_fusable(tm_matmul_mode(), T)) {
-        // One tile per workgroup (a single protein, a few short ones): the edge update of encoder layer l and the message pass of
-        // the layer after it are ONE launch (edge_msg_fused_kernel: no grid-wide dependency between them; 16 launches instead
-        // of 19, bit-identical results). Launch order: msg0, node0, [edge0 + msg1], node1, [edge1 + msg2], node2,
-        // [edge2 + dec msg0], dnode0, dmsg1, dnode1, dmsg2, dnode2.
-        for (int l = 0; l < 3; ++l) {
-            const EncW &e = w->enc[l];
-            if (l == 0) TRY(launch_msg(false, e.W1 + 128, 384, e.W2, e.b2, ws.P, hE, E_idx, mask, T, ws.Ssum, ws.cnt, st));
-            const NodeProj next = l < 2 ? enc_msg_proj(w, l + 1, ws.P) : dec0;
-            const NodeProj ep{e.W11, 384, e.b11, e.W11 + 256, 384, ws.P2, nullptr, nullptr};
-            TRY(launch_node_update(e.W3, e.b3, e.norm1_w, e.norm1_b, e.Win, e.bin, e.Wout, e.bout, e.norm2_w, e.norm2_b, hV,
-                                   ws.Ssum, ws.cnt, mask, T, hV, &ep, &next, st));
-            if (l < 2) {
-                const EncW &n = w->enc[l + 1];
-                TRY(launch_edge_msg_fused(e, ws.P2, hE, E_idx, false, n.W1 + 128, 384, n.W2, n.b2, ws.P, mask, T, ws.Ssum, ws.cnt, st));
-            } else if (S) {
-                TRY(launch_edge_msg_fused(e, ws.P2, hE, E_idx, true, d0.W1 + 128, 512, d0.W2, d0.b2, ws.P, mask, T, ws.Ssum, ws.cnt, st));
-                *dec_msg0_done = true;
-            } else {
-                TRY(launch_enc_edge(e, ws.P2, hE, E_idx, T, st));
-            }
-        }
-    } else {
-        for (int l = 0; l < 3; ++l) {
-            const NodeProj next = l < 2 ? enc_msg_proj(w, l + 1, ws.P) : dec0;
-            TRY(run_enc_layer(w, l, hV, hE, E_idx, mask, T, ws, true, &next, st));
-        }
+    // One tile per workgroup (a single protein, a few short ones): the edge update of encoder layer l and the message pass of
+    // the layer after it are ONE launch (edge_msg_fused_kernel: no grid-wide dependency between them; 16 launches instead
+    // of 19, bit-identical results). Launch order: msg0, node0, [edge0 + msg1], node1, [edge1 + msg2], node2,
+    // [edge2 + dec msg0], dnode0, dmsg1, dnode1, dmsg2, dnode2. Larger launches: msg, node, edge per layer.
+    const bool fused = fuse_small && edge_msg_fusable(w->mode, T);
+    *dec_msg0_done = fused && S;
+    for (int l = 0; l < 3; ++l) {
+        const NodeProj next = l < 2 ? enc_msg_proj(w, l + 1, ws.P) : dec_msg_proj(w, 0, P_dec0, S);
+        const MsgW *then = !fused ? nullptr : l < 2 ? &w->enc[l + 1].msg : S ? &w->dec[0].msg : nullptr;
+        TRY(run_enc_layer(w, l, hV, hE, E_idx, mask, T, ws, true, fused && l > 0, &next, then, st));
     }
     return TMPNN_OK;
 }
@@ -541,7 +496,6 @@ extern "C" int tmpnn_edge_featurize(const tmpnn_weights_t *w, const float *X, co
     REQUIRE(w && X && residue_idx && chain_enc && E_idx && D_nb && h_E, "edge_featurize: null pointer");
     REQUIRE(T >= 0 && T <= T_MAX, "edge_featurize: bad T");
     if (T == 0) return TMPNN_OK;
-    const TmModeScope scope(w);
     return launch_featurize(w, X, residue_idx, chain_enc, E_idx, D_nb, T, h_E, E_opt, (hipStream_t)stream);
 }
 
@@ -576,10 +530,9 @@ extern "C" int tmpnn_enc_layer(const tmpnn_weights_t *w, int layer, float *h_V, 
     REQUIRE(layer >= 0 && layer < 3, "enc_layer: layer %d outside [0,3)", layer);
     REQUIRE(T >= 0 && T <= T_MAX, "enc_layer: bad T");
     if (T == 0) return TMPNN_OK;
-    const TmModeScope scope(w);
     LayerWs ws;
     TRY(carve_layer_ws(workspace, workspace_bytes, T, &ws));
-    return run_enc_layer(w, layer, h_V, h_E, E_idx, mask, T, ws, false, nullptr, (hipStream_t)stream);
+    return run_enc_layer(w, layer, h_V, h_E, E_idx, mask, T, ws, false, false, nullptr, nullptr, (hipStream_t)stream);
 }
 
 // measurement hook (tools/gemm_probe.py): one [48x128] x [128x128]^T GEMM per tile, mode 0 = fp32 MFMA, 1 = bf16x3 six-term, 2 = f16x2 three-term
@@ -625,10 +578,9 @@ extern "C" int tmpnn_dec_layer(const tmpnn_weights_t *w, int layer, const float 
     REQUIRE(layer >= 0 && layer < 3, "dec_layer: layer %d outside [0,3)", layer);
     REQUIRE(T >= 0 && T <= T_MAX, "dec_layer: bad T");
     if (T == 0) return TMPNN_OK;
-    const TmModeScope scope(w);
     LayerWs ws;
     TRY(carve_layer_ws(workspace, workspace_bytes, T, &ws));
-    return run_dec_layer(w, layer, h_V_in, h_V_out, h_E, E_idx, S, mask, T, ws, false, nullptr, (hipStream_t)stream);
+    return run_dec_layer(w, layer, h_V_in, h_V_out, h_E, E_idx, S, mask, T, ws, false, false, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int tmpnn_seq_embed(const tmpnn_weights_t *w, const int32_t *S, int64_t T, float *h_S, tmpnn_stream_t stream) {
@@ -649,7 +601,6 @@ extern "C" int tmpnn_ddg_head(const tmpnn_weights_t *w, const float *hV_last, co
     REQUIRE(w && hV_last && hV_prev && S && ddg && T >= 0 && T <= T_MAX, "ddg_head: bad argument");
     REQUIRE(w->n_tensors == TMPNN_N_TENSORS, "ddg_head: weight handle was created without the TransferModel head tensors");
     if (T == 0) return TMPNN_OK;
-    const TmModeScope scope(w);
     return launch_head(w, hV_last, hV_prev, S, T, ddg, z_opt, status_opt, (hipStream_t)stream);
 }
 
@@ -705,7 +656,6 @@ extern "C" int tmpnn_ssm_forward(const tmpnn_weights_t *w, const float *X, const
     REQUIRE(max_len >= 1, "ssm_forward: max_len must be >= 1 (the longest protein of the batch)");
     if (max_len > 8192) return tm_set_error(TMPNN_E_UNSUPPORTED, "ssm_forward: max_len %d > 8192", max_len);
     hipStream_t st = (hipStream_t)stream;
-    const TmModeScope scope(w);
     // (status_opt: the k-NN kernel zeroes the word, and the LAST kernel flags what the k-NN kernel found, see KnnInit / HeadArgs)
 
     LayerWs ws;
@@ -725,24 +675,14 @@ extern "C" int tmpnn_ssm_forward(const tmpnn_weights_t *w, const float *X, const
     bool head_done = false;          // the ddG head ran inside the last node update's launch
     TRY(run_encoder(w, X, mask, residue_idx, chain_enc, offsets, n_proteins, T, max_len, K, ws, E_idx, D_nb, hE, hV[0], S, ws.P,
                     status_opt, &dec_msg0_done, st));
-    if (dec_msg0_done) {
-        for (int l = 0; l < 3; ++l) {
-            const DecW &d = w->dec[l];
-            if (l > 0) TRY(launch_msg(true, d.W1 + 128, 512, d.W2, d.b2, ws.P, hE, E_idx, mask, T, ws.Ssum, ws.cnt, st));
-            const NodeProj next = dec_msg_proj(w, l < 2 ? l + 1 : 2, ws.P, S);
-            // last layer: its node update and the ddG head of the same 16 residues are ONE launch (node_head_fused_kernel, bit-identical)
-            HeadArgs ha;
-            const bool with_head = l == 2 && ddg && node_head_fusable(tm_matmul_mode(), T);
-            if (with_head) TRY(tm_head_args(ha, w, hV[3], hV[2], S, T, ddg, nullptr, status_opt, E_idx));
-            TRY(launch_node_update(d.W3, d.b3, d.norm1_w, d.norm1_b, d.Win, d.bin, d.Wout, d.bout, d.norm2_w, d.norm2_b, hV[l],
-                                   ws.Ssum, ws.cnt, mask, T, hV[l + 1], l < 2 ? &next : nullptr, nullptr, st, with_head ? &ha : nullptr,
-                                   with_head ? &head_done : nullptr));
-        }
-    } else {
-        for (int l = 0; l < 3; ++l) {
-            const NodeProj next = dec_msg_proj(w, l < 2 ? l + 1 : 2, ws.P, S);
-            TRY(run_dec_layer(w, l, hV[l], hV[l + 1], hE, E_idx, S, mask, T, ws, true, l < 2 ? &next : nullptr, st));
-        }
+    for (int l = 0; l < 3; ++l) {
+        const NodeProj next = dec_msg_proj(w, l < 2 ? l + 1 : 2, ws.P, S);
+        // last layer of a small launch: its node update and the ddG head of the same 16 residues are ONE launch (node_head_fused_kernel, bit-identical)
+        HeadArgs ha;
+        const bool with_head = dec_msg0_done && l == 2 && ddg && node_head_fusable(w->mode, T);
+        if (with_head) TRY(tm_head_args(ha, w, hV[3], hV[2], S, T, ddg, nullptr, status_opt, E_idx));
+        TRY(run_dec_layer(w, l, hV[l], hV[l + 1], hE, E_idx, S, mask, T, ws, true, dec_msg0_done && l == 0, l < 2 ? &next : nullptr, st,
+                          with_head ? &ha : nullptr, with_head ? &head_done : nullptr));
     }
     if (ddg && !head_done) TRY(launch_head(w, hV[3], hV[2], S, T, ddg, nullptr, status_opt, st, E_idx));
     if (log_probs_opt) TRY(launch_log_probs(w, hV[3], T, log_probs_opt, status_opt, st, ddg ? nullptr : E_idx));
@@ -803,60 +743,12 @@ extern "C" int tmpnn_encode(const tmpnn_weights_t *w, const float *X, const floa
     if (!D_nb)
         return tm_set_error(TMPNN_E_WORKSPACE, "encode: workspace %zu < %zu bytes", workspace_bytes, tmpnn_encode_workspace_bytes(T));
     hipStream_t st = (hipStream_t)stream;
-    const TmModeScope scope(w);
     bool unused = false;
     TRY(run_encoder(w, X, mask, residue_idx, chain_enc, offsets, n_proteins, T, max_len, K, ws, c.E_idx, D_nb, c.hE, c.hV, nullptr,
                     c.P0, status_opt, &unused, st));
     // the encoder state is this call's output: a value that left the f16x2 range upstream has reached it, and rows of an over-long
     // protein have an empty neighbour list (the MAXLEN probe of the fused forward's last kernel)
     return launch_range_check(c.hV, T * TMPNN_HID, status_opt, st, c.E_idx, T);
-}
-
-extern "C" int tmpnn_decode_variants(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const int32_t *S_var, int64_t V,
-                                     const float *mask, int64_t T, float *ddg, float *hidden_opt, float *log_probs_opt,
-                                     int32_t *status_opt, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream) {
-    REQUIRE(w, "decode_variants: null weight handle");
-    REQUIRE(T >= 0 && T <= T_MAX && V >= 0, "decode_variants: bad sizes (T=%lld, V=%lld)", (long long)T, (long long)V);
-    REQUIRE(!ddg || w->n_tensors == TMPNN_N_TENSORS, "decode_variants: ddg requested but the handle has no head tensors");
-    if (T == 0 || V == 0) return TMPNN_OK;            // nothing to decode (pointers may be null)
-    if (T > T_MAX / V)
-        return tm_set_error(TMPNN_E_UNSUPPORTED, "decode_variants: V * T = %lld * %lld rows exceed %lld (decode the variants in chunks)",
-                            (long long)V, (long long)T, (long long)T_MAX);
-    REQUIRE(S_var && mask, "decode_variants: null input pointer");
-    REQUIRE(ddg || hidden_opt || log_probs_opt, "decode_variants: no output requested");
-    EncCtx c;
-    TRY(carve_ctx("decode_variants", const_cast<void *>(ctx), ctx_bytes, T, &c));
-    const int64_t R = V * T;
-    const size_t need = tmpnn_decode_variants_workspace_bytes(T, V);
-    uintptr_t base = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    if (!workspace || workspace_bytes < need)
-        return tm_set_error(TMPNN_E_WORKSPACE, "decode_variants: workspace %zu < %zu bytes", workspace_bytes, need);
-    Carver cv{(char *)base, workspace_bytes - (base - (uintptr_t)workspace)};
-    float *P = (float *)cv.take((size_t)R * 256 * 4);
-    float *Ssum = (float *)cv.take((size_t)R * TMPNN_HID * 4);
-    float *cnt = (float *)cv.take((size_t)R * 4);
-    float *mask_rep = (float *)cv.take((size_t)R * 4);
-    float *hV[4];
-    for (int i = 0; i < 4; ++i) hV[i] = (float *)cv.take((size_t)R * TMPNN_HID * 4);
-    if (!P || !Ssum || !cnt || !mask_rep || !hV[3])
-        return tm_set_error(TMPNN_E_WORKSPACE, "decode_variants: workspace %zu < %zu bytes", workspace_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    const TmModeScope scope(w);
-    // rows r = v T + t. The row-wise kernels (node update + the next layer's projection, head, log-probabilities) run over all V T
-    // rows as they run over a ragged batch; the message pass shares the backbone's h_E tile between the variants of a workgroup.
-    TRY(launch_variant_expand(c.hV, c.P0, mask, w->seq_table[0], S_var, T, V, hV[0], P, mask_rep, status_opt, st));
-    for (int l = 0; l < 3; ++l) {
-        const DecW &d = w->dec[l];
-        TRY(launch_variant_msg(d.W1 + 128, 512, d.W2, d.b2, P, c.hE, c.E_idx, mask, T, V, Ssum, cnt, st));
-        const NodeProj next = dec_msg_proj(w, l < 2 ? l + 1 : 2, P, S_var);
-        TRY(launch_node_update(d.W3, d.b3, d.norm1_w, d.norm1_b, d.Win, d.bin, d.Wout, d.bout, d.norm2_w, d.norm2_b, hV[l], Ssum, cnt,
-                               mask_rep, R, hV[l + 1], l < 2 ? &next : nullptr, nullptr, st));
-    }
-    if (ddg) TRY(launch_head(w, hV[3], hV[2], S_var, R, ddg, nullptr, status_opt, st));
-    if (log_probs_opt) TRY(launch_log_probs(w, hV[3], R, log_probs_opt, status_opt, st));
-    if (!ddg && !log_probs_opt) TRY(launch_range_check(hV[3], R * TMPNN_HID, status_opt, st));
-    if (hidden_opt) TRY(launch_variant_hidden(hV + 1, T, V, hidden_opt, st));
-    return TMPNN_OK;
 }
 
 // ---- order-masked decoding over one encoded backbone --------------------------------------------------
@@ -870,57 +762,57 @@ extern "C" size_t tmpnn_decode_ordered_workspace_bytes(int64_t T, int64_t V) {
            align256((size_t)T * TMPNN_KS * 4) + 256;
 }
 
-extern "C" int tmpnn_decode_ordered(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const int32_t *S_var,
-                                    const int32_t *rank, int64_t V, const float *mask, int64_t T, float *ddg, float *hidden_opt,
-                                    float *log_probs_opt, int32_t *status_opt, void *workspace, size_t workspace_bytes,
-                                    tmpnn_stream_t stream) {
-    REQUIRE(w, "decode_ordered: null weight handle");
-    REQUIRE(T >= 0 && T <= T_MAX && V >= 0, "decode_ordered: bad sizes (T=%lld, V=%lld)", (long long)T, (long long)V);
-    REQUIRE(!ddg || w->n_tensors == TMPNN_N_TENSORS, "decode_ordered: ddg requested but the handle has no head tensors");
+// The body of tmpnn_decode_variants (ordered == false, rank unused) and tmpnn_decode_ordered (`what` names the entry in messages).
+// Rows r = v T + t. The row-wise kernels (node update + the next layer's projection, head, log-probabilities) run over all V T rows
+// as they run over a ragged batch; the message pass shares the backbone's h_E tile between the variants of a workgroup. Ordered: the
+// message pass of every layer picks each neighbour's row by rank — the variant's own projection (this layer's state + sequence term)
+// for a neighbour decoded earlier, Penc_l (the encoder state's projection, no sequence) for the others.
+static int decode_rows(const char *what, bool ordered, const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const int32_t *S_var,
+                       const int32_t *rank, int64_t V, const float *mask, int64_t T, float *ddg, float *hidden_opt, float *log_probs_opt,
+                       int32_t *status_opt, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream) {
+    REQUIRE(w, "%s: null weight handle", what);
+    REQUIRE(T >= 0 && T <= T_MAX && V >= 0, "%s: bad sizes (T=%lld, V=%lld)", what, (long long)T, (long long)V);
+    REQUIRE(!ddg || w->n_tensors == TMPNN_N_TENSORS, "%s: ddg requested but the handle has no head tensors", what);
     if (T == 0 || V == 0) return TMPNN_OK;            // nothing to decode (pointers may be null)
     if (T > T_MAX / V)
-        return tm_set_error(TMPNN_E_UNSUPPORTED, "decode_ordered: V * T = %lld * %lld rows exceed %lld (decode the variants in chunks)",
+        return tm_set_error(TMPNN_E_UNSUPPORTED, "%s: V * T = %lld * %lld rows exceed %lld (decode the variants in chunks)", what,
                             (long long)V, (long long)T, (long long)T_MAX);
-    if (T > ORD_ROWS_MAX / (V + 1))
-        return tm_set_error(TMPNN_E_UNSUPPORTED, "decode_ordered: (V + 1) * T = %lld * %lld rows exceed %lld (decode the variants in chunks)",
+    if (ordered && T > ORD_ROWS_MAX / (V + 1))
+        return tm_set_error(TMPNN_E_UNSUPPORTED, "%s: (V + 1) * T = %lld * %lld rows exceed %lld (decode the variants in chunks)", what,
                             (long long)(V + 1), (long long)T, (long long)ORD_ROWS_MAX);
-    REQUIRE(S_var && rank && mask, "decode_ordered: null input pointer");
-    REQUIRE(ddg || hidden_opt || log_probs_opt, "decode_ordered: no output requested");
+    REQUIRE(S_var && mask && (rank || !ordered), "%s: null input pointer", what);
+    REQUIRE(ddg || hidden_opt || log_probs_opt, "%s: no output requested", what);
     EncCtx c;
-    TRY(carve_ctx("decode_ordered", const_cast<void *>(ctx), ctx_bytes, T, &c));
+    TRY(carve_ctx(what, const_cast<void *>(ctx), ctx_bytes, T, &c));
     const int64_t R = V * T;
-    const size_t need = tmpnn_decode_ordered_workspace_bytes(T, V);
+    const size_t need = ordered ? tmpnn_decode_ordered_workspace_bytes(T, V) : tmpnn_decode_variants_workspace_bytes(T, V);
     uintptr_t base = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
     if (!workspace || workspace_bytes < need)
-        return tm_set_error(TMPNN_E_WORKSPACE, "decode_ordered: workspace %zu < %zu bytes", workspace_bytes, need);
+        return tm_set_error(TMPNN_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
     Carver cv{(char *)base, workspace_bytes - (base - (uintptr_t)workspace)};
-    float *P = (float *)cv.take((size_t)(R + T) * 256 * 4);         // [V + 1, T, 256]: slot V = Penc_l, the encoder state's projection
+    float *P = (float *)cv.take((size_t)(R + (ordered ? T : 0)) * 256 * 4);   // ordered: [V + 1, T, 256], slot V = Penc_l
     float *Ssum = (float *)cv.take((size_t)R * TMPNN_HID * 4);
     float *cnt = (float *)cv.take((size_t)R * 4);
     float *mask_rep = (float *)cv.take((size_t)R * 4);
-    void *vis = cv.take((size_t)R * 8);
-    int32_t *remap = (int32_t *)cv.take((size_t)T * TMPNN_KS * 4);
     float *hV[4];
     for (int i = 0; i < 4; ++i) hV[i] = (float *)cv.take((size_t)R * TMPNN_HID * 4);
-    if (!P || !Ssum || !cnt || !mask_rep || !vis || !remap || !hV[3])
-        return tm_set_error(TMPNN_E_WORKSPACE, "decode_ordered: workspace %zu < %zu bytes", workspace_bytes, need);
+    void *vis = ordered ? cv.take((size_t)R * 8) : nullptr;                   // visibility words, and the fp32 form's remapped list
+    int32_t *remap = ordered ? (int32_t *)cv.take((size_t)T * TMPNN_KS * 4) : nullptr;
+    if (!P || !Ssum || !cnt || !mask_rep || !hV[3] || (ordered && (!vis || !remap)))
+        return tm_set_error(TMPNN_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
     hipStream_t st = (hipStream_t)stream;
-    const TmModeScope scope(w);
     float *Penc = P + (size_t)R * 256;
-    // As tmpnn_decode_variants, but the message pass of every layer picks each neighbour's row by rank: the variant's own
-    // projection (this layer's state + sequence term) for a neighbour decoded earlier, Penc_l (no sequence) for the others.
     TRY(launch_variant_expand(c.hV, c.P0, mask, w->seq_table[0], S_var, T, V, hV[0], P, mask_rep, status_opt, st));
-    TRY(launch_variant_penc0(c.P0, T, Penc, st));               // Penc_0 = P0 (its neighbour half is W1c_0 h_V_enc)
-    TRY(launch_variant_vis(rank, c.E_idx, T, V, vis, st));
+    if (ordered) {
+        TRY(launch_variant_penc0(c.P0, T, Penc, st));               // Penc_0 = P0 (its neighbour half is W1c_0 h_V_enc)
+        TRY(launch_variant_vis(rank, c.E_idx, T, V, vis, st));
+    }
     for (int l = 0; l < 3; ++l) {
-        const DecW &d = w->dec[l];
-        TRY(launch_variant_msg(d.W1 + 128, 512, d.W2, d.b2, P, c.hE, c.E_idx, mask, T, V, Ssum, cnt, st, vis, remap));
+        TRY(launch_variant_msg(w->mode, w->dec[l].msg, P, c.hE, c.E_idx, mask, T, V, Ssum, cnt, st, vis, remap));
         const NodeProj next = dec_msg_proj(w, l < 2 ? l + 1 : 2, P, S_var);
-        TRY(launch_node_update(d.W3, d.b3, d.norm1_w, d.norm1_b, d.Win, d.bin, d.Wout, d.bout, d.norm2_w, d.norm2_b, hV[l], Ssum, cnt,
-                               mask_rep, R, hV[l + 1], l < 2 ? &next : nullptr, nullptr, st));
-        if (l < 2) {                                  // T rows, not V T: the next layer's projection of the ENCODER state
-            const DecW &n = w->dec[l + 1];
-            const NodeProj pe{n.W1, 512, n.b1, n.W1 + 384, 512, Penc, nullptr, nullptr};
+        TRY(launch_node_update(w->mode, w->dec[l].node, hV[l], Ssum, cnt, mask_rep, R, hV[l + 1], l < 2 ? &next : nullptr, nullptr, st));
+        if (ordered && l < 2) {                       // T rows, not V T: the next layer's projection of the ENCODER state
+            const NodeProj pe = dec_msg_proj(w, l + 1, Penc, nullptr);
             TRY(launch_node_proj(c.hV, pe, T, st));
         }
     }
@@ -929,4 +821,19 @@ extern "C" int tmpnn_decode_ordered(const tmpnn_weights_t *w, const void *ctx, s
     if (!ddg && !log_probs_opt) TRY(launch_range_check(hV[3], R * TMPNN_HID, status_opt, st));
     if (hidden_opt) TRY(launch_variant_hidden(hV + 1, T, V, hidden_opt, st));
     return TMPNN_OK;
+}
+
+extern "C" int tmpnn_decode_variants(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const int32_t *S_var, int64_t V,
+                                     const float *mask, int64_t T, float *ddg, float *hidden_opt, float *log_probs_opt,
+                                     int32_t *status_opt, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream) {
+    return decode_rows("decode_variants", false, w, ctx, ctx_bytes, S_var, nullptr, V, mask, T, ddg, hidden_opt, log_probs_opt, status_opt,
+                       workspace, workspace_bytes, stream);
+}
+
+extern "C" int tmpnn_decode_ordered(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const int32_t *S_var,
+                                    const int32_t *rank, int64_t V, const float *mask, int64_t T, float *ddg, float *hidden_opt,
+                                    float *log_probs_opt, int32_t *status_opt, void *workspace, size_t workspace_bytes,
+                                    tmpnn_stream_t stream) {
+    return decode_rows("decode_ordered", true, w, ctx, ctx_bytes, S_var, rank, V, mask, T, ddg, hidden_opt, log_probs_opt, status_opt,
+                       workspace, workspace_bytes, stream);
 }

@@ -226,10 +226,9 @@ __global__ __launch_bounds__(512, 2) void enc_edge8_rp_kernel(EdgeArgsB a, unsig
     }
 }
 
-int launch_enc_edge_split(int mode, const EncW &e, const float *P, float *hE, const int32_t *E_idx, int64_t T, hipStream_t st) {
+int launch_enc_edge_split(int mode, const EdgeW &e, const float *P, float *hE, const int32_t *E_idx, int64_t T, hipStream_t st) {
     const bool h2 = mode == TM_MM_F16X2;
-    EdgeArgsB a{e.W11 + 128, e.W12, e.b12, e.W13, e.b13, e.norm3_w, e.norm3_b, P, hE, E_idx, (int)T,
-                h2 ? tm_find_wimg(e.W11 + 128) : nullptr, h2 ? tm_find_wimg(e.W12) : nullptr, h2 ? tm_find_wimg(e.W13) : nullptr};
+    EdgeArgsB a{e.W11e, e.W12, e.b12, e.W13, e.b13, e.n3w, e.n3b, P, hE, E_idx, (int)T, e.img.w11, e.img.w12, e.img.w13};   // (images: null unless f16x2)
     if (h2 && !(a.img11 && a.img12 && a.img13))
         return tm_set_error(TMPNN_E_INVALID, "enc_edge_split: f16x2 handle without the fragment images of W11e / W12 / W13");
     const int64_t cap = tm_num_cus();

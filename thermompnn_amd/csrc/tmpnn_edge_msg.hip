@@ -200,18 +200,16 @@ __global__ __launch_bounds__(512, 2) void edge_msg_fused_kernel(EdgeArgsB a, Msg
 // The fused form is used when every workgroup has at most one tile (f16x2 handles only).
 bool edge_msg_fusable(int mode, int64_t T) { return mode == TM_MM_F16X2 && T > 0 && T <= (int64_t)tm_num_cus(); }
 
-int launch_edge_msg_fused(const EncW &e, const float *P_edge, float *hE, const int32_t *E_idx, bool dec, const float *W1e, int ld1,
-                          const float *W2, const float *b2, const float *P_msg, const float *mask, int64_t T, float *Ssum, float *cnt,
-                          hipStream_t st) {
-    EdgeArgsB a{e.W11 + 128, e.W12, e.b12, e.W13, e.b13, e.norm3_w, e.norm3_b, P_edge, hE, E_idx, (int)T,
-                tm_find_wimg(e.W11 + 128), tm_find_wimg(e.W12), tm_find_wimg(e.W13)};
-    MsgArgsB b{W1e, ld1, W2, b2, P_msg, hE, E_idx, mask, Ssum, cnt, (int)T, tm_find_wimg(W1e), tm_find_wimg(W2), tm_find_wimgp(W1e), tm_find_wimgp(W2), 0};
+int launch_edge_msg_fused(const EdgeW &e, const float *P_edge, float *hE, const int32_t *E_idx, const MsgW &m, const float *P_msg,
+                          const float *mask, int64_t T, float *Ssum, float *cnt, hipStream_t st) {
+    EdgeArgsB a{e.W11e, e.W12, e.b12, e.W13, e.b13, e.n3w, e.n3b, P_edge, hE, E_idx, (int)T, e.img.w11, e.img.w12, e.img.w13};
+    MsgArgsB b{m.W1e, m.ld1, m.W2, m.b2, P_msg, hE, E_idx, mask, Ssum, cnt, (int)T, m.img.w1, m.img.w2, m.img.p1, m.img.p2, 0};
     if (!(a.img11 && a.img12 && a.img13 && b.imgp1 && b.imgp2))
         return tm_set_error(TMPNN_E_INVALID, "edge_msg_fused: f16x2 handle without the fragment images of the edge update / message pass");
     const int64_t cap = tm_num_cus();
     const int grid = (int)(T < cap ? T : cap);
     tm_prof_begin("edge_msg_fused", st);
-    if (dec) edge_msg_fused_kernel<SplitH2, true><<<grid, 512, 0, st>>>(a, b);
+    if (m.dec) edge_msg_fused_kernel<SplitH2, true><<<grid, 512, 0, st>>>(a, b);
     else edge_msg_fused_kernel<SplitH2, false><<<grid, 512, 0, st>>>(a, b);
     tm_prof_end(st);
     return tm_check_launch("edge_msg_fused");

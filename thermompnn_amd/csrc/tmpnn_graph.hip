@@ -976,10 +976,10 @@ int launch_featurize(const tmpnn_weights *w, const float *X, const int32_t *ridx
     a.hE = h_E; a.E_opt = E_opt; a.T = (int)T;
     for (int i = 0; i < 16; ++i)   // torch.linspace(2, 22, 16): double arithmetic, symmetric halves, cast to fp32
         a.mu[i] = i < 8 ? (float)(2.0 + (20.0 / 15.0) * i) : (float)(22.0 - (20.0 / 15.0) * (15 - i));
-    const bool h2 = tm_matmul_mode() == TM_MM_F16X2;
+    const bool h2 = w->mode == TM_MM_F16X2;
     if (h2) {
-        for (int b = 0; b < 4; ++b) a.img_e[b] = tm_find_wimg(w->edge_w + 16 + 128 * b);
-        a.img_we = tm_find_wimg(w->We_w);
+        for (int b = 0; b < 4; ++b) a.img_e[b] = w->feat_img.edge[b];
+        a.img_we = w->feat_img.we;
         if (!a.img_e[0] || !a.img_e[1] || !a.img_e[2] || !a.img_e[3] || !a.img_we)
             return tm_set_error(TMPNN_E_INVALID, "edge_featurize: f16x2 handle without the fragment images of W_edge / W_e");
     }

@@ -194,7 +194,7 @@ __global__ void prep_conv_center_kernel(const float *__restrict__ conv_w, float 
 int launch_prep_tables(tmpnn_weights *w, hipStream_t st) {
     prep_pos_table_kernel<<<66, TM_H, 0, st>>>(w->pos_w, w->pos_b, w->edge_w, w->pos_table);
     for (int l = 0; l < 3; ++l)
-        prep_seq_table_kernel<<<TMPNN_VOCAB, TM_H, 0, st>>>(w->Ws_w, w->dec[l].W1, w->seq_table[l]);
+        prep_seq_table_kernel<<<TMPNN_VOCAB, TM_H, 0, st>>>(w->Ws_w, w->dec[l].msg_proj.spec.Wa, w->seq_table[l]);
     if (w->n_tensors == TMPNN_N_TENSORS)
         prep_conv_center_kernel<<<(384 * 384 + 255) / 256, 256, 0, st>>>(w->conv_w, w->conv_center);
     return tm_check_launch("prep_tables");
@@ -204,9 +204,9 @@ int tm_head_args(HeadArgs &a, const tmpnn_weights *w, const float *hA, const flo
                  float *z_opt, int32_t *status, const int32_t *maxlen_probe) {
     a = HeadArgs{w->conv_center, w->conv_b, w->mlp_w[0], w->mlp_b[0], w->mlp_w[1], w->mlp_b[1], w->mlp_w[2], w->mlp_b[2],
                  w->ddg_w, w->ddg_b, w->Ws_w, hA, hB, S, ddg, z_opt, (int)T, status, maxlen_probe, {}};
-    if (tm_matmul_mode() != TM_MM_F16X2) return TMPNN_OK;
+    if (w->mode != TM_MM_F16X2) return TMPNN_OK;
     for (int u = 0; u < 12; ++u) {
-        a.img[u] = tm_find_wimg(u < 9 ? w->conv_center + (size_t)128 * (u / 3) * 384 + 128 * (u % 3) : w->mlp_w[0] + 128 * (u - 9));
+        a.img[u] = w->head_img.unit[u];
         if (!a.img[u]) return tm_set_error(TMPNN_E_INVALID, "ddg_head: f16x2 handle without the fragment image of unit %d", u);
     }
     return TMPNN_OK;
@@ -229,7 +229,7 @@ int launch_head(const tmpnn_weights *w, const float *hA, const float *hB, const 
     const int64_t tiles = (T + best_rows - 1) / best_rows;
     const int grid = (int)(tiles < slots ? tiles : slots);
     tm_prof_begin("head", st);
-    if (tm_matmul_mode() == TM_MM_F16X2) {
+    if (w->mode == TM_MM_F16X2) {
         if (best_rows == 16) head8_split_kernel<SplitH2, 1><<<grid, 512, 0, st>>>(a);
         else if (best_rows == 32) head8_split_kernel<SplitH2, 2><<<grid, 512, 0, st>>>(a);
         else head8_split_kernel<SplitH2, 3><<<grid, 512, 0, st>>>(a);

@@ -18,7 +18,7 @@ struct HeadArgs {
     const int32_t *maxlen_probe;          // fused forward: E_idx [T,48]; slot 0 < 0 marks a row the k-NN kernel left empty because its
                                           // protein is longer than max_len -> TMPNN_STATUS_MAXLEN (the k-NN kernel zeroes the word and
                                           // therefore cannot OR into it itself: no memset launch in front of the forward)
-    const char *img[12];                  // f16 fragment images of the 12 GEMM units (WImg, tmpnn_internal.h); f16x2 only
+    const char *img[12];                  // f16 fragment images of the 12 GEMM units (HeadImg, tmpnn_internal.h); f16x2 only
 };
 
 __device__ __forceinline__ f4 relu4(f4 v) { return f4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)}; }

@@ -5,48 +5,69 @@
 
 #include "../../include/tmpnn.h"
 
-struct EncW {   // device pointers into the raw state-dict tensors of one EncLayer
-    const float *norm1_w, *norm1_b, *norm2_w, *norm2_b, *norm3_w, *norm3_b;
-    const float *W1, *b1, *W2, *b2, *W3, *b3, *W11, *b11, *W12, *b12, *W13, *b13;
-    const float *Win, *bin, *Wout, *bout;
-};
-struct DecW {
-    const float *norm1_w, *norm1_b, *norm2_w, *norm2_b;
-    const float *W1, *b1, *W2, *b2, *W3, *b3;
-    const float *Win, *bin, *Wout, *bout;
-};
-// Pre-built f16x2 MFMA A-fragment image of one 128 x 128 weight block for the 8-wavefront node kernels: 64 KB,
+// Pre-built f16x2 MFMA A-fragment image of one 128 x 128 weight block for the 8-wavefront kernels: 64 KB,
 // [wavefront 8][k-step 4][plane 2][lane 64] x 16 B — a wavefront's fragment is four coalesced 1 KB loads per plane
-// instead of 16-row gathers of fp32 that are split on the fly (tmpnn_split.hip: node_update8_split_kernel).
+// instead of 16-row gathers of fp32 that are split on the fly (tmpnn_node.hip: node_update8_split_kernel).
 #define TM_WIMG_BYTES 65536
-#define TM_N_WIMG 110          // enc: W3 + 4 W_in + 4 W_out + W1a W1c W11a W11c + W1e W2 W11e W12 W13 (18) x 3; dec: W3 + 4 + 4 + W1a W1d + W1e W2 (13) x 3; head: 9 blocks of the centre tap + 3 of both_out.1; featurizer: 4 blocks of W_edge[:, 16:416] + W_e
-#define TM_N_WIMGP 12          // the message kernels' W1e and W2 (3 encoder + 3 decoder layers) again with the K axis permuted inside every 32-deep step
-                               // (msg8_wave_kernel, tmpnn_msg.hip): element e of lane group q <-> k = 32 c + 16 (e >> 2) + 4 q + (e & 3)
-// The image rule: an f16x2 handle always carries every fragment image above (tmpnn_weights_create builds them all); an f16x2 launcher
-// looks up the images it needs and refuses with TMPNN_E_INVALID when one is missing; the f16x2 kernels assume them. fp32 and bf16x3
-// handles build no images and do not take this path.
-struct WImg { const float *base; const char *img; };      // base = address of the block's element [0][0] in the raw tensor
+// The image rule: tmpnn_weights_create_p builds every image of an f16x2 handle where it fills the weight structs below, and
+// stores its address in the struct member beside the weights it was made from; fp32 and bf16x3 handles build none and leave
+// those members null. An f16x2 launcher refuses with TMPNN_E_INVALID when an image it needs is null; the f16x2 kernels assume them.
+// Every struct keeps its images in one member `img` of nothing but `const char *`, so that the compiler counts them:
+#define TM_IMG_COUNT(S) ((int)(sizeof(S::img) / sizeof(const char *)))
+
+// kernel-side description of a node projection (an argument of node_proj_kernel's launcher and a member of NodeArgs):
+// P [T,256]: P[t, 0:128] = Wa h_t + ba, P[t, 128:256] = Wc h_t (+ add_tab[add_idx[t]] when add_tab is set: the decoder's
+// sequence term W1[:, 256:384] W_s[S_t], which rides with the neighbour's projection)
+struct ProjSpec { const float *Wa; int lda; const float *ba; const float *Wc; int ldc; float *P; const float *add_tab; const int32_t *add_idx; };
+// host side: the same with the images of its two blocks. The handle keeps one per consumer with P / add_* unset
+// (enc_msg_proj, enc_edge_proj and dec_msg_proj of tmpnn_api.hip fill those per call).
+struct NodeProj { ProjSpec spec; struct { const char *a, *c; } img; };
+// Device pointers into the raw state-dict tensors of one layer, grouped by the launcher that takes them.
+struct NodeW {   // node update: W3, LayerNorm 1, the feed-forward pair, LayerNorm 2
+    const float *W3, *b3, *n1w, *n1b, *Win, *bin, *Wout, *bout, *n2w, *n2b;
+    const char *img[9];            // W3, then (W_in rows 128 c.., W_out columns 128 c..) for c = 0..3: NodeArgs::img[0:9]
+};
+struct MsgW {    // message pass: the edge block of W1 (leading dimension 384 in the encoder, 512 in the decoder) and W2
+    const float *W1e; int ld1; const float *W2, *b2;
+    bool dec;
+    struct { const char *w1, *w2, *p1, *p2; } img;   // p*: the same blocks with the K axis permuted inside every 32-deep step
+                                                     // (msg8_wave_kernel: element e of lane group q <-> k = 32 c + 16 (e >> 2) + 4 q + (e & 3))
+};
+struct EdgeW {   // encoder edge update: the edge block of W11, W12, W13, LayerNorm 3
+    const float *W11e, *W12, *b12, *W13, *b13, *n3w, *n3b;
+    struct { const char *w11, *w12, *w13; } img;
+};
+struct EncW { NodeW node; MsgW msg; EdgeW edge; NodeProj msg_proj, edge_proj; };   // projections: W1a | W1c and W11a | W11c
+struct DecW { NodeW node; MsgW msg; NodeProj msg_proj; };                          // W1a | W1d (spec.Wa is W1 itself)
+struct FeatImg { const char *edge[4], *we; };   // edge_embedding.weight[:, 16:416] (four 128-column blocks, the last zero-padded), W_e
+struct HeadImg { const char *unit[12]; };        // 9 blocks of the conv centre tap + 3 of both_out.1: HeadArgs::img
 
 struct tmpnn_weights {
     int n_tensors;
     int mode;              // TM_MM_*: matrix-core path of this handle's per-edge GEMMs
-    WImg wimg[TM_N_WIMG];  // derived fragment images (in the caller's packed buffer), looked up by block base address
-    int n_wimg;
-    WImg wimgp[TM_N_WIMGP]; // K-permuted images (few: linear search)
-    int n_wimgp;
     const float *t[TMPNN_N_TENSORS];
     // features
     const float *pos_w, *pos_b, *edge_w, *norm_edges_w, *norm_edges_b, *We_w, *We_b, *Ws_w;
+    FeatImg feat_img;
     EncW enc[3];
     DecW dec[3];
     const float *Wout_w, *Wout_b;
     // head
     const float *conv_w, *conv_b, *mlp_w[3], *mlp_b[3], *ddg_w, *ddg_b;
+    HeadImg head_img;
     // derived tables (in the caller's packed buffer)
     float *pos_table;      // [66,128]   (W_pos^T + b_pos) . W_edge[:, :16]^T
     float *seq_table[3];   // [21,128]   W_s . W1_dec[l][:, 256:384]^T
     float *conv_center;    // [384,384]  feature_convolution.weight[:, :, 4]
 };
+// images of a full f16x2 handle, in the packed buffer behind the tables (a handle without the head tensors builds TM_N_HEAD_IMG fewer)
+enum {
+    TM_N_ENC_IMG = TM_IMG_COUNT(NodeW) + TM_IMG_COUNT(MsgW) + TM_IMG_COUNT(EdgeW) + 2 * TM_IMG_COUNT(NodeProj),
+    TM_N_DEC_IMG = TM_IMG_COUNT(NodeW) + TM_IMG_COUNT(MsgW) + TM_IMG_COUNT(NodeProj),
+    TM_N_HEAD_IMG = (int)(sizeof(HeadImg) / sizeof(const char *)),
+    TM_N_IMG = (int)(sizeof(FeatImg) / sizeof(const char *)) + TM_N_HEAD_IMG + 3 * TM_N_ENC_IMG + 3 * TM_N_DEC_IMG
+};
+static_assert(TM_N_IMG == 122, "tmpnn_weights_packed_bytes() is part of the ABI: 122 images of 64 KB + the tables");
 
 // scratch carved out of the caller's workspace for the message-passing layers
 struct LayerWs {
@@ -83,13 +104,10 @@ int launch_gather_rows(const float *nodes, const void *idx, int idx64, int64_t n
 int launch_gather_edges(const float *edges, const int64_t *idx, int B, int N, int K, int C, float *out, hipStream_t st);
 
 // tmpnn_layers.hip
-int launch_msg(bool dec, const float *W1e, int ld1, const float *W2, const float *b2, const float *P,
-               const float *hE, const int32_t *E_idx, const float *mask, int64_t T, float *Ssum, float *cnt, hipStream_t st);
-// P [T,256]: P[t, 0:128] = Wa h_t + ba, P[t, 128:256] = Wc h_t (+ add_tab[add_idx[t]] when add_tab is set: the decoder's
-// sequence term W1[:, 256:384] W_s[S_t], which rides with the neighbour's projection)
-struct NodeProj { const float *Wa; int lda; const float *ba; const float *Wc; int ldc; float *P; const float *add_tab; const int32_t *add_idx; };
-// kernel-side argument blocks of node_update (tmpnn_layers.hip: fp32 MFMA; tmpnn_split.hip: f16x2)
-struct ProjSpec { const float *Wa; int lda; const float *ba; const float *Wc; int ldc; float *P; const float *add_tab; const int32_t *add_idx; };
+// Every launcher below takes the precision (`mode`, TM_MM_*: the handle's) and the weight struct with its images as arguments.
+int launch_msg(int mode, const MsgW &m, const float *P, const float *hE, const int32_t *E_idx, const float *mask, int64_t T,
+               float *Ssum, float *cnt, hipStream_t st);
+// kernel-side argument block of node_update (tmpnn_layers.hip: fp32 MFMA; tmpnn_node.hip: f16x2)
 struct NodeArgs {
     const float *W3, *b3, *n1w, *n1b, *Win, *bin, *Wout, *bout, *n2w, *n2b;
     const float *h_in, *Ssum, *cnt, *mask;
@@ -104,12 +122,10 @@ struct HeadArgs;
 int launch_node_update_split(const NodeArgs &a, int64_t T, hipStream_t st, const HeadArgs *head = nullptr, bool *head_ran = nullptr);
 bool node_head_fusable(int mode, int64_t T);
 int launch_node_proj(const float *h, const NodeProj &np, int64_t T, hipStream_t st);
-int launch_node_update(const float *W3, const float *b3, const float *n1w, const float *n1b, const float *Win,
-                       const float *bin, const float *Wout, const float *bout, const float *n2w, const float *n2b,
-                       const float *h_in, const float *Ssum, const float *cnt, const float *mask, int64_t T,
+int launch_node_update(int mode, const NodeW &n, const float *h_in, const float *Ssum, const float *cnt, const float *mask, int64_t T,
                        float *h_out, const NodeProj *p0, const NodeProj *p1, hipStream_t st, const HeadArgs *head = nullptr,
                        bool *head_ran = nullptr);
-int launch_enc_edge(const EncW &e, const float *P, float *hE, const int32_t *E_idx, int64_t T, hipStream_t st);
+int launch_enc_edge(int mode, const EdgeW &e, const float *P, float *hE, const int32_t *E_idx, int64_t T, hipStream_t st);
 
 // tmpnn_head.hip
 int launch_head(const tmpnn_weights *w, const float *hA, const float *hB, const int32_t *S, int64_t T, float *ddg,
@@ -139,22 +155,22 @@ int launch_prep_tables(tmpnn_weights *w, hipStream_t st);
 
 int launch_clock_probe(int blocks, int iters, unsigned long long *out, float *sink, hipStream_t st);
 int launch_clock_monitor(int iters, unsigned long long *out, hipStream_t st);
-// tmpnn_split.hip (mode = TM_MM_F16X2 | TM_MM_BF16X3)
-int launch_enc_edge_split(int mode, const EncW &e, const float *P, float *hE, const int32_t *E_idx, int64_t T, hipStream_t st);
-int launch_msg_split(int mode, bool dec, const float *W1e, int ld1, const float *W2, const float *b2, const float *P,
-                     const float *hE, const int32_t *E_idx, const float *mask, int64_t T, float *Ssum, float *cnt, hipStream_t st);
+// tmpnn_edge.hip, tmpnn_msg.hip (mode = TM_MM_F16X2 | TM_MM_BF16X3)
+int launch_enc_edge_split(int mode, const EdgeW &e, const float *P, float *hE, const int32_t *E_idx, int64_t T, hipStream_t st);
+int launch_msg_split(int mode, const MsgW &m, const float *P, const float *hE, const int32_t *E_idx, const float *mask, int64_t T,
+                     float *Ssum, float *cnt, hipStream_t st);
+// tmpnn_split.hip
 int launch_gemm_probe(int mode, const float *X, const float *W, float *Y, int64_t T, int reps, hipStream_t st);
-// small launches (one tile per workgroup): edge update of layer l + message pass of the next layer as one launch (bit-identical)
+// tmpnn_edge_msg.hip, small launches (one tile per workgroup, f16x2): edge update of layer l + message pass of the next layer as
+// one launch (bit-identical)
 bool edge_msg_fusable(int mode, int64_t T);
-int launch_edge_msg_fused(const EncW &e, const float *P_edge, float *hE, const int32_t *E_idx, bool dec, const float *W1e, int ld1,
-                          const float *W2, const float *b2, const float *P_msg, const float *mask, int64_t T, float *Ssum, float *cnt,
-                          hipStream_t st);
+int launch_edge_msg_fused(const EdgeW &e, const float *P_edge, float *hE, const int32_t *E_idx, const MsgW &m, const float *P_msg,
+                          const float *mask, int64_t T, float *Ssum, float *cnt, hipStream_t st);
 // tmpnn_variants.hip: V sequence variants over one encoded backbone, rows r = v T + t (tmpnn_decode_variants)
 int launch_variant_expand(const float *hV, const float *P0, const float *mask, const float *tab, const int32_t *S_var, int64_t T,
                           int64_t V, float *hV_rep, float *P, float *mask_rep, int32_t *status, hipStream_t st);
-int launch_variant_msg(const float *W1e, int ld1, const float *W2, const float *b2, const float *P, const float *hE,
-                       const int32_t *E_idx, const float *mask, int64_t T, int64_t V, float *Ssum, float *cnt, hipStream_t st,
-                       const void *vis = nullptr, int32_t *remap = nullptr);
+int launch_variant_msg(int mode, const MsgW &m, const float *P, const float *hE, const int32_t *E_idx, const float *mask, int64_t T,
+                       int64_t V, float *Ssum, float *cnt, hipStream_t st, const void *vis = nullptr, int32_t *remap = nullptr);
 // order-masked decode (tmpnn_decode_ordered): visibility words [V T] x 8 bytes from rank [V,T]; P0 -> slot V of the table (layer 0)
 int launch_variant_vis(const int32_t *rank, const int32_t *E_idx, int64_t T, int64_t V, void *vis, hipStream_t st);
 int launch_variant_penc0(const float *P0, int64_t T, float *Penc, hipStream_t st);
@@ -177,17 +193,7 @@ int tm_num_cus();
 // matrix-core path of the per-edge GEMMs (tmpnn_split.h): a property of the weight handle (tmpnn_weights_create_p);
 // TMPNN_PRECISION = f16x2 (default) | bf16x3 | fp32 only picks the default of handles created without one.
 enum { TM_MM_FP32 = 0, TM_MM_BF16X3 = 1, TM_MM_F16X2 = 2 };
-int tm_matmul_mode();                 // mode of the API call in progress on this thread (set from the handle)
-const tmpnn_weights *tm_cur_weights();   // handle of the API call in progress (nullptr outside one)
-struct TmModeScope {                  // entry points that take a handle open one of these
-    int saved;
-    const tmpnn_weights *saved_w;
-    explicit TmModeScope(const tmpnn_weights *w);
-    ~TmModeScope();
-};
 int launch_prep_wimg(const float *W, int ld, char *dst, hipStream_t st, int n_rows = 128, int k_valid = 128, int k_wrap = 0, bool perm = false);       // tmpnn_split.hip
-const char *tm_find_wimg(const float *base);                                   // nullptr if no image (or no handle in scope)
-const char *tm_find_wimgp(const float *base);                                  // ... the K-permuted image of a full 128 x 128 block
 // Non-finite tests under -fno-honor-nans. The kernels are built with relaxed NaN semantics, so hipcc may fold a NaN test
 // on the RESULT of floating-point arithmetic (measured: both the sum test and the exponent-bit test on a computed value
 // were compiled away; only the inf half survives). Tests are therefore made on raw bits LOADED FROM MEMORY, before any

@@ -486,57 +486,53 @@ static int grid_for(int64_t work_items, int blocks_per_cu) {
 
 int launch_node_proj(const float *h, const NodeProj &np, int64_t T, hipStream_t st) {
     const int64_t tiles = (T + TM_TILE - 1) / TM_TILE;
-    { tm_prof_begin("node_proj", st); node_proj_kernel<<<grid_for(tiles, 2), TM_THREADS, 0, st>>>(h, np.Wa, np.lda, np.ba, np.Wc, np.ldc, (int)T, np.P, np.add_tab, np.add_idx); tm_prof_end(st); }
+    { tm_prof_begin("node_proj", st); node_proj_kernel<<<grid_for(tiles, 2), TM_THREADS, 0, st>>>(h, np.spec.Wa, np.spec.lda, np.spec.ba, np.spec.Wc, np.spec.ldc, (int)T, np.spec.P, np.spec.add_tab, np.spec.add_idx); tm_prof_end(st); }
     return tm_check_launch("node_proj");
 }
 
-int launch_msg(bool dec, const float *W1e, int ld1, const float *W2, const float *b2, const float *P,
-               const float *hE, const int32_t *E_idx, const float *mask, int64_t T, float *Ssum, float *cnt, hipStream_t st) {
+int launch_msg(int mode, const MsgW &m, const float *P, const float *hE, const int32_t *E_idx, const float *mask, int64_t T,
+               float *Ssum, float *cnt, hipStream_t st) {
+    const bool dec = m.dec;
     tm_prof_begin(dec ? "dec_msg" : "enc_msg", st);
-    if (tm_matmul_mode() != TM_MM_FP32) {
-        const int rc = launch_msg_split(tm_matmul_mode(), dec, W1e, ld1, W2, b2, P, hE, E_idx, mask, T, Ssum, cnt, st);
+    if (mode != TM_MM_FP32) {
+        const int rc = launch_msg_split(mode, m, P, hE, E_idx, mask, T, Ssum, cnt, st);
         tm_prof_end(st);
         return rc;
     }
-    MsgArgs a{W1e, ld1, W2, b2, P, hE, E_idx, mask, Ssum, cnt, (int)T, 0};
+    MsgArgs a{m.W1e, m.ld1, m.W2, m.b2, P, hE, E_idx, mask, Ssum, cnt, (int)T, 0};
     if (dec) msg_kernel<true, 4><<<grid_for(T, 2), 256, 0, st>>>(a);
     else msg_kernel<false, 4><<<grid_for(T, 2), 256, 0, st>>>(a);
     tm_prof_end(st);
     return tm_check_launch(dec ? "dec_msg" : "enc_msg");
 }
 
-int launch_enc_edge(const EncW &e, const float *P, float *hE, const int32_t *E_idx, int64_t T, hipStream_t st) {
+int launch_enc_edge(int mode, const EdgeW &e, const float *P, float *hE, const int32_t *E_idx, int64_t T, hipStream_t st) {
     tm_prof_begin("enc_edge", st);
-    if (tm_matmul_mode() != TM_MM_FP32) {        // split-precision 16-bit matrix-core forms (tmpnn_split.hip)
-        const int rc = launch_enc_edge_split(tm_matmul_mode(), e, P, hE, E_idx, T, st);
+    if (mode != TM_MM_FP32) {        // split-precision 16-bit matrix-core forms (tmpnn_edge.hip)
+        const int rc = launch_enc_edge_split(mode, e, P, hE, E_idx, T, st);
         tm_prof_end(st);
         return rc;
     }
-    EdgeArgs a{e.W11 + 128, e.W12, e.b12, e.W13, e.b13, e.norm3_w, e.norm3_b, P, hE, E_idx, (int)T};
+    EdgeArgs a{e.W11e, e.W12, e.b12, e.W13, e.b13, e.n3w, e.n3b, P, hE, E_idx, (int)T};
     enc_edge8_kernel<<<grid_for(T, 1), 512, 0, st>>>(a);
     tm_prof_end(st);
     return tm_check_launch("enc_edge8");
 }
 
-int launch_node_update(const float *W3, const float *b3, const float *n1w, const float *n1b, const float *Win,
-                       const float *bin, const float *Wout, const float *bout, const float *n2w, const float *n2b,
-                       const float *h_in, const float *Ssum, const float *cnt, const float *mask, int64_t T,
+int launch_node_update(int mode, const NodeW &n, const float *h_in, const float *Ssum, const float *cnt, const float *mask, int64_t T,
                        float *h_out, const NodeProj *p0, const NodeProj *p1, hipStream_t st, const HeadArgs *head, bool *head_ran) {
     if (head_ran) *head_ran = false;
-    NodeArgs a{W3, b3, n1w, n1b, Win, bin, Wout, bout, n2w, n2b, h_in, Ssum, cnt, mask, h_out, (int)T, {}};
+    NodeArgs a{n.W3, n.b3, n.n1w, n.n1b, n.Win, n.bin, n.Wout, n.bout, n.n2w, n.n2b, h_in, Ssum, cnt, mask, h_out, (int)T, {}, {}};
     const NodeProj *ps[2] = {p0, p1};
     for (int k = 0; k < 2; ++k)
-        a.proj[k] = ps[k] ? ProjSpec{ps[k]->Wa, ps[k]->lda, ps[k]->ba, ps[k]->Wc, ps[k]->ldc, ps[k]->P, ps[k]->add_tab, ps[k]->add_idx}
-                          : ProjSpec{nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr};
-    if (tm_matmul_mode() == TM_MM_F16X2) {   // fragment images of the 13 GEMM units (none for an absent projection)
-        const float *base[13] = {W3};
-        for (int c = 0; c < 4; ++c) { base[1 + 2 * c] = Win + (size_t)128 * c * 128; base[2 + 2 * c] = Wout + 128 * c; }
-        for (int k = 0; k < 2; ++k) { base[9 + 2 * k] = ps[k] ? ps[k]->Wa : nullptr; base[10 + 2 * k] = ps[k] ? ps[k]->Wc : nullptr; }
-        for (int u = 0; u < 13; ++u) {
-            a.img[u] = base[u] ? tm_find_wimg(base[u]) : nullptr;
-            if (base[u] && !a.img[u])
+        if (ps[k]) a.proj[k] = ps[k]->spec;           // (an absent projection stays all null: P == nullptr)
+    if (mode == TM_MM_F16X2) {   // fragment images of the 13 GEMM units (none for an absent projection)
+        for (int u = 0; u < 9; ++u) a.img[u] = n.img[u];
+        for (int k = 0; k < 2; ++k)
+            if (ps[k]) { a.img[9 + 2 * k] = ps[k]->img.a; a.img[10 + 2 * k] = ps[k]->img.c; }
+        for (int u = 0; u < 13; ++u)
+            if ((u < 9 || ps[(u - 9) / 2]) && !a.img[u])
                 return tm_set_error(TMPNN_E_INVALID, "node_update: f16x2 handle without the fragment image of unit %d", u);
-        }
         tm_prof_begin("node_update", st);
         const int rc = launch_node_update_split(a, T, st, head, head_ran);
         tm_prof_end(st);

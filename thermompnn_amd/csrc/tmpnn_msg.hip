@@ -475,12 +475,10 @@ __global__ __launch_bounds__(512, 2) void msg8_wave_kernel(MsgArgsB a, unsigned 
         prof[(tm_bid() == 0 ? 16 : 24) + (tm_tid() >> 6)] = __builtin_readcyclecounter() - c_begin;
 }
 
-int launch_msg_split(int mode, bool dec, const float *W1e, int ld1, const float *W2, const float *b2, const float *P,
-                     const float *hE, const int32_t *E_idx, const float *mask, int64_t T, float *Ssum, float *cnt,
-                     hipStream_t st) {
-    const bool h2 = mode == TM_MM_F16X2;
-    MsgArgsB a{W1e, ld1, W2, b2, P, hE, E_idx, mask, Ssum, cnt, (int)T, h2 ? tm_find_wimg(W1e) : nullptr, h2 ? tm_find_wimg(W2) : nullptr,
-               h2 ? tm_find_wimgp(W1e) : nullptr, h2 ? tm_find_wimgp(W2) : nullptr, 0};
+int launch_msg_split(int mode, const MsgW &m, const float *P, const float *hE, const int32_t *E_idx, const float *mask, int64_t T,
+                     float *Ssum, float *cnt, hipStream_t st) {
+    const bool h2 = mode == TM_MM_F16X2, dec = m.dec;
+    MsgArgsB a{m.W1e, m.ld1, m.W2, m.b2, P, hE, E_idx, mask, Ssum, cnt, (int)T, m.img.w1, m.img.w2, m.img.p1, m.img.p2, 0};   // (images: null unless f16x2)
     if (h2 && !(a.imgp1 && a.imgp2))
         return tm_set_error(TMPNN_E_INVALID, "msg_split: f16x2 handle without the K-permuted fragment images of W1e / W2");
     const int64_t cap = tm_num_cus();

@@ -426,7 +426,7 @@ __device__ __forceinline__ void row_stats_finish8d(const float *stat_row, int la
 // ------------------------------------------------------------------------------------------------
 // shared by the per-edge kernel files (tmpnn_edge.hip, tmpnn_msg.hip, tmpnn_edge_msg.hip, tmpnn_node.hip)
 // ------------------------------------------------------------------------------------------------
-// Weight fragment of wavefront wv from a pre-built image (WImg, tmpnn_internal.h): 8 coalesced 16-byte loads instead of the
+// Weight fragment of wavefront wv from a pre-built image (TM_WIMG_BYTES, tmpnn_internal.h): 8 coalesced 16-byte loads instead of the
 // 16-row fp32 gathers + on-the-fly split of load_wfrag_split. img == nullptr -> the gather path.
 // The message pass's K order (round 5). Its wavefront-per-residue form (msg8_wave_kernel) keeps the activations in the MFMA accumulator
 // layout, so lane group q of 32-deep step c holds k = 32 c + 4 q + {0..3} and 32 c + 16 + 4 q + {0..3}. The products of a step are summed

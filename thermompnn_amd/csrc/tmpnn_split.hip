@@ -79,7 +79,7 @@ int launch_gemm_probe(int mode, const float *X, const float *W, float *Y, int64_
     return tm_check_launch("gemm_probe");
 }
 
-// fragment image of one 128 x 128 block (see WImg in tmpnn_internal.h): [wv 8][c 4][plane 2][lane 64] x 16 B
+// fragment image of one 128 x 128 block (see TM_WIMG_BYTES in tmpnn_internal.h): [wv 8][c 4][plane 2][lane 64] x 16 B
 // perm (full blocks only): the 8 values of lane group q in step c are k = 32 c + 4 q + {0..3} and 32 c + 16 + 4 q + {0..3} — the K order in
 // which a wavefront that keeps its activations in the accumulator layout holds them (msg8_wave_kernel)
 __global__ void prep_wimg_kernel(const float *__restrict__ W, int ld, int n_rows, int k_valid, int k_wrap, char *__restrict__ dst, bool perm) {

@@ -284,10 +284,8 @@ int launch_variant_penc0(const float *P0, int64_t T, float *Penc, hipStream_t st
 
 // vis == nullptr: every neighbour visible, P [V T, 256] (tmpnn_decode_variants). Otherwise P [(V + 1) T, 256] with Penc_l in slot V,
 // (V + 1) T 256 < 2^32 (checked by the caller); remap [T,48]: scratch of the fp32 form.
-int launch_variant_msg(const float *W1e, int ld1, const float *W2, const float *b2, const float *P, const float *hE,
-                       const int32_t *E_idx, const float *mask, int64_t T, int64_t V, float *Ssum, float *cnt, hipStream_t st,
-                       const void *vis, int32_t *remap) {
-    const int mode = tm_matmul_mode();
+int launch_variant_msg(int mode, const MsgW &m, const float *P, const float *hE, const int32_t *E_idx, const float *mask, int64_t T,
+                       int64_t V, float *Ssum, float *cnt, hipStream_t st, const void *vis, int32_t *remap) {
     if (mode == TM_MM_FP32) {       // the fused forward's own kernel, variant after variant: its arithmetic exactly
         for (int64_t v = 0; v < V; ++v) {
             const int32_t *list = E_idx;
@@ -300,15 +298,14 @@ int launch_variant_msg(const float *W1e, int ld1, const float *W2, const float *
                 if (rc != TMPNN_OK) return rc;
                 list = remap;
             }
-            const int rc = launch_msg(true, W1e, ld1, W2, b2, P + (size_t)v * T * 256, hE, list, mask, T, Ssum + (size_t)v * T * TM_H,
-                                      cnt + (size_t)v * T, st);
+            const int rc = launch_msg(mode, m, P + (size_t)v * T * 256, hE, list, mask, T, Ssum + (size_t)v * T * TM_H, cnt + (size_t)v * T, st);
             if (rc != TMPNN_OK) return rc;
         }
         return TMPNN_OK;
     }
     const bool h2 = mode == TM_MM_F16X2;
-    VarMsgArgs a{W1e, ld1, W2, b2, P, hE, E_idx, mask, Ssum, cnt, (int)T, (int)V, 0, 0, h2 ? tm_find_wimgp(W1e) : nullptr,
-                 h2 ? tm_find_wimgp(W2) : nullptr, (const uint2 *)vis, (unsigned)((uint64_t)V * (uint64_t)T * 256u)};
+    VarMsgArgs a{m.W1e, m.ld1, m.W2, m.b2, P, hE, E_idx, mask, Ssum, cnt, (int)T, (int)V, 0, 0, m.img.p1, m.img.p2, (const uint2 *)vis,
+                 (unsigned)((uint64_t)V * (uint64_t)T * 256u)};
     if (h2 && !(a.imgp1 && a.imgp2))
         return tm_set_error(TMPNN_E_INVALID, "variant_msg: f16x2 handle without the K-permuted fragment images of W1e / W2");
     // Variants per workgroup: all of them once the residues alone fill the chip four times over; below that the variant axis is cut
