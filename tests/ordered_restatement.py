@@ -15,7 +15,8 @@ from oracle import thermompnn_oracle as orc
 
 def ordered_decode(W, g, S_var, ranks, E_idx, f64=False):
     """W: full synthetic state dict (prot_mpnn.* keys); g: a golden fixture (X, mask, residue_idx, chain_enc); S_var, ranks [V,L];
-    E_idx [L,K] -> dict(hidden [V,3,L,128], log_probs [V,L,21]) as numpy arrays."""
+    E_idx [L,K], K <= 48 -> dict(hidden [V,3,L,128], log_probs [V,L,21], ddg [V,L,21]) as numpy arrays. ddg is the oracle's
+    head_table on the restated decoder states as ssm_table calls it (reversed hidden list, the variant's own h_S and S)."""
     t = torch.from_numpy
     dt = torch.float64 if f64 else torch.float32
     orig_float, orig_default = torch.Tensor.float, torch.get_default_dtype()
@@ -23,7 +24,7 @@ def ordered_decode(W, g, S_var, ranks, E_idx, f64=False):
         torch.Tensor.float = lambda self, *a, **k: self.double()      # the oracle's explicit .float() casts -> float64
         torch.set_default_dtype(torch.float64)
     try:
-        mp = {k: v.to(dt) for k, v in orc.split_weights(W)[0].items()}
+        mp, hd = ({k: v.to(dt) for k, v in part.items()} for part in orc.split_weights(W))
         X, mask = t(np.ascontiguousarray(g["X"])).to(dt)[None], t(np.ascontiguousarray(g["mask"])).to(dt)[None]
         ridx, cenc = t(g["residue_idx"].astype(np.int64))[None], t(g["chain_enc"].astype(np.int64))[None]
         ei = t(np.ascontiguousarray(E_idx).astype(np.int64))[None]
@@ -36,7 +37,7 @@ def ordered_decode(W, g, S_var, ranks, E_idx, f64=False):
                 h_V_enc, h_E = orc.enc_layer(mp, f"encoder_layers.{i}", h_V_enc, h_E, E_idx_t, mask, mask_attend)
             h_EXV_encoder = orc.cat_neighbors_nodes(h_V_enc, orc.cat_neighbors_nodes(torch.zeros_like(h_V_enc), h_E, E_idx_t), E_idx_t)
             mask_1D = mask.view(1, -1, 1, 1)
-            hidden, log_probs = [], []
+            hidden, log_probs, ddg = [], [], []
             for S, rank in zip(np.asarray(S_var), np.asarray(ranks)):
                 r = t(rank.astype(np.int64))[None]
                 vis = (torch.gather(r.unsqueeze(1).expand(-1, r.shape[1], -1), 2, E_idx_t) < r.unsqueeze(-1)).to(dt).unsqueeze(-1)
@@ -48,13 +49,14 @@ def ordered_decode(W, g, S_var, ranks, E_idx, f64=False):
                 for i in range(3):
                     h_ESV = mask_bw * orc.cat_neighbors_nodes(h_V, h_ES, E_idx_t) + h_EXV_encoder_fw
                     h_V = orc.dec_layer(mp, f"decoder_layers.{i}", h_V, h_ESV, mask)
-                    hs.append(h_V[0])
-                hidden.append(torch.stack(hs))
+                    hs.append(h_V)
+                hidden.append(torch.cat(hs))
+                ddg.append(orc.head_table(hd, hs[::-1], h_S, t(S.astype(np.int64))[None])[1][0])
                 log_probs.append(F.log_softmax(orc.linear(h_V, mp, "W_out"), dim=-1)[0])
     finally:
         torch.Tensor.float = orig_float
         torch.set_default_dtype(orig_default)
-    return {"hidden": torch.stack(hidden).numpy(), "log_probs": torch.stack(log_probs).numpy()}
+    return {"hidden": torch.stack(hidden).numpy(), "log_probs": torch.stack(log_probs).numpy(), "ddg": torch.stack(ddg).numpy()}
 
 
 def conditional_ranks(randn, idx, L, backbone_only=False):

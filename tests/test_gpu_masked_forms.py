@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from masked_backbones import LAYOUTS, SEEN, layout_arrays, oracle_trace, variants_of
+from masked_backbones import LAYOUTS, SEEN, checked_graph, filler, layout_arrays, oracle_trace, pack, protein, variants_of
 
 pytestmark = pytest.mark.gpu
 
@@ -34,26 +34,6 @@ def engine(precision, K=48):
     return _ENGINES[precision, K]
 
 
-def protein(name):
-    X, S, mask, ridx, cenc = layout_arrays(name)
-    return dict(X=X, S=S, mask=mask, ridx=ridx, cenc=cenc)
-
-
-def filler():
-    """The unmasked L = 64 synthetic protein the ragged batches are filled up with."""
-    from thermompnn_amd.synthetic import AA20, synthetic_backbone
-    X, seq = synthetic_backbone(64, 1)
-    return dict(X=X.astype(np.float32), S=np.array([AA20.index(c) for c in seq], dtype=np.int64), mask=np.ones(64, np.float32),
-                ridx=np.arange(64), cenc=np.ones(64, np.int64))
-
-
-def pack(prots):
-    cat = lambda k, dt: torch.from_numpy(np.concatenate([np.asarray(p[k]) for p in prots])).to("cuda:0", dt)
-    starts = np.concatenate([[0], np.cumsum([len(p["S"]) for p in prots])])
-    return dict(X=cat("X", torch.float32), S=cat("S", torch.int32), mask=cat("mask", torch.float32), ridx=cat("ridx", torch.int32),
-                cenc=cat("cenc", torch.int32), offsets=torch.tensor(starts, dtype=torch.int32), starts=starts)
-
-
 def close(got, want, tol, prec, what):
     err = float(np.abs(np.asarray(got, dtype=np.float64) - np.asarray(want, dtype=np.float64)).max()) if np.size(want) else 0.0
     WORST[f"{prec}/{what}"] = max(WORST.get(f"{prec}/{what}", 0.0), err)
@@ -73,23 +53,6 @@ def _evidence(tmp_path_factory):
             json.dump({"lines": {"intermediate": TOL_INTERMEDIATE, "ddg": TOL_DDG}, "worst_abs_error": WORST}, fh, indent=1, sort_keys=True)
     except OSError:
         pass
-
-
-def checked_graph(name, ei, K=48):
-    """The device's graph of a layout alone ([L, 48] local indices): -1 beyond min(K, L), and on every unmasked row a valid top-k of
-    the oracle's adjusted distances up to exact ties. -> [L, Keff]."""
-    from oracle import thermompnn_oracle as orc
-    X, _, mask, _, _ = layout_arrays(name)
-    L = len(mask)
-    Keff = min(K, L)
-    assert (ei[:, Keff:] == -1).all() and (ei[:, :Keff] >= 0).all() and (ei[:, :Keff] < L).all()
-    D_adj = orc.adjusted_distances(torch.from_numpy(X)[None, :, 1], torch.from_numpy(mask)[None])[0].numpy()
-    dead = set(np.nonzero(mask == 0)[0].tolist())
-    for i in np.nonzero(mask > 0)[0]:
-        kth = np.sort(D_adj[i])[Keff - 1]
-        assert (D_adj[i, ei[i, :Keff]] <= kth).all() and len(set(ei[i, :Keff].tolist())) == Keff, f"row {i}"
-        assert set(ei[i, :Keff].tolist()) & dead, f"row {i} lists no masked residue"
-    return np.ascontiguousarray(ei[:, :Keff]), D_adj
 
 
 # ---- a. the single operators ------------------------------------------------------------------------

@@ -15,6 +15,7 @@ from ordered_restatement import ordered_decode
 pytestmark = pytest.mark.gpu
 
 TOL_INTERMEDIATE = 1e-5   # abs; the project's line for decoder states and log-probabilities
+TOL_DDG = 1e-4            # kcal/mol
 ORDER_MOVES = 1e-3        # 100 x the line: two opposite orders must differ by more than this somewhere
 PRECISIONS = ["f16x2", "bf16x3", "fp32"]
 _ENGINES, _MODELS, _RESTATED = {}, {}, {}
@@ -145,11 +146,12 @@ def test_arbitrary_orders_match_the_restatement(case, precision):
     enc = encode(eng, p)
     ei = enc.E_idx.cpu().numpy()[:, :min(48, p["L"])]
     seqs, ranks = orders_of(g)
-    res = eng.decode_ordered(enc, seqs, ranks, want_hidden=True)
+    res = eng.decode_ordered(enc, seqs, ranks, want_ddg=True, want_hidden=True)
     got = {k: v.cpu().numpy() for k, v in res.items()}
+    assert (got["ddg"][np.arange(len(seqs))[:, None], np.arange(p["L"]), seqs] == 0).all()      # relative to the variant's own residue
     ref = restated(g, case, seqs, ranks, ei)
     t64 = restated(g, case, seqs, ranks, ei, f64=True) if is_hot(g) else None
-    for what in ("hidden", "log_probs"):
+    for what, line in (("hidden", TOL_INTERMEDIATE), ("log_probs", TOL_INTERMEDIATE), ("ddg", TOL_DDG)):
         if t64 is not None:
             truth = t64[what].astype(np.float64)
             ref_err = float(np.abs(ref[what].astype(np.float64) - truth).max())
@@ -158,8 +160,8 @@ def test_arbitrary_orders_match_the_restatement(case, precision):
             assert hip_err <= HOT_F64_FACTOR * ref_err, (case, precision, what, hip_err, ref_err)
         else:
             err = np.abs(got[what].astype(np.float64) - ref[what]).reshape(len(seqs), -1).max(1)
-            print(f"{case}/{precision}/{what}: per variant {np.array2string(err, precision=2)} (line {TOL_INTERMEDIATE:g})")
-            assert err.max() <= TOL_INTERMEDIATE, (case, precision, what, err)
+            print(f"{case}/{precision}/{what}: per variant {np.array2string(err, precision=2)} (line {line:g})")
+            assert err.max() <= line, (case, precision, what, err)
     # the order is honoured: left-to-right (variant 0) and reversed (variant 2) of the same sequence are far apart
     assert float(np.abs(ref["log_probs"][0] - ref["log_probs"][2]).max()) > ORDER_MOVES
     assert float(np.abs(got["log_probs"][0] - got["log_probs"][2]).max()) > ORDER_MOVES

@@ -10,12 +10,24 @@ import pytest
 import torch
 
 from conftest import load_golden, tol_scale, weights_for_case
+from masked_backbones import layout_arrays
 from ordered_restatement import conditional_ranks, ordered_decode
 
 TOL_INTERMEDIATE = 1e-5   # abs; the line test_oracle_golden.py holds the oracle's log_probs to
 T_MAX = (1 << 31) // (48 * 4) - 1
 E_INVALID, E_WORKSPACE, E_UNSUPPORTED = -1, -4, -2
 CASES = ["syn_L32", "2OCJ_A", "2OCJ_A_gap"]
+MASKED_CASES = ["msk_L17", "msk_L40", "msk_L56_2ch"]     # layouts of masked_backbones.py; their fixtures carry the reference's own E_idx
+
+
+def inputs_of(case):
+    """The structure of a case with the graph the reference decoded on: a golden fixture, or a masked layout with the E_idx its
+    ordered fixture stores (torch.topk's choice among the masked residues tied at D_max)."""
+    if case not in MASKED_CASES:
+        return load_golden(case)
+    X, S, mask, ridx, cenc = layout_arrays(case)
+    return dict(X=X, S=S, mask=mask, residue_idx=ridx, chain_enc=cenc, weight_seed=np.int64(0),
+                E_idx=load_golden("ordered_" + case)["E_idx"])
 
 
 @pytest.fixture(scope="module")
@@ -25,11 +37,11 @@ def lib():
     return _lib.load()
 
 
-@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("case", CASES + MASKED_CASES)
 def test_restatement_reproduces_the_reference(case):
     """fp32, on the fixture's own E_idx: every looped row of cond (one decode per position, the position last), the looped rows of
     cond_backbone_only (the position first) and uncond (all ranks equal). Rows that are not looped over are exactly 0."""
-    g, o = load_golden(case), load_golden("ordered_" + case)
+    g, o = inputs_of(case), load_golden("ordered_" + case)
     W = weights_for_case(g)
     L = len(g["S"])
     looped = np.nonzero(g["mask"] == 1)[0]
@@ -52,6 +64,53 @@ def test_restatement_reproduces_the_reference(case):
     np.testing.assert_allclose(unc[looped], o["cond_backbone_only"][looped], atol=tol(o["cond_backbone_only"]), rtol=0)
     # the modes are far apart on the scale of the line: a test at 1e-5 tells them apart
     assert np.abs(o["cond"] - o["uncond"])[looped].max() > 1e-2
+
+
+@pytest.mark.parametrize("case", MASKED_CASES)
+def test_masked_fixtures_hold_a_visible_masked_neighbour_of_an_unmasked_row(case):
+    """What the three masked fixtures are for: in each, some unmasked row lists a masked residue on the reference's own graph, and
+    that row's cond (the masked residue decoded earlier: its sequence term and zero decoder state enter) differs from its uncond
+    (its encoder state enters). The reference masks by the row, not by the neighbour (mask_bw = mask_1D * mask_attend)."""
+    g, o = inputs_of(case), load_golden("ordered_" + case)
+    L = len(g["S"])
+    ei = o["E_idx"].astype(np.int64)
+    assert ei.shape == (L, min(48, L)) and ei.min() >= 0 and ei.max() < L
+    assert o["cond"].shape == o["uncond"].shape == o["cond_backbone_only"].shape == (L, 21)
+    dead = g["mask"] == 0
+    rows = [i for i in np.nonzero(~dead)[0] if dead[ei[i]].any()]
+    assert rows, "no unmasked row lists a masked residue"
+    moved = np.abs(o["cond"][rows] - o["uncond"][rows]).max(1)
+    assert (moved > 0).all() and moved.max() > 1e-2, moved
+    # under the order of row i (i last) every listed masked residue is visible: randn orders the others, never i
+    i = rows[0]
+    rank = conditional_ranks(o["randn"], int(i), L)
+    assert (rank[ei[i][dead[ei[i]]]] < rank[i]).all()
+
+
+def test_restatement_ddg_is_the_head_on_the_restated_states_also_on_30_columns():
+    """ddg of the restatement: relative to the variant's own residue, the oracle's head_table on the restated states (recomputed
+    here from the returned hidden), float64 within the 1e-4 line of fp32, and a 30-column graph is accepted. The recomputation
+    makes the same head_table call in the same argument order as the restatement, so it cannot tell a wrong order of the hidden
+    list; that is held by the GPU comparisons of ddg against kernels that are themselves pinned to the reference's ddG fixtures."""
+    from oracle import thermompnn_oracle as orc
+    g = inputs_of("msk_L40")
+    W = weights_for_case(g)
+    L = len(g["S"])
+    rng = np.random.default_rng(2)
+    S = np.stack([g["S"].astype(np.int64), rng.integers(0, 21, L)])
+    ranks = np.stack([rng.permutation(L), np.zeros(L, np.int64)])
+    for ei in (g["E_idx"], np.ascontiguousarray(g["E_idx"][:, :30])):
+        r32, r64 = ordered_decode(W, g, S, ranks, ei), ordered_decode(W, g, S, ranks, ei, f64=True)
+        assert r32["ddg"].shape == (2, L, 21) and r32["ddg"].dtype == np.float32 and r64["ddg"].dtype == np.float64
+        assert (r32["ddg"][np.arange(2)[:, None], np.arange(L), S] == 0).all()
+        hd = orc.split_weights(W)[1]
+        for v in range(2):
+            h = [torch.from_numpy(r32["hidden"][v, l])[None] for l in (2, 1, 0)]
+            h_S = torch.nn.functional.embedding(torch.from_numpy(S[v])[None], W["prot_mpnn.W_s.weight"])
+            assert np.array_equal(orc.head_table(hd, h, h_S, torch.from_numpy(S[v])[None])[1][0].numpy(), r32["ddg"][v])
+        for k in ("ddg", "hidden", "log_probs"):
+            assert np.abs(r32[k] - r64[k]).max() < (1e-4 if k == "ddg" else TOL_INTERMEDIATE), k
+    assert np.abs(r32["ddg"][0] - r32["ddg"][1]).max() > 1e-2
 
 
 @pytest.mark.parametrize("case", CASES)
