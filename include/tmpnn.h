@@ -336,6 +336,32 @@ int tmpnn_decode_ordered(const tmpnn_weights_t *w, const void *ctx, size_t ctx_b
                          float *hidden_opt, float *log_probs_opt, int32_t *status_opt,
                          void *workspace, size_t workspace_bytes, tmpnn_stream_t stream);
 
+/* ---- autoregressive sampling over one encoded backbone ---------------------------------------------------
+ * ProteinMPNN.sample's loop (protein_mpnn_utils.py:1279-1383) for N CHAINS over the encoded batch, in ONE launch: a chain is one
+ * sequence being sampled over the packed residue axis, with its own decoding order, fixed positions and uniform draws. A workgroup
+ * owns up to 16 chains and runs their T steps inside the kernel; no workgroup reads what another writes. Step s of chain n decodes
+ * residue t = order[n,s] with tmpnn_decode_ordered's arithmetic for a variant whose ranks are the inverse of `order` (the residues of
+ * earlier steps are visible with the letters the chain chose), then
+ *     probs = softmax(logits * inv_temperature + bias[t]);  with allowed: probs = probs * allowed[t] / sum(probs * allowed[t]);
+ *     c_a = fp32 running sum of probs in index order; the pick is the smallest a with c_a > u[n,t] * c_20, or, if rounding leaves
+ *     none, the largest a with probs_a > 0.
+ * S_out[n,t] is the pick where free[n,t] * mask[t] == 1 and S_fixed[n,t] elsewhere; probs_opt[n,t,:] is probs there and exactly 0
+ * elsewhere. A chain's result has the same bits whatever N is, whichever slot it takes and whichever chains run with it. The message
+ * GEMMs run at the handle's precision (f16x2 | bf16x3); the 16-row node update, projections and logits are exact fp32 matrix-core
+ * arithmetic for both. An fp32 handle is refused with TMPNN_E_UNSUPPORTED (use "bf16x3"). 3 * N * T < 2^24 (32-bit row arithmetic):
+ * TMPNN_E_UNSUPPORTED beyond it (sample in chunks of chains) and tmpnn_sample_workspace_bytes returns 0. An order entry outside
+ * [0, T) skips that step; letters are clamped to [0, 21) before any table lookup; non-finite logits OR TMPNN_STATUS_RANGE into
+ * status_opt (zeroed on the stream first) and that step takes S_fixed. T == 0 or N == 0 is a no-op. */
+size_t tmpnn_sample_workspace_bytes(int64_t T, int64_t N);          /* 0 = unsupported sizes */
+int tmpnn_sample(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const float *mask, int64_t T, int64_t N,
+                 const int32_t *order,      /* [N,T] a permutation of 0..T-1 per chain: order[n,s] is decoded at step s */
+                 const int32_t *S_fixed,    /* [N,T] letters kept where free == 0 or mask == 0 */
+                 const float *free,         /* [N,T] 1 = sample here (the reference's chain_mask * chain_M_pos) */
+                 const float *u,            /* [N,T] uniforms in [0,1), indexed by RESIDUE, not by step */
+                 float inv_temperature, const float *bias_opt /* [T,21] */, const float *allowed_opt /* [T,21] */,
+                 int32_t *S_out /* [N,T] */, float *probs_opt /* [N,T,21] */,
+                 int32_t *status_opt, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream);
+
 /* ---- host side: native PDB reader + packer ------------------------------------------
  * Replaces alt_parse_PDB (protein_mpnn_utils.py:183-350) + the packing of tied_featurize (:353-605) for one
  * structure: one pass over the file, all requested chains. `chains` = string of one-letter chain ids in the

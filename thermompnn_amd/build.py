@@ -15,7 +15,7 @@ LIB = os.path.join(HERE, "libtmpnn.so")
 # and tools/phase_prof.py load it through TMPNN_LIB.
 DEBUG_LIB = os.path.join(HERE, "libtmpnn_debug.so")
 SOURCES = ["tmpnn_api.hip", "tmpnn_graph.hip", "tmpnn_layers.hip", "tmpnn_head.hip", "tmpnn_split.hip", "tmpnn_edge.hip", "tmpnn_msg.hip",
-           "tmpnn_edge_msg.hip", "tmpnn_node.hip", "tmpnn_variants.hip", "tmpnn_train.hip", "tmpnn_finetune.hip", "tmpnn_pdb.cpp",
+           "tmpnn_edge_msg.hip", "tmpnn_node.hip", "tmpnn_variants.hip", "tmpnn_sample.hip", "tmpnn_train.hip", "tmpnn_finetune.hip", "tmpnn_pdb.cpp",
            "tmpnn_csv.cpp"]
 HEADERS = ["tmpnn_common.h", "tmpnn_split.h", "tmpnn_internal.h", "tmpnn_head_body.h", os.path.join("..", "..", "include", "tmpnn.h"),
            os.path.join("..", "..", "include", "tmpnn_debug.h"), "tmpnn_host_guard.hpp"]
@@ -30,7 +30,8 @@ DEVICE_FLAGS = ["-mno-amdgpu-ieee", "-fno-honor-nans"]
 # of exactly this property, and the variant decoder's message kernel, tmpnn_variants.hip): their GELU clamps are gfx950's NaN-PROPAGATING v_minimum3_f32 /
 # v_maximum3_f32 (IEEE-754-2019; no canonicalising op in front of them either), which hipcc emits from __builtin_elementwise_minimum /
 # maximum only in a translation unit that honours NaNs (under -fno-honor-nans they degrade to v_min / v_max). See gelu2, TM_GELU_NAN3.
-NAN3_FILES = ("tmpnn_split.hip", "tmpnn_edge.hip", "tmpnn_msg.hip", "tmpnn_edge_msg.hip", "tmpnn_node.hip", "tmpnn_variants.hip")
+NAN3_FILES = ("tmpnn_split.hip", "tmpnn_edge.hip", "tmpnn_msg.hip", "tmpnn_edge_msg.hip", "tmpnn_node.hip", "tmpnn_variants.hip",
+              "tmpnn_sample.hip")
 FILE_FLAGS = {f: ["-DTM_GELU_NAN3=1"] for f in NAN3_FILES}
 
 

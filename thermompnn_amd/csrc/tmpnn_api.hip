@@ -837,3 +837,56 @@ extern "C" int tmpnn_decode_ordered(const tmpnn_weights_t *w, const void *ctx, s
     return decode_rows("decode_ordered", true, w, ctx, ctx_bytes, S_var, rank, V, mask, T, ddg, hidden_opt, log_probs_opt, status_opt,
                        workspace, workspace_bytes, stream);
 }
+
+// ---- autoregressive sampling over one encoded backbone -------------------------------------------------
+// 3 N T table rows of 128 floats are addressed inside the chain kernel; bounded like ORD_ROWS_MAX bounds the ordered decode's table
+static const int64_t SAMPLE_ROWS_MAX = ((int64_t)1 << 24) - 1;
+
+extern "C" size_t tmpnn_sample_workspace_bytes(int64_t T, int64_t N) {
+    if (T < 0 || N < 0 || T > T_MAX || (N > 0 && T > SAMPLE_ROWS_MAX / 3 / N)) return 0;
+    const size_t R = (size_t)T * (size_t)N;
+    return 2 * align256((size_t)T * 256 * 4) + align256(3 * R * TMPNN_HID * 4) + align256(R * 4) + 256;
+}
+
+extern "C" int tmpnn_sample(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const float *mask, int64_t T, int64_t N,
+                            const int32_t *order, const int32_t *S_fixed, const float *free_, const float *u, float inv_temperature,
+                            const float *bias_opt, const float *allowed_opt, int32_t *S_out, float *probs_opt, int32_t *status_opt,
+                            void *workspace, size_t workspace_bytes, tmpnn_stream_t stream) {
+    const char *what = "sample";
+    REQUIRE(w, "%s: null weight handle", what);
+    REQUIRE(T >= 0 && T <= T_MAX && N >= 0, "%s: bad sizes (T=%lld, N=%lld)", what, (long long)T, (long long)N);
+    if (T == 0 || N == 0) return TMPNN_OK;            // nothing to sample (pointers may be null)
+    if (T > SAMPLE_ROWS_MAX / 3 / N)
+        return tm_set_error(TMPNN_E_UNSUPPORTED, "%s: 3 * N * T = 3 * %lld * %lld rows exceed %lld (sample the chains in chunks)", what,
+                            (long long)N, (long long)T, (long long)SAMPLE_ROWS_MAX);
+    REQUIRE(mask && order && S_fixed && free_ && u && S_out, "%s: null input pointer", what);
+    REQUIRE(inv_temperature > 0.f && inv_temperature <= 3.0e38f, "%s: inv_temperature must be positive and finite", what);
+    EncCtx c;
+    TRY(carve_ctx(what, const_cast<void *>(ctx), ctx_bytes, T, &c));
+    const size_t need = tmpnn_sample_workspace_bytes(T, N);
+    uintptr_t base = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
+    if (!workspace || workspace_bytes < need)
+        return tm_set_error(TMPNN_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
+    Carver cv{(char *)base, workspace_bytes - (base - (uintptr_t)workspace)};
+    float *Penc1 = (float *)cv.take((size_t)T * 256 * 4);
+    float *Penc2 = (float *)cv.take((size_t)T * 256 * 4);
+    float *tab = (float *)cv.take((size_t)3 * N * T * TMPNN_HID * 4);
+    int32_t *rank = (int32_t *)cv.take((size_t)N * T * 4);
+    if (!Penc1 || !Penc2 || !tab || !rank)
+        return tm_set_error(TMPNN_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
+    // (the handle is read only now: every check above works on the arguments alone)
+    if (w->mode == TM_MM_FP32)
+        return tm_set_error(TMPNN_E_UNSUPPORTED, "%s: the chain kernel has no fp32 form; create the handle with precision \"bf16x3\" (or \"f16x2\")", what);
+    hipStream_t st = (hipStream_t)stream;
+    if (status_opt && hipMemsetAsync(status_opt, 0, 4, st) != hipSuccess) return tm_check_launch("sample: status memset");
+    // residue -> step, scattered from `order` by the chain kernel's prologue; "not decoded" everywhere else
+    if (hipMemsetAsync(rank, 0x7f, (size_t)N * T * 4, st) != hipSuccess) return tm_check_launch("sample: rank memset");
+    {   // the later layers' projections of the ENCODER state (layer 0's is the ctx's P0), as the ordered decode makes them
+        const NodeProj p1 = dec_msg_proj(w, 1, Penc1, nullptr), p2 = dec_msg_proj(w, 2, Penc2, nullptr);
+        TRY(launch_node_proj(c.hV, p1, T, st));
+        TRY(launch_node_proj(c.hV, p2, T, st));
+    }
+    const float *Penc[3] = {c.P0, Penc1, Penc2};
+    return launch_sample_chains(w, c.hE, c.E_idx, c.hV, c.P0, Penc, mask, T, N, order, S_fixed, free_, u, inv_temperature, bias_opt,
+                                allowed_opt, S_out, probs_opt, status_opt, tab, rank, st);
+}

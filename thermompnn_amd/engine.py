@@ -447,6 +447,79 @@ class Engine:
             check(self.lib.tmpnn_status_error(st), f"tmpnn_{what}")
         return res
 
+    # -- autoregressive sampling over one backbone ----------------------------------------------------
+    def sample(self, enc: "EncodedBackbone", order, S_fixed, free, u, temperature: float = 1.0, bias=None, allowed=None,
+               max_rows: Optional[int] = None, check_status: bool = True):
+        """N chains sampled autoregressively over an encoded batch in one launch per chunk (tmpnn_sample): ``order`` [N,T] (a
+        permutation of 0..T-1 per chain, order[n,s] is decoded at step s), ``S_fixed`` [N,T] letters kept where ``free`` [N,T] is 0
+        or the mask is 0, ``u`` [N,T] uniforms in [0,1) indexed by RESIDUE, ``bias`` / ``allowed`` [T,21] or None ->
+        dict(S [N,T] int32, probs [N,T,21]); probs = softmax(logits / temperature + bias) (times allowed, renormalised) on free
+        positions and exactly 0 elsewhere, and the letter is the smallest a whose fp32 running sum of probs exceeds u * total.
+        N is sampled in chunks of at most ``max_rows`` rows (N * T; default 2**18) — a chain's result does not depend on the chunking.
+        Range contract as ``decode_variants``: a non-finite result of an f16x2 context re-encodes the backbone and reruns the whole
+        call at ``retry_precision`` with a warning, or raises TmpnnRangeError."""
+        T, dev = enc.T, self.device
+        O, S0 = self._i32(order), self._i32(S_fixed)
+        Fr, U = self._f32(free), self._f32(u)
+        for name, t in (("order", O), ("S_fixed", S0), ("free", Fr), ("u", U)):
+            if t.dim() != 2 or t.shape[1] != T or t.shape[0] != O.shape[0]:
+                raise TmpnnError(f"sample: {name} must be [N, {T}] like order, got {tuple(t.shape)}")
+        if not float(temperature) > 0.0 or not np.isfinite(float(temperature)):
+            raise TmpnnError(f"sample: temperature must be positive and finite, got {temperature!r}")
+        B = A = None
+        if bias is not None:
+            B = self._f32(bias)
+            if tuple(B.shape) != (T, VOCAB):
+                raise TmpnnError(f"sample: bias must be [{T}, {VOCAB}], got {tuple(B.shape)}")
+        if allowed is not None:
+            A = self._f32(allowed)
+            if tuple(A.shape) != (T, VOCAB):
+                raise TmpnnError(f"sample: allowed must be [{T}, {VOCAB}], got {tuple(A.shape)}")
+        N = O.shape[0]
+        res = {"S": torch.empty((N, T), dtype=torch.int32, device=dev), "probs": torch.empty((N, T, VOCAB), dtype=torch.float32, device=dev)}
+        if N == 0 or T == 0:
+            return res
+        _need_cuda(enc.ctx)
+        # every row of `order` a permutation (one device sort), every letter in range: ONE read-back of both verdicts
+        steps = torch.arange(T, dtype=torch.int32, device=dev)
+        ok = torch.stack([(torch.sort(O, dim=1).values == steps).all(), ((S0 >= 0) & (S0 < VOCAB)).all()]).tolist()
+        if not ok[0]:
+            raise TmpnnError(f"sample: every row of order must be a permutation of 0..{T - 1}")
+        if not ok[1]:
+            raise TmpnnError(f"sample: residue indices must lie in [0, {VOCAB})")
+        rows = int(max_rows) if max_rows is not None else 1 << 18
+        per = max(1, rows // T)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)     # per call: OR of the chunks' words
+        need = self.lib.tmpnn_sample_workspace_bytes(T, min(per, N))
+        if need == 0:
+            raise TmpnnError(f"sample: {min(per, N)} chains of {T} residues exceed one launch's table; lower max_rows")
+
+        def run(e: "EncodedBackbone") -> int:
+            w = self.weights_for(e.precision)
+            ws = self._workspace(need)
+            status.zero_()
+            for n0 in range(0, N, per):
+                n1 = min(N, n0 + per)
+                check(self.lib.tmpnn_sample(w.handle, _ptr(e.ctx), e.ctx.numel(), _ptr(e.mask), T, n1 - n0, _ptr(O[n0:n1]), _ptr(S0[n0:n1]),
+                                            _ptr(Fr[n0:n1]), _ptr(U[n0:n1]), 1.0 / float(temperature), _ptr(B), _ptr(A),
+                                            _ptr(res["S"][n0:n1]), _ptr(res["probs"][n0:n1]), _ptr(self._status), _ptr(ws), ws.numel(),
+                                            _stream()), "tmpnn_sample")
+                status.bitwise_or_(self._status)
+            return int(status.item()) if check_status else 0
+
+        st = run(enc)
+        if st & _lib.STATUS_RANGE:
+            retry, used = self.retry_precision, enc.precision
+            if used != "f16x2" or not retry or retry == used:
+                check(self.lib.tmpnn_status_error(st), f"tmpnn_sample[{used}]")
+            warnings.warn(f"ThermoMPNN HIP engine: non-finite result in {used} (an operand left the fp16 range); "
+                          f"rerunning this batch at precision {retry}", RuntimeWarning, stacklevel=2)
+            X, ridx, cenc, max_len = enc.inputs
+            st = run(self.encode(X, enc.mask, ridx, cenc, enc.offsets, max_len=max_len, precision=retry))
+        if st:
+            check(self.lib.tmpnn_status_error(st), "tmpnn_sample")
+        return res
+
     def capture_graph(self, X, S, mask, residue_idx, chain_enc, offsets, max_len: int, out: Optional[dict] = None, **want):
         """Capture ONE fused forward (its ~20 launches + the status memset) into a hipGraph: -> (graph, out). ``graph.replay()``
         reruns it on the captured tensors — refill X / S / ... in place for a new protein of the same length. The C-ABI

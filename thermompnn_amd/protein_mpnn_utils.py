@@ -2,8 +2,9 @@
 
 Same names, signatures and return conventions; the arithmetic runs in libtmpnn.so
 (hand-written HIP for gfx950) — this module only packs arguments. Out-of-scope symbols of the
-reference file (CA_ProteinFeatures, sample/tied_sample, StructureDataset*, loss_*) are not provided.
+reference file (CA_ProteinFeatures, tied_sample, StructureDataset*, loss_*) are not provided.
 ``ProteinMPNN.conditional_probs`` / ``unconditional_probs`` (:1496-1587) are: the masked decoder runs in tmpnn_decode_ordered.
+``ProteinMPNN.sample`` (:1279-1383) is: whole chains are sampled autoregressively inside one launch (tmpnn_sample).
 """
 from __future__ import annotations
 
@@ -15,13 +16,35 @@ from .engine import Engine, cat_neighbors_nodes, gather_edges, gather_nodes  # n
 from .pdb_io import alt_parse_PDB, featurize, tied_featurize  # noqa: F401  (API surface)
 
 
+def decoding_order(order_mask, randn) -> torch.Tensor:
+    """The reference's ``decoding_order = argsort((order_mask + 0.0001) * abs(randn))`` (protein_mpnn_utils.py:1297, :1533), with
+    that expression: decoding_order[..., s] is the residue decoded at step s."""
+    return torch.argsort((order_mask + 0.0001) * (torch.abs(randn)))
+
+
 def decoding_ranks(order_mask, randn) -> torch.Tensor:
-    """int32 ranks [..., L] for ``Engine.decode_ordered``: the inverse permutation of the reference's
-    ``decoding_order = argsort((order_mask + 0.0001) * abs(randn))`` (protein_mpnn_utils.py:1533), computed with that expression —
+    """int32 ranks [..., L] for ``Engine.decode_ordered``: the inverse permutation of ``decoding_order`` —
     rank[..., p] is the step at which residue p is decoded, and a residue sees the neighbours of lower rank."""
-    order = torch.argsort((order_mask + 0.0001) * (torch.abs(randn)))
+    order = decoding_order(order_mask, randn)
     steps = torch.arange(order.shape[-1], device=order.device).expand_as(order)
     return torch.empty_like(order).scatter_(-1, order, steps).to(torch.int32)
+
+
+def pack_sample_args(randn, chain_mask, mask, temperature, omit_AAs_np, bias_AAs_np, chain_M_pos, omit_AA_mask, bias_by_res):
+    """Host-side packing of ``ProteinMPNN.sample``'s arguments for ``Engine.sample`` (no device needed), with the reference's
+    expressions (:1296-1298, :1351-1353, :1372) -> dict(decoding_order [B,L] int64, free [B,L], bias [B,L,21],
+    allowed [B,L,21] or None). free = chain_mask * chain_M_pos (the kernel multiplies by the mask); the softmax argument is
+    logits / temperature + bias, bias = (bias_AAs_np + bias_by_res) / temperature - 1e8 * omit_AAs_np; allowed = 1 - omit_AA_mask."""
+    f = lambda x: torch.as_tensor(x).to(dtype=torch.float32)
+    chain_mask, mask = f(chain_mask), f(mask).to(chain_mask.device if isinstance(chain_mask, torch.Tensor) else "cpu")
+    free = chain_mask * f(chain_M_pos).to(chain_mask.device)
+    order = decoding_order(free * mask, f(randn).to(chain_mask.device))
+    B, L = free.shape
+    by_res = f(bias_by_res).to(chain_mask.device) if bias_by_res is not None else torch.zeros((B, L, 21), device=chain_mask.device)
+    bias = (f(bias_AAs_np).to(chain_mask.device)[None, None, :] + by_res) / float(temperature) \
+        - 1e8 * f(omit_AAs_np).to(chain_mask.device)[None, None, :]
+    allowed = None if omit_AA_mask is None else 1.0 - f(omit_AA_mask).to(chain_mask.device)
+    return {"decoding_order": order, "free": free, "bias": bias.expand(B, L, 21).contiguous(), "allowed": allowed}
 
 
 def _register_tree(root: nn.Module, shapes) -> None:
@@ -150,3 +173,54 @@ class ProteinMPNN(_EngineOwner):
             enc = self._encode_padded(eng, X, mask, residue_idx, chain_encoding_all)
             zeros = torch.zeros((1, B * L), dtype=torch.int32)
             return eng.decode_ordered(enc, zeros, zeros)["log_probs"].view(B, L, 21)
+
+    def sample(self, X, randn, S_true, chain_mask, chain_encoding_all, residue_idx, mask=None, temperature=1.0,
+               omit_AAs_np=None, bias_AAs_np=None, chain_M_pos=None, omit_AA_mask=None, pssm_coef=None, pssm_bias=None,
+               pssm_multi=None, pssm_log_odds_flag=None, pssm_log_odds_mask=None, pssm_bias_flag=None,
+               bias_by_res=None, generator=None, uniforms=None):
+        """-> {"S" [B,L] int64, "probs" [B,L,21], "decoding_order" [B,L]} (reference :1279-1383): every batch member is one chain
+        sampled autoregressively on the device — residue by residue in the reference's decoding order, each letter fed to the
+        residues decoded after it — inside one launch (``Engine.sample``). When all members share ``X / mask / residue_idx /
+        chain_encoding_all`` and the per-residue tables (the usual batch of copies of one structure) the structure is encoded once
+        and the B members run as B chains; otherwise each member gets its own encode.
+
+        Random stream: one uniform per (member, residue) from ``torch.rand(..., generator=generator)`` on the device picks the
+        letter by inverse CDF (the smallest a whose running sum of probs exceeds u * total). The DISTRIBUTION is the
+        reference's; the stream is not ``torch.multinomial``'s, so equal seeds do not give the reference's sequences.
+        ``uniforms`` [B,L] (indexed by residue) replaces the draw, e.g. to replay recorded ones.
+        pssm_bias_flag / pssm_log_odds_flag are not supported (NotImplementedError); ``tied_sample`` is not provided."""
+        if pssm_bias_flag or pssm_log_odds_flag:
+            raise NotImplementedError("sample: pssm_bias_flag / pssm_log_odds_flag are outside this port")
+        if not float(temperature) > 0.0:
+            raise ValueError(f"sample: temperature must be positive, got {temperature!r}")
+        eng = self.engine()
+        dev = eng.device
+        B, L = X.shape[0], X.shape[1]
+        if mask is None:
+            raise ValueError("sample: mask is required")
+        if chain_M_pos is None:
+            chain_M_pos = torch.ones_like(chain_mask)
+        zeros21 = torch.zeros(21)
+        pk = pack_sample_args(randn.to(dev), chain_mask.to(dev), mask.to(dev), temperature,
+                              zeros21 if omit_AAs_np is None else omit_AAs_np, zeros21 if bias_AAs_np is None else bias_AAs_np,
+                              chain_M_pos.to(dev), omit_AA_mask, bias_by_res)
+        order, free, bias, allowed = pk["decoding_order"], pk["free"], pk["bias"], pk["allowed"]
+        S_true = S_true.to(dev)
+        if S_true.numel() and (int(S_true.min()) < 0 or int(S_true.max()) >= 21):
+            raise ValueError("sample: S_true must lie in [0, 21)")
+        with torch.cuda.device(dev):
+            if uniforms is None:
+                uniforms = torch.rand((B, L), device=dev, dtype=torch.float32, generator=generator)
+            u = torch.as_tensor(uniforms).to(device=dev, dtype=torch.float32).reshape(B, L)
+            same = lambda t: t is None or bool((t[1:] == t[:1]).all())
+            shared = B > 1 and all(same(t) for t in (X.to(dev), mask.to(dev), residue_idx.to(dev), chain_encoding_all.to(dev), bias, allowed))
+            groups = [slice(0, B)] if shared or B == 1 else [slice(b, b + 1) for b in range(B)]
+            S = torch.empty((B, L), dtype=torch.int64, device=dev)
+            probs = torch.empty((B, L, 21), dtype=torch.float32, device=dev)
+            for g in groups:
+                b = g.start
+                enc = self._encode_padded(eng, X[b:b + 1], mask[b:b + 1], residue_idx[b:b + 1], chain_encoding_all[b:b + 1])
+                r = eng.sample(enc, order[g], S_true[g], free[g], u[g], temperature=float(temperature), bias=bias[b],
+                               allowed=None if allowed is None else allowed[b])
+                S[g], probs[g] = r["S"].to(torch.int64), r["probs"]
+        return {"S": S, "probs": probs, "decoding_order": order}
