@@ -352,40 +352,36 @@ extern "C" void tmpnn_weights_destroy(tmpnn_weights_t *w) { delete w; }
 
 static const int64_t T_MAX = ((int64_t)1 << 31) / (TMPNN_KS * 4) - 1;   // int32 tile arithmetic inside kernels
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct Carver {
-    char *p; size_t left;
-    void *take(size_t bytes) {
-        bytes = align256(bytes);
-        if (bytes > left) return nullptr;
-        void *r = p; p += bytes; left -= bytes;
-        return r;
-    }
-};
-
-extern "C" size_t tmpnn_layer_workspace_bytes(int64_t T) {
-    if (T < 0) return 0;
-    return 2 * align256((size_t)T * 256 * 4) + align256((size_t)T * TMPNN_HID * 4) + align256((size_t)T * 4) + 256;
+// ---- layouts of the caller-owned buffers: one function each, run by the entry on the buffer and by *_bytes() without a base -------
+// A layout struct's members are carved in the order they are declared (a braced list is evaluated left to right); `bytes` comes last.
+// *_bytes() adds 256 bytes of slack per alignment of the caller's base (tmpnn_workspace_bytes has carried two since the layer part
+// was split off).
+static LayerWs layer_ws(Carver &c, int64_t T) {             // (by reference: the forward's and the encoder's layouts go on behind it)
+    const size_t n = (size_t)T;
+    return LayerWs{c.take<float>(n * 256), c.take<float>(n * 256), c.take<float>(n * TMPNN_HID), c.take<float>(n), c.used};
 }
-extern "C" size_t tmpnn_workspace_bytes(int64_t T) {
-    if (T < 0) return 0;
-    return tmpnn_layer_workspace_bytes(T) + 2 * align256((size_t)T * TMPNN_KS * 4) +
-           align256((size_t)T * TMPNN_KS * TMPNN_HID * 4) + 4 * align256((size_t)T * TMPNN_HID * 4) + 256;
+struct FwdWs { LayerWs l; int32_t *E_idx; float *D_nb, *hE, *hV[4]; size_t bytes; };       // tmpnn_ssm_forward
+static FwdWs fwd_ws(Carver c, int64_t T) {
+    const size_t n = (size_t)T, nh = n * TMPNN_HID;
+    return FwdWs{layer_ws(c, T), c.take<int32_t>(n * TMPNN_KS), c.take<float>(n * TMPNN_KS), c.take<float>(n * TMPNN_KS * TMPNN_HID),
+                 {c.take<float>(nh), c.take<float>(nh), c.take<float>(nh), c.take<float>(nh)}, c.used};
 }
+struct EncWs { LayerWs l; float *D_nb; size_t bytes; };                                     // tmpnn_encode
+static EncWs enc_ws(Carver c, int64_t T) { return EncWs{layer_ws(c, T), c.take<float>((size_t)T * TMPNN_KS), c.used}; }
 
-static int carve_layer_ws(void *workspace, size_t bytes, int64_t T, LayerWs *ws, Carver *rest = nullptr) {
-    uintptr_t base = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    size_t skip = base - (uintptr_t)workspace;
-    if (!workspace || skip > bytes) return tm_set_error(TMPNN_E_WORKSPACE, "workspace missing or too small");
-    Carver c{(char *)base, bytes - skip};
-    ws->P = (float *)c.take((size_t)T * 256 * 4);
-    ws->P2 = (float *)c.take((size_t)T * 256 * 4);
-    ws->Ssum = (float *)c.take((size_t)T * TMPNN_HID * 4);
-    ws->cnt = (float *)c.take((size_t)T * 4);
-    if (!ws->P || !ws->P2 || !ws->Ssum || !ws->cnt) return tm_set_error(TMPNN_E_WORKSPACE, "workspace too small for T=%lld", (long long)T);
-    if (rest) *rest = c;
+extern "C" size_t tmpnn_layer_workspace_bytes(int64_t T) { Carver c; return T < 0 ? 0 : layer_ws(c, T).bytes + 256; }
+extern "C" size_t tmpnn_workspace_bytes(int64_t T) { return T < 0 ? 0 : fwd_ws(Carver(), T).bytes + 512; }
+
+// The entries that take whatever the carve fits (layers, ssm_forward, encode) carve from the aligned base and check the layer part here.
+static int layer_ws_fits(void *workspace, size_t bytes, const LayerWs &ws, int64_t T) {
+    if (!workspace || Carver(workspace, true).used > bytes) return tm_set_error(TMPNN_E_WORKSPACE, "workspace missing or too small");
+    if (ws.bytes > bytes) return tm_set_error(TMPNN_E_WORKSPACE, "workspace too small for T=%lld", (long long)T);
     return TMPNN_OK;
+}
+static int carve_layer_ws(void *workspace, size_t bytes, int64_t T, LayerWs *ws) {
+    Carver c(workspace, true);
+    *ws = layer_ws(c, T);
+    return layer_ws_fits(workspace, bytes, *ws, T);
 }
 
 // Which node projection the NEXT consumer of h_V needs (fused into node_update): encoder layer l+1's message
@@ -613,11 +609,15 @@ static int head_generic_dims_ok(int n_final, int n_layers, const int32_t *dims) 
     return 1;
 }
 
-extern "C" size_t tmpnn_head_generic_workspace_bytes(int64_t T, int n_final, int n_layers, const int32_t *dims) {
-    if (T < 0 || !head_generic_dims_ok(n_final, n_layers, dims)) return 0;
+struct HeadWs { float *buf0, *buf1; size_t bytes; };          // two [T, widest layer] activations, ping-pong
+static HeadWs head_ws(Carver c, int64_t T, int n_layers, const int32_t *dims) {
     int widest = dims[0];
     for (int l = 1; l <= n_layers; ++l) widest = dims[l] > widest ? dims[l] : widest;
-    return 2 * align256((size_t)T * widest * sizeof(float));
+    return HeadWs{c.take<float>((size_t)T * widest), c.take<float>((size_t)T * widest), c.used};
+}
+extern "C" size_t tmpnn_head_generic_workspace_bytes(int64_t T, int n_final, int n_layers, const int32_t *dims) {
+    if (T < 0 || !head_generic_dims_ok(n_final, n_layers, dims)) return 0;
+    return head_ws(Carver(), T, n_layers, dims).bytes;        // no slack: the entry uses the caller's base as it is
 }
 
 extern "C" int tmpnn_ddg_head_generic(const float *const *hidden, int n_final, const float *Ws, const int32_t *S, int64_t T,
@@ -636,9 +636,9 @@ extern "C" int tmpnn_ddg_head_generic(const float *const *hidden, int n_final, c
     const size_t need = tmpnn_head_generic_workspace_bytes(T, n_final, n_layers, dims);
     if (!workspace || workspace_bytes < need)
         return tm_set_error(TMPNN_E_WORKSPACE, "ddg_head_generic: workspace %zu < %zu bytes", workspace_bytes, need);
-    float *buf0 = (float *)workspace, *buf1 = (float *)((char *)workspace + need / 2);
+    const HeadWs h = head_ws(Carver(workspace, false), T, n_layers, dims);
     return launch_head_generic(hidden, n_final, Ws, S, T, conv_w, conv_b, n_layers, mlp_w, mlp_b, dims, ddg_w, ddg_b, ddg, z_opt,
-                               buf0, buf1, status_opt, (hipStream_t)stream);
+                               h.buf0, h.buf1, status_opt, (hipStream_t)stream);
 }
 
 extern "C" int tmpnn_ssm_forward(const tmpnn_weights_t *w, const float *X, const int32_t *S, const float *mask,
@@ -658,22 +658,19 @@ extern "C" int tmpnn_ssm_forward(const tmpnn_weights_t *w, const float *X, const
     hipStream_t st = (hipStream_t)stream;
     // (status_opt: the k-NN kernel zeroes the word, and the LAST kernel flags what the k-NN kernel found, see KnnInit / HeadArgs)
 
-    LayerWs ws;
-    Carver c{nullptr, 0};
-    TRY(carve_layer_ws(workspace, workspace_bytes, T, &ws, &c));
-    int32_t *E_idx = (int32_t *)c.take((size_t)T * TMPNN_KS * 4);
-    float *D_nb = (float *)c.take((size_t)T * TMPNN_KS * 4);
-    float *hE = (float *)c.take((size_t)T * TMPNN_KS * TMPNN_HID * 4);
-    float *hV[4];
-    for (int i = 0; i < 4; ++i) hV[i] = (float *)c.take((size_t)T * TMPNN_HID * 4);
-    if (!E_idx || !D_nb || !hE || !hV[3])
+    FwdWs f = fwd_ws(Carver(workspace, true), T);
+    TRY(layer_ws_fits(workspace, workspace_bytes, f.l, T));
+    if (f.bytes > workspace_bytes)
         return tm_set_error(TMPNN_E_WORKSPACE, "ssm_forward: workspace %zu < %zu bytes", workspace_bytes, tmpnn_workspace_bytes(T));
-    if (E_idx_opt) E_idx = E_idx_opt;
-    if (hidden_opt) for (int l = 0; l < 3; ++l) hV[1 + l] = hidden_opt + (size_t)l * T * TMPNN_HID;
+    if (E_idx_opt) f.E_idx = E_idx_opt;
+    if (hidden_opt) for (int l = 0; l < 3; ++l) f.hV[1 + l] = hidden_opt + (size_t)l * T * TMPNN_HID;
+    const LayerWs &ws = f.l;
+    int32_t *const E_idx = f.E_idx;
+    float *const *hV = f.hV;
 
     bool dec_msg0_done = false;      // small launches: decoder message pass 0 ran inside the last edge update's launch
     bool head_done = false;          // the ddG head ran inside the last node update's launch
-    TRY(run_encoder(w, X, mask, residue_idx, chain_enc, offsets, n_proteins, T, max_len, K, ws, E_idx, D_nb, hE, hV[0], S, ws.P,
+    TRY(run_encoder(w, X, mask, residue_idx, chain_enc, offsets, n_proteins, T, max_len, K, ws, E_idx, f.D_nb, f.hE, hV[0], S, ws.P,
                     status_opt, &dec_msg0_done, st));
     for (int l = 0; l < 3; ++l) {
         const NodeProj next = dec_msg_proj(w, l < 2 ? l + 1 : 2, ws.P, S);
@@ -681,7 +678,7 @@ extern "C" int tmpnn_ssm_forward(const tmpnn_weights_t *w, const float *X, const
         HeadArgs ha;
         const bool with_head = dec_msg0_done && l == 2 && ddg && node_head_fusable(w->mode, T);
         if (with_head) TRY(tm_head_args(ha, w, hV[3], hV[2], S, T, ddg, nullptr, status_opt, E_idx));
-        TRY(run_dec_layer(w, l, hV[l], hV[l + 1], hE, E_idx, S, mask, T, ws, true, dec_msg0_done && l == 0, l < 2 ? &next : nullptr, st,
+        TRY(run_dec_layer(w, l, hV[l], hV[l + 1], f.hE, E_idx, S, mask, T, ws, true, dec_msg0_done && l == 0, l < 2 ? &next : nullptr, st,
                           with_head ? &ha : nullptr, with_head ? &head_done : nullptr));
     }
     if (ddg && !head_done) TRY(launch_head(w, hV[3], hV[2], S, T, ddg, nullptr, status_opt, st, E_idx));
@@ -694,32 +691,21 @@ extern "C" int tmpnn_ssm_forward(const tmpnn_weights_t *w, const float *X, const
 
 // ---- many sequence variants over one encoded backbone ------------------------------------------------
 // The encoded backbone in the caller's ctx buffer: what the decoder reads and no sequence changes.
-struct EncCtx { int32_t *E_idx; float *hE, *hV, *P0; };      // [T,48], [T,48,128], [T,128], [T,256] (decoder layer 0's projection, no sequence term)
+struct EncCtx { int32_t *E_idx; float *hE, *hV, *P0; size_t bytes; };      // [T,48], [T,48,128], [T,128], [T,256] (decoder layer 0's projection, no sequence term)
 
-extern "C" size_t tmpnn_encode_bytes(int64_t T) {
-    if (T < 0) return 0;
-    return align256((size_t)T * TMPNN_KS * 4) + align256((size_t)T * TMPNN_KS * TMPNN_HID * 4) + align256((size_t)T * TMPNN_HID * 4) +
-           align256((size_t)T * 256 * 4);
+static EncCtx enc_ctx(Carver c, int64_t T) {               // (this order is the ctx's format: EncodedBackbone reads E_idx at offset 0)
+    const size_t n = (size_t)T;
+    return EncCtx{c.take<int32_t>(n * TMPNN_KS), c.take<float>(n * TMPNN_KS * TMPNN_HID), c.take<float>(n * TMPNN_HID), c.take<float>(n * 256),
+                  c.used};
 }
-extern "C" size_t tmpnn_encode_workspace_bytes(int64_t T) {
-    if (T < 0) return 0;
-    return tmpnn_layer_workspace_bytes(T) + align256((size_t)T * TMPNN_KS * 4);
-}
-extern "C" size_t tmpnn_decode_variants_workspace_bytes(int64_t T, int64_t V) {
-    if (T < 0 || V < 0 || (V > 0 && T > T_MAX / V)) return 0;
-    const size_t R = (size_t)T * (size_t)V;
-    return align256(R * 256 * 4) + 5 * align256(R * TMPNN_HID * 4) + 2 * align256(R * 4) + 256;
-}
+extern "C" size_t tmpnn_encode_bytes(int64_t T) { return T < 0 ? 0 : enc_ctx(Carver(), T).bytes; }     // no slack: a ctx is aligned
+extern "C" size_t tmpnn_encode_workspace_bytes(int64_t T) { return T < 0 ? 0 : enc_ws(Carver(), T).bytes + 256; }
 
 static int carve_ctx(const char *what, void *ctx, size_t ctx_bytes, int64_t T, EncCtx *c) {
     if (!ctx || ((uintptr_t)ctx & 255) != 0) return tm_set_error(TMPNN_E_INVALID, "%s: ctx is null or not 256-byte aligned", what);
     if (ctx_bytes < tmpnn_encode_bytes(T))
         return tm_set_error(TMPNN_E_WORKSPACE, "%s: ctx %zu < %zu bytes", what, ctx_bytes, tmpnn_encode_bytes(T));
-    Carver cv{(char *)ctx, ctx_bytes};
-    c->E_idx = (int32_t *)cv.take((size_t)T * TMPNN_KS * 4);
-    c->hE = (float *)cv.take((size_t)T * TMPNN_KS * TMPNN_HID * 4);
-    c->hV = (float *)cv.take((size_t)T * TMPNN_HID * 4);
-    c->P0 = (float *)cv.take((size_t)T * 256 * 4);
+    *c = enc_ctx(Carver(ctx, false), T);
     return TMPNN_OK;
 }
 
@@ -736,15 +722,13 @@ extern "C" int tmpnn_encode(const tmpnn_weights_t *w, const float *X, const floa
     if (max_len > 8192) return tm_set_error(TMPNN_E_UNSUPPORTED, "encode: max_len %d > 8192", max_len);
     EncCtx c;
     TRY(carve_ctx("encode", ctx, ctx_bytes, T, &c));
-    LayerWs ws;
-    Carver rest{nullptr, 0};
-    TRY(carve_layer_ws(workspace, workspace_bytes, T, &ws, &rest));
-    float *D_nb = (float *)rest.take((size_t)T * TMPNN_KS * 4);
-    if (!D_nb)
+    const EncWs e = enc_ws(Carver(workspace, true), T);
+    TRY(layer_ws_fits(workspace, workspace_bytes, e.l, T));
+    if (e.bytes > workspace_bytes)
         return tm_set_error(TMPNN_E_WORKSPACE, "encode: workspace %zu < %zu bytes", workspace_bytes, tmpnn_encode_workspace_bytes(T));
     hipStream_t st = (hipStream_t)stream;
     bool unused = false;
-    TRY(run_encoder(w, X, mask, residue_idx, chain_enc, offsets, n_proteins, T, max_len, K, ws, c.E_idx, D_nb, c.hE, c.hV, nullptr,
+    TRY(run_encoder(w, X, mask, residue_idx, chain_enc, offsets, n_proteins, T, max_len, K, e.l, c.E_idx, e.D_nb, c.hE, c.hV, nullptr,
                     c.P0, status_opt, &unused, st));
     // the encoder state is this call's output: a value that left the f16x2 range upstream has reached it, and rows of an over-long
     // protein have an empty neighbour list (the MAXLEN probe of the fused forward's last kernel)
@@ -755,11 +739,22 @@ extern "C" int tmpnn_encode(const tmpnn_weights_t *w, const float *X, const floa
 // (V + 1) T rows of 256 floats are addressed with 32-bit offsets inside the order-masked message kernel
 static const int64_t ORD_ROWS_MAX = ((int64_t)1 << 24) - 1;
 
+// Rows r = v T + t. Ordered: P is [V + 1, T, 256] (slot V = Penc_l), and the visibility words and the fp32 form's remapped list exist.
+struct DecWs { float *P, *Ssum, *cnt, *mask_rep, *hV[4]; uint64_t *vis; int32_t *remap; size_t bytes; };
+static DecWs dec_ws(Carver c, int64_t T, int64_t V, bool ordered) {
+    const size_t R = (size_t)T * (size_t)V, rh = R * TMPNN_HID;
+    return DecWs{c.take<float>((R + (ordered ? (size_t)T : 0)) * 256), c.take<float>(rh), c.take<float>(R), c.take<float>(R),
+                 {c.take<float>(rh), c.take<float>(rh), c.take<float>(rh), c.take<float>(rh)},
+                 ordered ? c.take<uint64_t>(R) : nullptr, ordered ? c.take<int32_t>((size_t)T * TMPNN_KS) : nullptr, c.used};
+}
+static size_t dec_ws_bytes(int64_t T, int64_t V, bool ordered) { return dec_ws(Carver(), T, V, ordered).bytes + 256; }
+extern "C" size_t tmpnn_decode_variants_workspace_bytes(int64_t T, int64_t V) {
+    if (T < 0 || V < 0 || (V > 0 && T > T_MAX / V)) return 0;
+    return dec_ws_bytes(T, V, false);
+}
 extern "C" size_t tmpnn_decode_ordered_workspace_bytes(int64_t T, int64_t V) {
     if (T < 0 || V < 0 || (V > 0 && (T > T_MAX / V || T > ORD_ROWS_MAX / (V + 1)))) return 0;
-    const size_t R = (size_t)T * (size_t)V;
-    return align256((R + (size_t)T) * 256 * 4) + 5 * align256(R * TMPNN_HID * 4) + 2 * align256(R * 4) + align256(R * 8) +
-           align256((size_t)T * TMPNN_KS * 4) + 256;
+    return dec_ws_bytes(T, V, true);
 }
 
 // The body of tmpnn_decode_variants (ordered == false, rank unused) and tmpnn_decode_ordered (`what` names the entry in messages).
@@ -785,30 +780,20 @@ static int decode_rows(const char *what, bool ordered, const tmpnn_weights_t *w,
     EncCtx c;
     TRY(carve_ctx(what, const_cast<void *>(ctx), ctx_bytes, T, &c));
     const int64_t R = V * T;
-    const size_t need = ordered ? tmpnn_decode_ordered_workspace_bytes(T, V) : tmpnn_decode_variants_workspace_bytes(T, V);
-    uintptr_t base = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
+    const size_t need = dec_ws_bytes(T, V, ordered);
     if (!workspace || workspace_bytes < need)
         return tm_set_error(TMPNN_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
-    Carver cv{(char *)base, workspace_bytes - (base - (uintptr_t)workspace)};
-    float *P = (float *)cv.take((size_t)(R + (ordered ? T : 0)) * 256 * 4);   // ordered: [V + 1, T, 256], slot V = Penc_l
-    float *Ssum = (float *)cv.take((size_t)R * TMPNN_HID * 4);
-    float *cnt = (float *)cv.take((size_t)R * 4);
-    float *mask_rep = (float *)cv.take((size_t)R * 4);
-    float *hV[4];
-    for (int i = 0; i < 4; ++i) hV[i] = (float *)cv.take((size_t)R * TMPNN_HID * 4);
-    void *vis = ordered ? cv.take((size_t)R * 8) : nullptr;                   // visibility words, and the fp32 form's remapped list
-    int32_t *remap = ordered ? (int32_t *)cv.take((size_t)T * TMPNN_KS * 4) : nullptr;
-    if (!P || !Ssum || !cnt || !mask_rep || !hV[3] || (ordered && (!vis || !remap)))
-        return tm_set_error(TMPNN_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
+    const DecWs d = dec_ws(Carver(workspace, true), T, V, ordered);
     hipStream_t st = (hipStream_t)stream;
+    float *const P = d.P, *const Ssum = d.Ssum, *const cnt = d.cnt, *const mask_rep = d.mask_rep, *const *hV = d.hV;
     float *Penc = P + (size_t)R * 256;
     TRY(launch_variant_expand(c.hV, c.P0, mask, w->seq_table[0], S_var, T, V, hV[0], P, mask_rep, status_opt, st));
     if (ordered) {
         TRY(launch_variant_penc0(c.P0, T, Penc, st));               // Penc_0 = P0 (its neighbour half is W1c_0 h_V_enc)
-        TRY(launch_variant_vis(rank, c.E_idx, T, V, vis, st));
+        TRY(launch_variant_vis(rank, c.E_idx, T, V, d.vis, st));
     }
     for (int l = 0; l < 3; ++l) {
-        TRY(launch_variant_msg(w->mode, w->dec[l].msg, P, c.hE, c.E_idx, mask, T, V, Ssum, cnt, st, vis, remap));
+        TRY(launch_variant_msg(w->mode, w->dec[l].msg, P, c.hE, c.E_idx, mask, T, V, Ssum, cnt, st, d.vis, d.remap));
         const NodeProj next = dec_msg_proj(w, l < 2 ? l + 1 : 2, P, S_var);
         TRY(launch_node_update(w->mode, w->dec[l].node, hV[l], Ssum, cnt, mask_rep, R, hV[l + 1], l < 2 ? &next : nullptr, nullptr, st));
         if (ordered && l < 2) {                       // T rows, not V T: the next layer's projection of the ENCODER state
@@ -842,10 +827,14 @@ extern "C" int tmpnn_decode_ordered(const tmpnn_weights_t *w, const void *ctx, s
 // 3 N T table rows of 128 floats are addressed inside the chain kernel; bounded like ORD_ROWS_MAX bounds the ordered decode's table
 static const int64_t SAMPLE_ROWS_MAX = ((int64_t)1 << 24) - 1;
 
+struct SampleWs { float *Penc1, *Penc2, *tab; int32_t *rank; size_t bytes; };     // [T,256] x 2, [N,3,T,128], [N,T]
+static SampleWs sample_ws(Carver c, int64_t T, int64_t N) {
+    const size_t n = (size_t)T, R = n * (size_t)N;
+    return SampleWs{c.take<float>(n * 256), c.take<float>(n * 256), c.take<float>(3 * R * TMPNN_HID), c.take<int32_t>(R), c.used};
+}
 extern "C" size_t tmpnn_sample_workspace_bytes(int64_t T, int64_t N) {
     if (T < 0 || N < 0 || T > T_MAX || (N > 0 && T > SAMPLE_ROWS_MAX / 3 / N)) return 0;
-    const size_t R = (size_t)T * (size_t)N;
-    return 2 * align256((size_t)T * 256 * 4) + align256(3 * R * TMPNN_HID * 4) + align256(R * 4) + 256;
+    return sample_ws(Carver(), T, N).bytes + 256;
 }
 
 extern "C" int tmpnn_sample(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const float *mask, int64_t T, int64_t N,
@@ -864,29 +853,22 @@ extern "C" int tmpnn_sample(const tmpnn_weights_t *w, const void *ctx, size_t ct
     EncCtx c;
     TRY(carve_ctx(what, const_cast<void *>(ctx), ctx_bytes, T, &c));
     const size_t need = tmpnn_sample_workspace_bytes(T, N);
-    uintptr_t base = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
     if (!workspace || workspace_bytes < need)
         return tm_set_error(TMPNN_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
-    Carver cv{(char *)base, workspace_bytes - (base - (uintptr_t)workspace)};
-    float *Penc1 = (float *)cv.take((size_t)T * 256 * 4);
-    float *Penc2 = (float *)cv.take((size_t)T * 256 * 4);
-    float *tab = (float *)cv.take((size_t)3 * N * T * TMPNN_HID * 4);
-    int32_t *rank = (int32_t *)cv.take((size_t)N * T * 4);
-    if (!Penc1 || !Penc2 || !tab || !rank)
-        return tm_set_error(TMPNN_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
+    const SampleWs s = sample_ws(Carver(workspace, true), T, N);
     // (the handle is read only now: every check above works on the arguments alone)
     if (w->mode == TM_MM_FP32)
         return tm_set_error(TMPNN_E_UNSUPPORTED, "%s: the chain kernel has no fp32 form; create the handle with precision \"bf16x3\" (or \"f16x2\")", what);
     hipStream_t st = (hipStream_t)stream;
     if (status_opt && hipMemsetAsync(status_opt, 0, 4, st) != hipSuccess) return tm_check_launch("sample: status memset");
     // residue -> step, scattered from `order` by the chain kernel's prologue; "not decoded" everywhere else
-    if (hipMemsetAsync(rank, 0x7f, (size_t)N * T * 4, st) != hipSuccess) return tm_check_launch("sample: rank memset");
+    if (hipMemsetAsync(s.rank, 0x7f, (size_t)N * T * 4, st) != hipSuccess) return tm_check_launch("sample: rank memset");
     {   // the later layers' projections of the ENCODER state (layer 0's is the ctx's P0), as the ordered decode makes them
-        const NodeProj p1 = dec_msg_proj(w, 1, Penc1, nullptr), p2 = dec_msg_proj(w, 2, Penc2, nullptr);
+        const NodeProj p1 = dec_msg_proj(w, 1, s.Penc1, nullptr), p2 = dec_msg_proj(w, 2, s.Penc2, nullptr);
         TRY(launch_node_proj(c.hV, p1, T, st));
         TRY(launch_node_proj(c.hV, p2, T, st));
     }
-    const float *Penc[3] = {c.P0, Penc1, Penc2};
+    const float *Penc[3] = {c.P0, s.Penc1, s.Penc2};
     return launch_sample_chains(w, c.hE, c.E_idx, c.hV, c.P0, Penc, mask, T, N, order, S_fixed, free_, u, inv_temperature, bias_opt,
-                                allowed_opt, S_out, probs_opt, status_opt, tab, rank, st);
+                                allowed_opt, S_out, probs_opt, status_opt, s.tab, s.rank, st);
 }

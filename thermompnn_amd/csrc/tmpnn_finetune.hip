@@ -480,8 +480,6 @@ __global__ __launch_bounds__(TM_THREADS) void ft_csr_sort_kernel(const int32_t *
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
-static size_t ft_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 static int ft_dims_ok(int n_final, int n_layers, const int32_t *dims) {
     if (n_final < 0 || n_final > 3 || n_layers < 1 || n_layers > FT_MAX_LAYERS || !dims) return 0;
     if (dims[0] != FT_H * n_final + FT_H || dims[n_layers] != TMPNN_VOCAB) return 0;
@@ -556,13 +554,11 @@ struct FtWs {
 
 static FtWs ft_carve2(void *saved, void *scratch, bool split, int64_t L, int64_t M, int lightattn, int n_layers, const int32_t *dims) {
     FtWs w{};
-    size_t so = 0, co = 0;
-    auto take_s = [&](size_t nbytes) { void *r = saved ? (void *)((char *)saved + so) : nullptr; so += ft_align(nbytes); return r; };
-    auto take_c = [&](size_t nbytes) { void *r = scratch ? (void *)((char *)scratch + co) : nullptr; co += ft_align(nbytes); return r; };
-    auto f = [&](int64_t n) { return (float *)take_s((size_t)n * 4); };
-    auto i32 = [&](int64_t n) { return (int32_t *)take_s((size_t)n * 4); };
-    auto fc = [&](int64_t n) { return (float *)take_c((size_t)n * 4); };
-    auto ic = [&](int64_t n) { return (int32_t *)take_c((size_t)n * 4); };
+    Carver sv(saved, false), sc(scratch, false);       // (a null base measures; the entries compare with the byte counts first)
+    auto f = [&](int64_t n) { return sv.take<float>((size_t)n); };
+    auto i32 = [&](int64_t n) { return sv.take<int32_t>((size_t)n); };
+    auto fc = [&](int64_t n) { return sc.take<float>((size_t)n); };
+    auto ic = [&](int64_t n) { return sc.take<int32_t>((size_t)n); };
     const int64_t K = L < TM_KS ? L : TM_KS, E = L * K, H = FT_H, D0 = dims[0];
     // saved
     w.offs = i32(2); w.E48 = i32(L * TM_KS); w.eidx = i32(E); w.cls = i32(E); w.rows_id = i32(M); w.status = i32(1);
@@ -582,7 +578,7 @@ static FtWs ft_carve2(void *saved, void *scratch, bool split, int64_t L, int64_t
         s.out = f(L * H);
     }
     w.head_bytes = tmpnn_head_train_workspace_bytes(M, n_layers >= 1 ? (int)(D0 / H - 1) : 0, lightattn, n_layers, dims);
-    w.head_ws = take_s(w.head_bytes);
+    w.head_ws = sv.take<char>(w.head_bytes);
     if (split) { w.ftm = f(E * H); w.fdh = f(L * H); w.fdF = f(L * H); }
     // scratch
     w.cnt = ic(L + 1); w.cur = ic(L + 1); w.coff = ic(L + 1); w.clist = ic(E);
@@ -596,14 +592,14 @@ static FtWs ft_carve2(void *saved, void *scratch, bool split, int64_t L, int64_t
     w.P = fc(pe * std::max<int64_t>(H * (4 * H + 1), 4 * H * (H + 1)));
     w.CP = fc((int64_t)FT_CLS_PARTS * std::max<int64_t>(66 * 16, TMPNN_VOCAB * H));
     if (split) {
-        w.head_ws_b = take_c(w.head_bytes);
+        w.head_ws_b = sc.take<char>(w.head_bytes);
     } else {
         w.ftm = w.tm; w.fdh = w.dh1; w.fdF = w.dF;
         w.head_ws_b = w.head_ws;
     }
-    w.saved_bytes = so + (split ? 256 : 0);
-    w.scratch_bytes = co + 256;
-    w.bytes = so + co + 256;
+    w.saved_bytes = sv.used + (split ? 256 : 0);
+    w.scratch_bytes = sc.used + 256;
+    w.bytes = sv.used + sc.used + 256;
     return w;
 }
 

@@ -75,6 +75,25 @@ struct LayerWs {
     float *P2;     // [T,256] node projections for the encoder edge update
     float *Ssum;   // [T,128] sum_k mask_k * m2_k
     float *cnt;    // [T]     sum_k mask_k
+    size_t bytes;  // of the workspace, up to the end of cnt
+};
+
+// Caller-owned buffers are carved into arrays that each start on a 256-byte boundary. A buffer's layout is ONE function that takes
+// its arrays from a Carver and reports `used`: the entry runs it on the caller's buffer and compares with the caller's byte count
+// before it touches an array; the buffer's *_bytes() runs it without a base (null pointers, only the count) and adds the buffer's
+// slack. So a size cannot drift from its carve.
+static inline size_t tm_align256(size_t b) { return (b + 255) & ~(size_t)255; }
+struct Carver {
+    char *base = nullptr;        // nullptr: measure
+    size_t used = 0;
+    Carver() {}
+    // the caller's buffer as it is, or (align_base) from its first 256-byte boundary on, the bytes skipped charged to `used`
+    Carver(void *buf, bool align_base) : base((char *)buf), used(align_base ? tm_align256((uintptr_t)buf) - (uintptr_t)buf : 0) {}
+    template <class T> T *take(size_t n) {
+        T *const r = base ? (T *)(base + used) : nullptr;
+        used += tm_align256(n * sizeof(T));
+        return r;
+    }
 };
 
 int tm_set_error(int code, const char *fmt, ...);

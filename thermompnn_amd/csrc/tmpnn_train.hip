@@ -279,8 +279,6 @@ __global__ __launch_bounds__(TM_THREADS) void tr_adamw_kernel(TrAdam a) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-static size_t tr_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 static int tr_dims_ok(int n_final, int n_layers, const int32_t *dims) {
     if (n_final < 0 || n_final > 3 || n_layers < 1 || n_layers > TR_MAX_LAYERS || !dims) return 0;
     if (dims[0] != TMPNN_HID * n_final + TMPNN_HID || dims[n_layers] != TMPNN_VOCAB) return 0;
@@ -321,21 +319,19 @@ struct TrWs { float *H[TR_MAX_LAYERS + 1]; float *mask, *dA, *dB, *P; size_t byt
 
 static TrWs tr_carve(void *base, int64_t M, int lightattn, int n_layers, const int32_t *dims) {
     TrWs w{};
-    char *p = (char *)base;
-    size_t off = 0;
-    auto take = [&](size_t nbytes) { float *r = base ? (float *)(p + off) : nullptr; off += tr_align(nbytes); return r; };
+    Carver c(base, false);                           // (base == nullptr measures; the entries compare with `bytes` first)
     int widest = dims[0];
     for (int l = 1; l <= n_layers; ++l) widest = dims[l] > widest ? dims[l] : widest;
-    w.H[0] = lightattn ? take((size_t)M * dims[0] * 4) : nullptr;
-    for (int l = 1; l <= n_layers; ++l) w.H[l] = take((size_t)M * dims[l] * 4);
-    w.mask = lightattn ? take((size_t)M * dims[0] * 4) : nullptr;
-    w.dA = take((size_t)M * widest * 4);
-    w.dB = take((size_t)M * widest * 4);
+    w.H[0] = lightattn ? c.take<float>((size_t)M * dims[0]) : nullptr;
+    for (int l = 1; l <= n_layers; ++l) w.H[l] = c.take<float>((size_t)M * dims[l]);
+    w.mask = lightattn ? c.take<float>((size_t)M * dims[0]) : nullptr;
+    w.dA = c.take<float>((size_t)M * widest);
+    w.dB = c.take<float>((size_t)M * widest);
     size_t pmax = 0;
     for (int l = 0; l < n_layers; ++l) pmax = std::max(pmax, (size_t)dims[l + 1] * (dims[l] + 1));
     if (lightattn) pmax = std::max(pmax, (size_t)dims[0] * (dims[0] + 1));
-    w.P = take(pmax * tr_parts(M) * 4);
-    w.bytes = off + 256;
+    w.P = c.take<float>(pmax * tr_parts(M));
+    w.bytes = c.used + 256;
     return w;
 }
 

@@ -43,6 +43,21 @@ def _selftest(lib, device) -> None:
     _selftested.add(key)
 
 
+def range_retry(run, used: str, retry: Optional[str], what: str, stacklevel: int = 2) -> None:
+    """The range contract of every checked call. ``run(precision)`` makes the call's launches at that precision and returns the
+    device status word. A RANGE bit after an f16x2 run (an operand left the fp16 range) with a ``retry`` precision to go to: one
+    RuntimeWarning, attributed ``stacklevel`` frames up as ``warnings.warn`` counts them from the CALLER of this function, and one
+    rerun at ``retry``. Whatever bits are left, rerun or not, raise through tmpnn_status_error (TmpnnRangeError for RANGE)."""
+    st = run(used)
+    if st & _lib.STATUS_RANGE and not st & _lib.STATUS_MAXLEN and used == "f16x2" and retry and retry != used:
+        warnings.warn(f"ThermoMPNN HIP engine: non-finite result in {used} (an operand left the fp16 range); "
+                      f"rerunning this batch at precision {retry}", RuntimeWarning, stacklevel=stacklevel + 1)
+        used = retry
+        st = run(retry)
+    if st:
+        check(_lib.load().tmpnn_status_error(st), f"tmpnn_{what}[{used}]")
+
+
 class Weights:
     """Device-resident weight set + the native handle (tmpnn_weights_create)."""
 
@@ -322,28 +337,16 @@ class Engine:
         else:
             ws, status = self._workspace(need), self._status
 
-        def run(w: Weights):
-            check(self.lib.tmpnn_ssm_forward(w.handle, _ptr(X), _ptr(S), _ptr(mask), _ptr(ridx), _ptr(cenc), _ptr(offsets),
-                                             N, T, max_len, self.K, _ptr(res.get("ddg") if want_ddg else None),
+        def run(precision: str) -> int:
+            check(self.lib.tmpnn_ssm_forward(self.weights_for(precision).handle, _ptr(X), _ptr(S), _ptr(mask), _ptr(ridx), _ptr(cenc),
+                                             _ptr(offsets), N, T, max_len, self.K, _ptr(res.get("ddg") if want_ddg else None),
                                              _ptr(res.get("hidden") if want_hidden else None),
                                              _ptr(res.get("log_probs") if want_log_probs else None),
                                              _ptr(res.get("E_idx") if want_E_idx else None), _ptr(status), _ptr(ws),
                                              ws.numel(), _stream()), "tmpnn_ssm_forward")
+            return int(status.item()) if check_status and T > 0 and N > 0 else 0      # (ONE 4-byte D2H copy = a stream sync)
 
-        used = precision or self.precision
-        run(self.weights_for(used))
-        if check_status and T > 0 and N > 0:
-            st = self._raise_status("tmpnn_ssm_forward", status)
-            if st & _lib.STATUS_RANGE:
-                retry = self.retry_precision
-                if used != "f16x2" or not retry or retry == used:
-                    check(self.lib.tmpnn_status_error(st), f"tmpnn_ssm_forward[{used}]")
-                warnings.warn(f"ThermoMPNN HIP engine: non-finite result in {used} (an operand left the fp16 range); "
-                              f"rerunning this batch at precision {retry}", RuntimeWarning, stacklevel=2)
-                run(self.weights_for(retry))
-                st = self._raise_status("tmpnn_ssm_forward", status)
-                if st:
-                    check(self.lib.tmpnn_status_error(st), f"tmpnn_ssm_forward[{retry}]")
+        range_retry(run, precision or self.precision, self.retry_precision, "ssm_forward")
         return res
 
     # -- many sequence variants over one backbone ----------------------------------------------------
@@ -411,41 +414,46 @@ class Engine:
             res["log_probs"] = torch.empty((V, T, VOCAB), dtype=torch.float32, device=dev)
         if V == 0 or T == 0:
             return res
-        rows = int(max_rows) if max_rows is not None else 1 << 18
-        per = max(1, rows // T)
-        status = torch.zeros(1, dtype=torch.int32, device=dev)     # per call: OR of the chunks' words
+        per = self._per_chunk(max_rows, T)
         sizer = self.lib.tmpnn_decode_variants_workspace_bytes if R is None else self.lib.tmpnn_decode_ordered_workspace_bytes
 
-        def run(e: "EncodedBackbone") -> int:
-            w = self.weights_for(e.precision)
-            ws = self._workspace(sizer(T, min(per, V)))
-            status.zero_()
-            for v0 in range(0, V, per):
-                v1 = min(V, v0 + per)
-                part = lambda k: _ptr(res[k][v0:v1]) if k in res else None
-                if R is None:
-                    check(self.lib.tmpnn_decode_variants(w.handle, _ptr(e.ctx), e.ctx.numel(), _ptr(S[v0:v1]), v1 - v0, _ptr(e.mask), T,
-                                                         part("ddg"), part("hidden"), part("log_probs"), _ptr(self._status), _ptr(ws),
-                                                         ws.numel(), _stream()), "tmpnn_decode_variants")
-                else:
-                    check(self.lib.tmpnn_decode_ordered(w.handle, _ptr(e.ctx), e.ctx.numel(), _ptr(S[v0:v1]), _ptr(R[v0:v1]), v1 - v0,
-                                                        _ptr(e.mask), T, part("ddg"), part("hidden"), part("log_probs"),
-                                                        _ptr(self._status), _ptr(ws), ws.numel(), _stream()), "tmpnn_decode_ordered")
+        def launch(e: "EncodedBackbone", w: Weights, ws: torch.Tensor, v0: int, v1: int):
+            part = lambda k: _ptr(res[k][v0:v1]) if k in res else None
+            if R is None:
+                check(self.lib.tmpnn_decode_variants(w.handle, _ptr(e.ctx), e.ctx.numel(), _ptr(S[v0:v1]), v1 - v0, _ptr(e.mask), T,
+                                                     part("ddg"), part("hidden"), part("log_probs"), _ptr(self._status), _ptr(ws),
+                                                     ws.numel(), _stream()), "tmpnn_decode_variants")
+            else:
+                check(self.lib.tmpnn_decode_ordered(w.handle, _ptr(e.ctx), e.ctx.numel(), _ptr(S[v0:v1]), _ptr(R[v0:v1]), v1 - v0,
+                                                    _ptr(e.mask), T, part("ddg"), part("hidden"), part("log_probs"),
+                                                    _ptr(self._status), _ptr(ws), ws.numel(), _stream()), "tmpnn_decode_ordered")
+
+        self._chunked(what, enc, V, per, sizer(T, min(per, V)), launch, check_status, stacklevel=3)
+        return res
+
+    # -- the chunk loop and range contract of the calls over an encoded backbone (decode_variants, decode_ordered, sample) ---------
+    @staticmethod
+    def _per_chunk(max_rows: Optional[int], T: int) -> int:
+        """Variants / chains per launch: at most ``max_rows`` rows (default 2**18) of T residues, at least one."""
+        return max(1, (int(max_rows) if max_rows is not None else 1 << 18) // T)
+
+    def _chunked(self, what: str, enc: "EncodedBackbone", n: int, per: int, need: int, launch, check_status: bool, stacklevel: int):
+        """``launch(e, w, ws, i0, i1)`` for every chunk of at most ``per`` of ``n`` items, each with the engine's status word, on
+        ``enc`` and a workspace of ``need`` bytes; the OR of the chunks' words (one read-back) goes through ``range_retry``, whose
+        rerun encodes the backbone again at the retry precision. ``stacklevel``: as ``warnings.warn`` counts from the caller."""
+        def run(precision: str) -> int:
+            e = enc
+            if precision != enc.precision:
+                X, ridx, cenc, max_len = enc.inputs
+                e = self.encode(X, enc.mask, ridx, cenc, enc.offsets, max_len=max_len, precision=precision)
+            w, ws = self.weights_for(precision), self._workspace(need)
+            status = torch.zeros(1, dtype=torch.int32, device=self.device)
+            for i0 in range(0, n, per):
+                launch(e, w, ws, i0, min(n, i0 + per))
                 status.bitwise_or_(self._status)
             return int(status.item()) if check_status else 0
 
-        st = run(enc)
-        if st & _lib.STATUS_RANGE:
-            retry, used = self.retry_precision, enc.precision
-            if used != "f16x2" or not retry or retry == used:
-                check(self.lib.tmpnn_status_error(st), f"tmpnn_{what}[{used}]")
-            warnings.warn(f"ThermoMPNN HIP engine: non-finite result in {used} (an operand left the fp16 range); "
-                          f"rerunning this batch at precision {retry}", RuntimeWarning, stacklevel=3)
-            X, ridx, cenc, max_len = enc.inputs
-            st = run(self.encode(X, enc.mask, ridx, cenc, enc.offsets, max_len=max_len, precision=retry))
-        if st:
-            check(self.lib.tmpnn_status_error(st), f"tmpnn_{what}")
-        return res
+        range_retry(run, enc.precision, self.retry_precision, what, stacklevel + 1)
 
     # -- autoregressive sampling over one backbone ----------------------------------------------------
     def sample(self, enc: "EncodedBackbone", order, S_fixed, free, u, temperature: float = 1.0, bias=None, allowed=None,
@@ -487,37 +495,18 @@ class Engine:
             raise TmpnnError(f"sample: every row of order must be a permutation of 0..{T - 1}")
         if not ok[1]:
             raise TmpnnError(f"sample: residue indices must lie in [0, {VOCAB})")
-        rows = int(max_rows) if max_rows is not None else 1 << 18
-        per = max(1, rows // T)
-        status = torch.zeros(1, dtype=torch.int32, device=dev)     # per call: OR of the chunks' words
+        per = self._per_chunk(max_rows, T)
         need = self.lib.tmpnn_sample_workspace_bytes(T, min(per, N))
         if need == 0:
             raise TmpnnError(f"sample: {min(per, N)} chains of {T} residues exceed one launch's table; lower max_rows")
 
-        def run(e: "EncodedBackbone") -> int:
-            w = self.weights_for(e.precision)
-            ws = self._workspace(need)
-            status.zero_()
-            for n0 in range(0, N, per):
-                n1 = min(N, n0 + per)
-                check(self.lib.tmpnn_sample(w.handle, _ptr(e.ctx), e.ctx.numel(), _ptr(e.mask), T, n1 - n0, _ptr(O[n0:n1]), _ptr(S0[n0:n1]),
-                                            _ptr(Fr[n0:n1]), _ptr(U[n0:n1]), 1.0 / float(temperature), _ptr(B), _ptr(A),
-                                            _ptr(res["S"][n0:n1]), _ptr(res["probs"][n0:n1]), _ptr(self._status), _ptr(ws), ws.numel(),
-                                            _stream()), "tmpnn_sample")
-                status.bitwise_or_(self._status)
-            return int(status.item()) if check_status else 0
+        def launch(e: "EncodedBackbone", w: Weights, ws: torch.Tensor, n0: int, n1: int):
+            check(self.lib.tmpnn_sample(w.handle, _ptr(e.ctx), e.ctx.numel(), _ptr(e.mask), T, n1 - n0, _ptr(O[n0:n1]), _ptr(S0[n0:n1]),
+                                        _ptr(Fr[n0:n1]), _ptr(U[n0:n1]), 1.0 / float(temperature), _ptr(B), _ptr(A),
+                                        _ptr(res["S"][n0:n1]), _ptr(res["probs"][n0:n1]), _ptr(self._status), _ptr(ws), ws.numel(),
+                                        _stream()), "tmpnn_sample")
 
-        st = run(enc)
-        if st & _lib.STATUS_RANGE:
-            retry, used = self.retry_precision, enc.precision
-            if used != "f16x2" or not retry or retry == used:
-                check(self.lib.tmpnn_status_error(st), f"tmpnn_sample[{used}]")
-            warnings.warn(f"ThermoMPNN HIP engine: non-finite result in {used} (an operand left the fp16 range); "
-                          f"rerunning this batch at precision {retry}", RuntimeWarning, stacklevel=2)
-            X, ridx, cenc, max_len = enc.inputs
-            st = run(self.encode(X, enc.mask, ridx, cenc, enc.offsets, max_len=max_len, precision=retry))
-        if st:
-            check(self.lib.tmpnn_status_error(st), "tmpnn_sample")
+        self._chunked("sample", enc, N, per, need, launch, check_status, stacklevel=2)
         return res
 
     def capture_graph(self, X, S, mask, residue_idx, chain_enc, offsets, max_len: int, out: Optional[dict] = None, **want):
