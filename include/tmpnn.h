@@ -361,6 +361,40 @@ int tmpnn_sample(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, co
                  float inv_temperature, const float *bias_opt /* [T,21] */, const float *allowed_opt /* [T,21] */,
                  int32_t *S_out /* [N,T] */, float *probs_opt /* [N,T,21] */,
                  int32_t *status_opt, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream);
+/* ProteinMPNN.tied_sample's loop (protein_mpnn_utils.py:1385-1494) and the PSSM terms of both reference samplers (:1354-1367,
+ * :1472-1481), again N chains in ONE launch; every argument tmpnn_sample has means what it means there. A chain's schedule is
+ * order[n,:] (a permutation) and close[n,:] (0 / 1): a GROUP is a maximal run of steps ending at a step with close == 1,
+ * close[n,T-1] must be 1, and close all ones is untied sampling. A group's members are decoded one after the other and share ONE
+ * draw. Walking the members in step order (t the residue, s the step):
+ *   - dead group (:1444-1450): the first member with mask[t] == 0 ends the group, t_dead = t. The members before it stay decoded,
+ *     the members after it are never decoded, the group's letter is S_fixed[n,t_dead] and the probs rows of ALL members are exactly 0;
+ *   - a live member is decoded as tmpnn_sample decodes it; neighbour j is visible iff its step is below s. A visible neighbour from
+ *     an earlier group gives its decoder-state rows plus the sequence term of its group's letter; an earlier member of the SAME group
+ *     gives its rows WITHOUT a sequence term (the reference has written h_V_stack[l+1][j], h_S[j] is still zero, :1454-1461); a
+ *     member that was never decoded gives zero state at layers 1 and 2 and the encoder row at layer 0, with its letter's sequence term;
+ *   - acc[0..20] += weight[n,t] * logits_t (:1464; weight = tied_beta[t] / len(group) is the caller's, NULL = 1, may be negative);
+ *   - at the closing member t1 of a live group, in this order (:1468-1488; every per-residue table is read at t1 — the reference's
+ *     loop variable as the member loop leaves it):
+ *         probs = softmax(acc * inv_temperature + bias[t1]);
+ *         pssm_mix:  probs = (1 - mix[t1]) * probs + mix[t1] * pssm_bias[t1];
+ *         pssm_keep: pm = probs * keep[t1] + 0.001 * probs;  probs = pm / sum(pm);
+ *         allowed:   pm = probs * allowed[t1];  probs = pm / sum(pm);
+ *     tmpnn_sample's draw rule on u[n,t1]; the letter is the pick where free[n,t1] == 1, S_fixed[n,t1] elsewhere; probs is
+ *     written to EVERY member's row, also where not free (:1492 has no chain_mask factor, unlike :1376);
+ *   - every member receives the letter in S_out (:1489-1491), and its table rows gain the letter's sequence term.
+ * With close all ones and no weight / PSSM tables this is tmpnn_sample, except that unmasked fixed positions get their probs row.
+ * Non-finite logits or totals OR TMPNN_STATUS_RANGE and the group takes S_fixed[n,t1]. Sizes, bounds (3 * N * T < 2^24), the fp32
+ * refusal ("bf16x3"), the no-op on T == 0 or N == 0 and chain independence as tmpnn_sample; pssm_bias_opt is required iff
+ * pssm_mix_opt is given (TMPNN_E_INVALID otherwise). */
+size_t tmpnn_sample_tied_workspace_bytes(int64_t T, int64_t N);     /* 0 = unsupported sizes */
+int tmpnn_sample_tied(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const float *mask, int64_t T, int64_t N,
+                      const int32_t *order, const int32_t *close /* [N,T] 1 = the step is the last member of its group */,
+                      const int32_t *S_fixed, const float *free, const float *u /* [N,T] by residue; read at closing members */,
+                      float inv_temperature, const float *weight_opt /* [N,T] by residue */, const float *bias_opt /* [T,21] */,
+                      const float *allowed_opt /* [T,21] */, const float *pssm_mix_opt /* [T] pssm_multi * pssm_coef */,
+                      const float *pssm_bias_opt /* [T,21] */, const float *pssm_keep_opt /* [T,21] pssm_log_odds_mask */,
+                      int32_t *S_out /* [N,T] */, float *probs_opt /* [N,T,21] */,
+                      int32_t *status_opt, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream);
 
 /* ---- host side: native PDB reader + packer ------------------------------------------
  * Replaces alt_parse_PDB (protein_mpnn_utils.py:183-350) + the packing of tied_featurize (:353-605) for one

@@ -837,19 +837,21 @@ extern "C" size_t tmpnn_sample_workspace_bytes(int64_t T, int64_t N) {
     return sample_ws(Carver(), T, N).bytes + 256;
 }
 
-extern "C" int tmpnn_sample(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const float *mask, int64_t T, int64_t N,
-                            const int32_t *order, const int32_t *S_fixed, const float *free_, const float *u, float inv_temperature,
-                            const float *bias_opt, const float *allowed_opt, int32_t *S_out, float *probs_opt, int32_t *status_opt,
-                            void *workspace, size_t workspace_bytes, tmpnn_stream_t stream) {
-    const char *what = "sample";
+// The body of tmpnn_sample (tied == null) and tmpnn_sample_tied (`what` names the entry in messages): the same checks, workspace
+// layout and encoder-state projections; the tied form's arrays travel to the chain kernel's second form.
+static int sample_rows(const char *what, const SampleTied *tied, const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes,
+                       const float *mask, int64_t T, int64_t N, const int32_t *order, const int32_t *S_fixed, const float *free_,
+                       const float *u, float inv_temperature, const float *bias_opt, const float *allowed_opt, int32_t *S_out,
+                       float *probs_opt, int32_t *status_opt, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream) {
     REQUIRE(w, "%s: null weight handle", what);
     REQUIRE(T >= 0 && T <= T_MAX && N >= 0, "%s: bad sizes (T=%lld, N=%lld)", what, (long long)T, (long long)N);
     if (T == 0 || N == 0) return TMPNN_OK;            // nothing to sample (pointers may be null)
     if (T > SAMPLE_ROWS_MAX / 3 / N)
         return tm_set_error(TMPNN_E_UNSUPPORTED, "%s: 3 * N * T = 3 * %lld * %lld rows exceed %lld (sample the chains in chunks)", what,
                             (long long)N, (long long)T, (long long)SAMPLE_ROWS_MAX);
-    REQUIRE(mask && order && S_fixed && free_ && u && S_out, "%s: null input pointer", what);
+    REQUIRE(mask && order && S_fixed && free_ && u && S_out && (!tied || tied->close), "%s: null input pointer", what);
     REQUIRE(inv_temperature > 0.f && inv_temperature <= 3.0e38f, "%s: inv_temperature must be positive and finite", what);
+    REQUIRE(!tied || (tied->pssm_mix != nullptr) == (tied->pssm_bias != nullptr), "%s: pssm_bias goes with pssm_mix (give both or neither)", what);
     EncCtx c;
     TRY(carve_ctx(what, const_cast<void *>(ctx), ctx_bytes, T, &c));
     const size_t need = tmpnn_sample_workspace_bytes(T, N);
@@ -870,5 +872,26 @@ extern "C" int tmpnn_sample(const tmpnn_weights_t *w, const void *ctx, size_t ct
     }
     const float *Penc[3] = {c.P0, s.Penc1, s.Penc2};
     return launch_sample_chains(w, c.hE, c.E_idx, c.hV, c.P0, Penc, mask, T, N, order, S_fixed, free_, u, inv_temperature, bias_opt,
-                                allowed_opt, S_out, probs_opt, status_opt, s.tab, s.rank, st);
+                                allowed_opt, S_out, probs_opt, status_opt, s.tab, s.rank, tied, st);
+}
+
+extern "C" int tmpnn_sample(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const float *mask, int64_t T, int64_t N,
+                            const int32_t *order, const int32_t *S_fixed, const float *free_, const float *u, float inv_temperature,
+                            const float *bias_opt, const float *allowed_opt, int32_t *S_out, float *probs_opt, int32_t *status_opt,
+                            void *workspace, size_t workspace_bytes, tmpnn_stream_t stream) {
+    return sample_rows("sample", nullptr, w, ctx, ctx_bytes, mask, T, N, order, S_fixed, free_, u, inv_temperature, bias_opt, allowed_opt,
+                       S_out, probs_opt, status_opt, workspace, workspace_bytes, stream);
+}
+
+// The tied form has tmpnn_sample's workspace (one layout, sample_ws): a chain's group state lives in the chain kernel's LDS.
+extern "C" size_t tmpnn_sample_tied_workspace_bytes(int64_t T, int64_t N) { return tmpnn_sample_workspace_bytes(T, N); }
+
+extern "C" int tmpnn_sample_tied(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const float *mask, int64_t T, int64_t N,
+                                 const int32_t *order, const int32_t *close, const int32_t *S_fixed, const float *free_, const float *u,
+                                 float inv_temperature, const float *weight_opt, const float *bias_opt, const float *allowed_opt,
+                                 const float *pssm_mix_opt, const float *pssm_bias_opt, const float *pssm_keep_opt, int32_t *S_out,
+                                 float *probs_opt, int32_t *status_opt, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream) {
+    const SampleTied tied{close, weight_opt, pssm_mix_opt, pssm_bias_opt, pssm_keep_opt};
+    return sample_rows("sample_tied", &tied, w, ctx, ctx_bytes, mask, T, N, order, S_fixed, free_, u, inv_temperature, bias_opt, allowed_opt,
+                       S_out, probs_opt, status_opt, workspace, workspace_bytes, stream);
 }

@@ -196,10 +196,12 @@ int launch_variant_penc0(const float *P0, int64_t T, float *Penc, hipStream_t st
 int launch_variant_hidden(const float *const *h, int64_t T, int64_t V, float *out, hipStream_t st);
 // tmpnn_sample.hip: N chains sampled autoregressively over one encoded backbone, 16 chains per workgroup, the T steps inside the launch
 // (tmpnn_sample). Penc[l] [T,256]: projections of the encoder state; rank [N,T] (pre-filled with a large value) and tab [N,3,T,128]: scratch
+// the tied form's extra arrays (tmpnn_sample_tied): close [N,T]; weight [N,T] by residue or null; the PSSM tables or null
+struct SampleTied { const int32_t *close; const float *weight, *pssm_mix, *pssm_bias, *pssm_keep; };
 int launch_sample_chains(const tmpnn_weights *w, const float *hE, const int32_t *E_idx, const float *hV, const float *P0,
                          const float *const *Penc, const float *mask, int64_t T, int64_t N, const int32_t *order, const int32_t *S_fixed,
                          const float *free_, const float *u, float inv_temp, const float *bias, const float *allowed, int32_t *S_out,
-                         float *probs, int32_t *status, float *tab, int32_t *rank, hipStream_t st);
+                         float *probs, int32_t *status, float *tab, int32_t *rank, const SampleTied *tied, hipStream_t st);
 int launch_selftest(int32_t *status, hipStream_t st);
 int tm_num_cus();
 // Kernel-form switches (TMPNN_KNN_REG, TMPNN_NODE_DEEP, TMPNN_FUSE_SMALL ...) and the per-phase timers (TMPNN_*_PROF, which

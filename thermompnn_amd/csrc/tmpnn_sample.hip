@@ -1,4 +1,5 @@
-// Autoregressive sampling over one encoded backbone (tmpnn_sample; protein_mpnn_utils.py:1279-1383): sample_chain_kernel<SP>.
+// Autoregressive sampling over one encoded backbone (tmpnn_sample, tmpnn_sample_tied; protein_mpnn_utils.py:1279-1494):
+// sample_chain_kernel<SP, TIED>.
 //
 // A CHAIN is one sequence being sampled over the packed residue axis (T rows); N chains per call, each with its own decoding order,
 // fixed positions and uniform draws. One workgroup (512 threads, 8 wavefronts) owns a group of up to 16 chains and loops over the T
@@ -20,11 +21,24 @@
 // here needs an image and no new weights exist. An fp32 handle is refused by the launcher with TMPNN_E_UNSUPPORTED (its message names
 // "bf16x3", the precision to use instead).
 //
+// Tied form (sample_chain_kernel<SP, true>, tmpnn_sample_tied; protein_mpnn_utils.py:1385-1494). A chain's steps fall into GROUPS
+// (maximal runs of steps ending at close == 1) that share one draw. Per chain the LDS holds the open group's first step, whether a
+// masked member ended it (and which), and the 21 weighted logits so far. A member whose group is dead runs with row mask
+// mask[t] * alive = 0, so its state is exactly zero; a non-closing step stores its three table rows WITHOUT the sequence term (a later
+// member of the group sees this state and no letter), the closing step computes the group's distribution and letter, stores its own
+// rows with the term as the untied form does, and adds the term to the earlier members' rows (row = row + seq_tab[l][letter]: the
+// same single fp32 add, so an untied chain's bits are the untied form's). The untied form (<SP, false>) is the kernel as it was,
+// instruction for instruction, and the only one tmpnn_sample launches.
+//
 // Ordering. Between a step's table writes and the next step's gathers stand a workgroup-scope release, one __syncthreads() and a
-// workgroup-scope acquire. That is enough because (1) a chain's row is never LOADED before that chain stores it — a neighbour that is
-// not yet decoded is read from Penc_l, never from the table, so no stale copy of the line can sit in this CU's L1 — and (2) rows are
-// whole 128-byte lines (512 bytes, 256-byte-aligned base), so no line holds part of a row already read and part of one still to be
-// written. The rank array (residue -> step, the host fills it with a large value, the prologue scatters `order` into it) obeys the same rule: it is
+// workgroup-scope acquire. Untied, a row is stored once and never LOADED before that (a neighbour that is not yet decoded is read
+// from Penc_l, never from the table). Tied, a row can be loaded by a later member of its group, then rewritten at the close, then
+// loaded again — and that is ordered too: a chain's rows are written and read by the wavefronts of ONE workgroup only, all of which
+// run on one CU and go through that CU's one vector L1 (write-through; a store updates or drops the line it hits), so after the
+// release -> barrier -> acquire every later load of the address, by any of them, returns the rewritten row. The rewrite itself is a
+// load and a store of the same address by the lanes that stored the row before (the chain's half-wavefront), in program order. Rows
+// are whole 128-byte lines (512 bytes, 256-byte-aligned base), so no line holds part of a row already written and part of one still
+// to be written. The rank array (residue -> step, the host fills it with a large value, the prologue scatters `order` into it) is
 // complete before its first load.
 //
 // Safe indices. An `order` entry outside [0, T) skips the step for that chain (nothing is dereferenced with it); letters are clamped to
@@ -61,6 +75,10 @@ struct SampleArgs {
     float *tab;                                      // [N,3,T,128]
     int32_t *rank;                                   // [N,T], pre-filled with a large value
     int T, N;
+    // tied form only (sample_chain_kernel<SP, true>)
+    const int32_t *close;                            // [N,T] 1 = the step ends its group
+    const float *weight;                             // [N,T] by residue, or null (1)
+    const float *pssm_mix, *pssm_bias, *pssm_keep;   // [T], [T,21], [T,21] or null
 };
 
 // 16-row fp32 GEMM unit: columns [n0 + 16 wv, +16) of W (rows of the weight matrix) against the swizzled [16,128] tile
@@ -73,7 +91,115 @@ __device__ __forceinline__ f4 sample_gemm16(const float *tile, const float *W, i
     return acc[0][0];
 }
 
-template <typename SP>
+// The tied form's step epilogue for one chain (one thread): a live member adds weight[t] * logits to the group's accumulator; the
+// closing step turns the accumulator into the group's distribution and letter (tmpnn.h, tmpnn_sample_tied). Every per-residue table
+// is read at the CLOSING member t (the reference's leaked loop variable, :1468-1488). Leaves the letter in S and the probs row that
+// every member receives (zeros for a dead group) in `logit`.
+__device__ __forceinline__ void tied_epilogue(const SampleArgs &a, int c, int t, float mk, bool closing, bool dead, int t_dead,
+                                              int &bad_acc, float *acc, float *logit, int &S_out) {
+    const int T = a.T;
+    const bool live = t >= 0 && !dead;
+    if (live) {
+        const unsigned *ul = reinterpret_cast<const unsigned *>(logit);
+        const float w = a.weight ? a.weight[(size_t)c * T + t] : 1.0f;
+        bool bad = false;
+#pragma unroll
+        for (int k = 0; k < TMPNN_VOCAB; ++k) {
+            bad = bad || tm_nonfinite_bits(ul[k]);
+            acc[k] = __builtin_fmaf(w, logit[k], acc[k]);
+        }
+        if (bad) bad_acc = 1;
+    }
+    if (!closing) return;
+    int S = 0;
+    float p[TMPNN_VOCAB];
+#pragma unroll
+    for (int k = 0; k < TMPNN_VOCAB; ++k) p[k] = 0.f;
+    if (live) {
+        const size_t ct = (size_t)c * T + t;
+        bool bad = bad_acc != 0;
+        float z[TMPNN_VOCAB];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < TMPNN_VOCAB; ++k) {
+            z[k] = acc[k] * a.inv_temp + (a.bias ? a.bias[(size_t)t * TMPNN_VOCAB + k] : 0.f);
+            mx = fmaxf(mx, z[k]);
+        }
+        float den = 0.f;
+#pragma unroll
+        for (int k = 0; k < TMPNN_VOCAB; ++k) {
+            p[k] = expf(z[k] - mx);
+            den += p[k];
+        }
+#pragma unroll
+        for (int k = 0; k < TMPNN_VOCAB; ++k) p[k] = p[k] / den;
+        if (a.pssm_mix) {                                           // :1472-1476
+            const float mix = a.pssm_mix[t];
+#pragma unroll
+            for (int k = 0; k < TMPNN_VOCAB; ++k) p[k] = (1.0f - mix) * p[k] + mix * a.pssm_bias[(size_t)t * TMPNN_VOCAB + k];
+        }
+        if (a.pssm_keep) {                                          // :1477-1481
+            float d1 = 0.f;
+#pragma unroll
+            for (int k = 0; k < TMPNN_VOCAB; ++k) {
+                p[k] = p[k] * a.pssm_keep[(size_t)t * TMPNN_VOCAB + k] + p[k] * 0.001f;
+                d1 += p[k];
+            }
+#pragma unroll
+            for (int k = 0; k < TMPNN_VOCAB; ++k) p[k] = p[k] / d1;
+        }
+        if (a.allowed) {
+            float d2 = 0.f;
+#pragma unroll
+            for (int k = 0; k < TMPNN_VOCAB; ++k) {
+                p[k] = p[k] * a.allowed[(size_t)t * TMPNN_VOCAB + k];
+                d2 += p[k];
+            }
+#pragma unroll
+            for (int k = 0; k < TMPNN_VOCAB; ++k) p[k] = p[k] / d2;
+        }
+        float cum[TMPNN_VOCAB];
+        float run = 0.f;
+#pragma unroll
+        for (int k = 0; k < TMPNN_VOCAB; ++k) {
+            run += p[k];
+            cum[k] = run;
+        }
+        {   // raw-bit test of the computed total (see tm_f16_range_computed): NaN / inf / not positive
+            float tot = run;
+            asm volatile("" : "+v"(tot));
+            const unsigned b = __float_as_uint(tot);
+            bad = bad || tm_nonfinite_bits(b) || (b >> 31) != 0u || (b & 0x7fffffffu) == 0u;
+        }
+        const float thr = a.u[ct] * run;
+        int pick = -1, lastpos = 0;
+#pragma unroll
+        for (int k = TMPNN_VOCAB - 1; k >= 0; --k)
+            if (cum[k] > thr) pick = k;                             // ends at the smallest such k
+#pragma unroll
+        for (int k = 0; k < TMPNN_VOCAB; ++k)
+            if (p[k] > 0.f) lastpos = k;
+        if (pick < 0) pick = lastpos;
+        int sf = a.S_fixed[ct];
+        sf = sf < 0 ? 0 : sf >= TMPNN_VOCAB ? TMPNN_VOCAB - 1 : sf;
+        const bool is_free = a.free_[ct] * mk == 1.0f;
+        if (bad) {
+            if (a.status) atomicOr(a.status, TMPNN_STATUS_RANGE);
+            pick = sf;
+        }
+        pick = pick < 0 ? 0 : pick >= TMPNN_VOCAB ? TMPNN_VOCAB - 1 : pick;
+        S = is_free ? pick : sf;
+    } else if (dead) {                                              // :1445-1448: the letter of the member that ended the group
+        const int sf = a.S_fixed[(size_t)c * T + t_dead];
+        S = sf < 0 ? 0 : sf >= TMPNN_VOCAB ? TMPNN_VOCAB - 1 : sf;
+        if (bad_acc && a.status) atomicOr(a.status, TMPNN_STATUS_RANGE);
+    }
+    S_out = S;
+#pragma unroll
+    for (int k = 0; k < TMPNN_VOCAB; ++k) logit[k] = p[k];
+}
+
+template <typename SP, bool TIED>
 __global__ __launch_bounds__(512) void sample_chain_kernel(SampleArgs a) {
     constexpr int TILEB = SP::NP * SPLIT_PLANE_BYTES, NC = TM_SAMPLE_CHAINS;
     constexpr bool PERM = SP::NP == 2;
@@ -89,6 +215,9 @@ __global__ __launch_bounds__(512) void sample_chain_kernel(SampleArgs a) {
     __shared__ int s_vis[NC][TM_KS];
     __shared__ float s_cnt[NC], s_mk[NC];
     __shared__ int s_t[NC], s_S[NC];
+    // tied form: the chain's open group — its first step, whether a masked member ended it (and which), the weighted logits so far
+    __shared__ int s_gs[TIED ? NC : 1], s_close[TIED ? NC : 1], s_dead[TIED ? NC : 1], s_tdead[TIED ? NC : 1], s_bad[TIED ? NC : 1];
+    __shared__ float s_acc[TIED ? NC : 1][TMPNN_VOCAB];
     const int tid = tm_tid(), lane = tid & 63, wv = tid >> 6, m = lane & 15, q = lane >> 4;
     const int ncol = 16 * wv + 4 * q, c4 = 4 * wv + q;
     const int c4s = PERM ? perm_c4(c4) : c4;
@@ -116,7 +245,24 @@ __global__ __launch_bounds__(512) void sample_chain_kernel(SampleArgs a) {
             const int t = a.order[(size_t)cc * T + s];
             const bool ok = c < a.N && t >= 0 && t < T;
             s_t[tid] = ok ? t : -1;
-            s_mk[tid] = ok ? a.mask[t] : 0.f;
+            if constexpr (TIED) {
+                if (s == 0 || s_close[tid]) {                       // the step before closed a group: a new one opens here
+                    s_gs[tid] = s;
+                    s_dead[tid] = 0;
+                    s_bad[tid] = 0;
+#pragma unroll
+                    for (int k = 0; k < TMPNN_VOCAB; ++k) s_acc[tid][k] = 0.f;
+                }
+                s_close[tid] = c < a.N ? (a.close[(size_t)cc * T + s] != 0 ? 1 : 0) : 1;
+                const float mk = ok ? a.mask[t] : 0.f;
+                if (ok && !s_dead[tid] && mk == 0.f) {              // the reference's break (:1444-1450): the group is dead from t on
+                    s_dead[tid] = 1;
+                    s_tdead[tid] = t;
+                }
+                s_mk[tid] = s_dead[tid] ? 0.f : mk;                 // mask[t] * alive: a skipped member's state is zero
+            } else {
+                s_mk[tid] = ok ? a.mask[t] : 0.f;
+            }
         }
         __syncthreads();
         {   // neighbour lists, visibility, counts: wavefront wv looks after rows 2 wv, 2 wv + 1
@@ -274,7 +420,10 @@ __global__ __launch_bounds__(512) void sample_chain_kernel(SampleArgs a) {
         }
         __syncthreads();
         // ---- softmax, tables, the draw: one thread per chain
-        if (tid < NC) {
+        if constexpr (TIED) {
+            if (tid < NC) tied_epilogue(a, cg0 + tid, s_t[tid], s_mk[tid], s_close[tid] != 0, s_dead[tid] != 0, s_tdead[tid],
+                                        s_bad[tid], s_acc[tid], s_logit[tid], s_S[tid]);
+        } else if (tid < NC) {
             const int t = s_t[tid], c = cg0 + tid;
             if (t >= 0) {
                 const size_t ct = (size_t)c * T + t;
@@ -348,7 +497,48 @@ __global__ __launch_bounds__(512) void sample_chain_kernel(SampleArgs a) {
             }
         }
         __syncthreads();
-        {   // ---- the chain's three neighbour rows of t, with the sequence term of the letter just chosen
+        if constexpr (TIED) {
+            // ---- the three neighbour rows of t: WITHOUT a sequence term while the group is open (a later member sees this state and no
+            // letter, :1454-1461), with it at the close — and then every earlier member's rows gain it (row = row + seq, the same
+            // single fp32 add), written by the half-wavefront that stored them; S_out and the probs row go to every member
+            const int t = s_t[hw], c = cg0 + hw;
+            if (c < a.N) {
+                const bool closing = s_close[hw] != 0;
+                const int S = s_S[hw];
+                float *tabc = a.tab + (size_t)c * 3 * (size_t)T * TM_H + 4 * c32;
+                const float *sq0 = a.L[0].seq_tab + S * TM_H + 4 * c32, *sq1 = a.L[1].seq_tab + S * TM_H + 4 * c32,
+                            *sq2 = a.L[2].seq_tab + S * TM_H + 4 * c32;
+                if (t >= 0) {
+                    float *row = tabc + (size_t)t * TM_H;
+                    const f4 n0 = ld4(a.P0 + (size_t)t * 256 + 128 + 4 * c32);
+                    const f4 n1 = ld4(s_nb[0] + hw * TM_H + 4 * c32), n2 = ld4(s_nb[1] + hw * TM_H + 4 * c32);
+                    if (closing) {
+                        st4(row, ld4(sq0) + n0);
+                        st4(row + (size_t)T * TM_H, ld4(sq1) + n1);
+                        st4(row + 2 * (size_t)T * TM_H, ld4(sq2) + n2);
+                    } else {
+                        st4(row, n0);
+                        st4(row + (size_t)T * TM_H, n1);
+                        st4(row + 2 * (size_t)T * TM_H, n2);
+                    }
+                }
+                if (closing) {
+                    for (int sp = s_gs[hw]; sp <= s; ++sp) {
+                        const int tp = a.order[(size_t)c * T + sp];
+                        if (tp < 0 || tp >= T) continue;
+                        if (sp < s) {
+                            float *row = tabc + (size_t)tp * TM_H;
+                            st4(row, ld4(row) + ld4(sq0));
+                            st4(row + (size_t)T * TM_H, ld4(row + (size_t)T * TM_H) + ld4(sq1));
+                            st4(row + 2 * (size_t)T * TM_H, ld4(row + 2 * (size_t)T * TM_H) + ld4(sq2));
+                        }
+                        const size_t cp = (size_t)c * T + tp;
+                        if (c32 == 0) a.S_out[cp] = S;
+                        if (a.probs && c32 < TMPNN_VOCAB) a.probs[cp * TMPNN_VOCAB + c32] = s_logit[hw][c32];
+                    }
+                }
+            }
+        } else {   // ---- the chain's three neighbour rows of t, with the sequence term of the letter just chosen
             const int t = s_t[hw];
             if (t >= 0) {
                 const int S = s_S[hw];
@@ -366,11 +556,12 @@ __global__ __launch_bounds__(512) void sample_chain_kernel(SampleArgs a) {
 }
 
 // Precision by the handle's mode (f16x2 | bf16x3; the caller refuses fp32). Penc[l]: [T,256] projections of the encoder state
-// (layer 0: the ctx's P0). rank [N,T] and tab [N,3,T,128] are scratch. Reads no environment, allocates nothing, never synchronises.
+// (layer 0: the ctx's P0). rank [N,T] and tab [N,3,T,128] are scratch. `tied` (or null) selects the tied form and carries its
+// arrays. Reads no environment, allocates nothing, never synchronises.
 int launch_sample_chains(const tmpnn_weights *w, const float *hE, const int32_t *E_idx, const float *hV, const float *P0,
                          const float *const *Penc, const float *mask, int64_t T, int64_t N, const int32_t *order, const int32_t *S_fixed,
                          const float *free_, const float *u, float inv_temp, const float *bias, const float *allowed, int32_t *S_out,
-                         float *probs, int32_t *status, float *tab, int32_t *rank, hipStream_t st) {
+                         float *probs, int32_t *status, float *tab, int32_t *rank, const SampleTied *tied, hipStream_t st) {
     SampleArgs a{};
     const bool h2 = w->mode == TM_MM_F16X2;
     for (int l = 0; l < 3; ++l) {
@@ -393,9 +584,17 @@ int launch_sample_chains(const tmpnn_weights *w, const float *hE, const int32_t 
     a.S_out = S_out; a.probs = probs; a.status = status; a.tab = tab; a.rank = rank;
     a.T = (int)T; a.N = (int)N;
     const int grid = (int)((N + TM_SAMPLE_CHAINS - 1) / TM_SAMPLE_CHAINS);
+    if (tied) {
+        a.close = tied->close; a.weight = tied->weight; a.pssm_mix = tied->pssm_mix; a.pssm_bias = tied->pssm_bias; a.pssm_keep = tied->pssm_keep;
+        tm_prof_begin("sample_chains_tied", st);
+        if (h2) sample_chain_kernel<SplitH2, true><<<grid, 512, 0, st>>>(a);
+        else sample_chain_kernel<SplitBF3, true><<<grid, 512, 0, st>>>(a);
+        tm_prof_end(st);
+        return tm_check_launch("sample_chains_tied");
+    }
     tm_prof_begin("sample_chains", st);
-    if (h2) sample_chain_kernel<SplitH2><<<grid, 512, 0, st>>>(a);
-    else sample_chain_kernel<SplitBF3><<<grid, 512, 0, st>>>(a);
+    if (h2) sample_chain_kernel<SplitH2, false><<<grid, 512, 0, st>>>(a);
+    else sample_chain_kernel<SplitBF3, false><<<grid, 512, 0, st>>>(a);
     tm_prof_end(st);
     return tm_check_launch("sample_chains");
 }

@@ -509,6 +509,68 @@ class Engine:
         self._chunked("sample", enc, N, per, need, launch, check_status, stacklevel=2)
         return res
 
+    def sample_tied(self, enc: "EncodedBackbone", order, close, S_fixed, free, u, temperature: float = 1.0, weight=None, bias=None,
+                    allowed=None, pssm_mix=None, pssm_bias=None, pssm_keep=None, max_rows: Optional[int] = None,
+                    check_status: bool = True):
+        """N chains sampled with TIED positions and PSSM terms in one launch per chunk (tmpnn_sample_tied; the reference's
+        tied_sample, protein_mpnn_utils.py:1385-1494). ``order`` / ``S_fixed`` / ``free`` / ``u`` / ``bias`` / ``allowed`` as ``sample``;
+        ``close`` [N,T] 0 / 1 with close[:, -1] == 1: a group is a maximal run of steps ending at a 1, its members are decoded one
+        after the other (a later member sees the earlier ones' states without a letter), their logits are summed with ``weight``
+        [N,T] (by residue; None = 1; tied_beta / len(group)) and ONE letter is drawn for the group, with every per-residue table read
+        at the closing member; a group that meets a masked member takes S_fixed there and leaves probs rows of 0. ``pssm_mix`` [T]
+        with ``pssm_bias`` [T,21]: probs = (1 - mix) probs + mix pssm_bias; ``pssm_keep`` [T,21]: probs = (probs keep + 0.001 probs),
+        renormalised; then ``allowed``. -> dict(S int32 [N,T], probs [N,T,21]); probs is written to every member of a live group,
+        fixed ones included. Chunking and the range contract as ``sample``."""
+        T, dev = enc.T, self.device
+        O, Cl, S0 = self._i32(order), self._i32(close), self._i32(S_fixed)
+        Fr, U = self._f32(free), self._f32(u)
+        Wt = None if weight is None else self._f32(weight)
+        for name, t in (("order", O), ("close", Cl), ("S_fixed", S0), ("free", Fr), ("u", U), ("weight", Wt)):
+            if t is not None and (t.dim() != 2 or t.shape[1] != T or t.shape[0] != O.shape[0]):
+                raise TmpnnError(f"sample_tied: {name} must be [N, {T}] like order, got {tuple(t.shape)}")
+        if not float(temperature) > 0.0 or not np.isfinite(float(temperature)):
+            raise TmpnnError(f"sample_tied: temperature must be positive and finite, got {temperature!r}")
+        if (pssm_mix is None) != (pssm_bias is None):
+            raise TmpnnError("sample_tied: pssm_bias goes with pssm_mix (give both or neither)")
+        tabs = {}
+        for name, t, shape in (("bias", bias, (T, VOCAB)), ("allowed", allowed, (T, VOCAB)), ("pssm_mix", pssm_mix, (T,)),
+                               ("pssm_bias", pssm_bias, (T, VOCAB)), ("pssm_keep", pssm_keep, (T, VOCAB))):
+            tabs[name] = None if t is None else self._f32(t)
+            if t is not None and tuple(tabs[name].shape) != shape:
+                raise TmpnnError(f"sample_tied: {name} must be {list(shape)}, got {tuple(tabs[name].shape)}")
+        N = O.shape[0]
+        res = {"S": torch.empty((N, T), dtype=torch.int32, device=dev), "probs": torch.empty((N, T, VOCAB), dtype=torch.float32, device=dev)}
+        if N == 0 or T == 0:
+            return res
+        _need_cuda(enc.ctx)
+        # a permutation per row (one device sort), letters in range, close 0 / 1 and ending every row: ONE read-back of the verdicts
+        steps = torch.arange(T, dtype=torch.int32, device=dev)
+        ok = torch.stack([(torch.sort(O, dim=1).values == steps).all(), ((S0 >= 0) & (S0 < VOCAB)).all(),
+                          ((Cl == 0) | (Cl == 1)).all(), (Cl[:, -1] == 1).all()]).tolist()
+        if not ok[0]:
+            raise TmpnnError(f"sample_tied: every row of order must be a permutation of 0..{T - 1}")
+        if not ok[1]:
+            raise TmpnnError(f"sample_tied: residue indices must lie in [0, {VOCAB})")
+        if not ok[2]:
+            raise TmpnnError("sample_tied: close must hold 0 or 1")
+        if not ok[3]:
+            raise TmpnnError("sample_tied: close[:, -1] must be 1 (the last step ends its group)")
+        per = self._per_chunk(max_rows, T)
+        need = self.lib.tmpnn_sample_tied_workspace_bytes(T, min(per, N))
+        if need == 0:
+            raise TmpnnError(f"sample_tied: {min(per, N)} chains of {T} residues exceed one launch's table; lower max_rows")
+
+        def launch(e: "EncodedBackbone", w: Weights, ws: torch.Tensor, n0: int, n1: int):
+            check(self.lib.tmpnn_sample_tied(w.handle, _ptr(e.ctx), e.ctx.numel(), _ptr(e.mask), T, n1 - n0, _ptr(O[n0:n1]), _ptr(Cl[n0:n1]),
+                                             _ptr(S0[n0:n1]), _ptr(Fr[n0:n1]), _ptr(U[n0:n1]), 1.0 / float(temperature),
+                                             _ptr(None if Wt is None else Wt[n0:n1]), _ptr(tabs["bias"]), _ptr(tabs["allowed"]),
+                                             _ptr(tabs["pssm_mix"]), _ptr(tabs["pssm_bias"]), _ptr(tabs["pssm_keep"]),
+                                             _ptr(res["S"][n0:n1]), _ptr(res["probs"][n0:n1]), _ptr(self._status), _ptr(ws), ws.numel(),
+                                             _stream()), "tmpnn_sample_tied")
+
+        self._chunked("sample_tied", enc, N, per, need, launch, check_status, stacklevel=2)
+        return res
+
     def capture_graph(self, X, S, mask, residue_idx, chain_enc, offsets, max_len: int, out: Optional[dict] = None, **want):
         """Capture ONE fused forward (its ~20 launches + the status memset) into a hipGraph: -> (graph, out). ``graph.replay()``
         reruns it on the captured tensors — refill X / S / ... in place for a new protein of the same length. The C-ABI

@@ -2,9 +2,11 @@
 
 Same names, signatures and return conventions; the arithmetic runs in libtmpnn.so
 (hand-written HIP for gfx950) — this module only packs arguments. Out-of-scope symbols of the
-reference file (CA_ProteinFeatures, tied_sample, StructureDataset*, loss_*) are not provided.
+reference file (CA_ProteinFeatures, StructureDataset*, loss_*) are not provided.
 ``ProteinMPNN.conditional_probs`` / ``unconditional_probs`` (:1496-1587) are: the masked decoder runs in tmpnn_decode_ordered.
 ``ProteinMPNN.sample`` (:1279-1383) is: whole chains are sampled autoregressively inside one launch (tmpnn_sample).
+``tied_sample`` (:1385-1494), the PSSM flags of ``sample`` and the design dictionaries of ``tied_featurize`` live in
+``thermompnn_amd.design`` (``ProteinMPNNDesign``, a subclass of this module's ``ProteinMPNN``, and ``design.tied_featurize``).
 """
 from __future__ import annotations
 
@@ -188,9 +190,10 @@ class ProteinMPNN(_EngineOwner):
         letter by inverse CDF (the smallest a whose running sum of probs exceeds u * total). The DISTRIBUTION is the
         reference's; the stream is not ``torch.multinomial``'s, so equal seeds do not give the reference's sequences.
         ``uniforms`` [B,L] (indexed by residue) replaces the draw, e.g. to replay recorded ones.
-        pssm_bias_flag / pssm_log_odds_flag are not supported (NotImplementedError); ``tied_sample`` is not provided."""
+        pssm_bias_flag / pssm_log_odds_flag are not supported here (NotImplementedError) and ``tied_sample`` is not provided:
+        ``thermompnn_amd.design.ProteinMPNNDesign`` has both."""
         if pssm_bias_flag or pssm_log_odds_flag:
-            raise NotImplementedError("sample: pssm_bias_flag / pssm_log_odds_flag are outside this port")
+            raise NotImplementedError("sample: pssm_bias_flag / pssm_log_odds_flag are served by thermompnn_amd.design.ProteinMPNNDesign")
         if not float(temperature) > 0.0:
             raise ValueError(f"sample: temperature must be positive, got {temperature!r}")
         eng = self.engine()
