@@ -282,6 +282,36 @@ int tmpnn_finetune_backward(const float *X, const int32_t *S, const float *mask,
                             const float *dpred, float *grads, int mpnn_grads, const void *saved, size_t saved_bytes, void *scratch,
                             size_t scratch_bytes, tmpnn_stream_t stream);
 
+/* ---- ProteinMPNN's own training objective: log p(sequence | structure) under a decoding order, and its gradient -----------------
+ * The training forward of tmpnn_finetune_forward (exact fp32, dropout at the same 15 sites with the same generator, keep_in / keep_out
+ * layout and tmpnn_finetune_mask_numel) with the ORDER-MASKED decoder of the reference's training flavour and the output layer:
+ * ranks [L] int32, edge (i, k) with j = E_idx[i, k] is visible iff ranks[j] < ranks[i] (equal ranks are not: the self edge never is;
+ * all ranks equal = no sequence information; ranks NULL = every neighbour visible, the self edge too: the order mask of ones under
+ * which tmpnn_ssm_forward computes its log_probs), and the decoder message input of every layer l for that edge is
+ *     mask_i * [ h_V^l_i | h_E_ik | vis * h_S_j | (vis ? h_V^l_j : h_V^enc_j) ],
+ * h_V^enc the last encoder output. log_probs [L,21] = log_softmax(W_out h_V^dec3 + b); rows with mask 0 are finite (h_V is 0 there).
+ * K = min(k_neighbors, L) neighbours, k_neighbors in [1, 48]; E_idx_opt [L, K]. With K < min(48, L) an edge dropout site uses the
+ * first L K rows of its [L min(48, L), 128] part of keep_in / keep_out. The slab holds ProteinMPNN's tensors in state-dict order,
+ * W_out.weight and W_out.bias included, and no head: tmpnn_seqloss_slab_numel floats. The backward takes ANY upstream gradient
+ * dlog_probs [L,21] (rows with mask 0 included: a loss multiplies by its own mask): dlogits = dlp - softmax * sum(dlp), W_out's
+ * gradients, then the decoder, W_s, encoder and featurizer backward of tmpnn_finetune_backward, where d h_S_j is collected over the
+ * visible edges only and d h_V_j of an invisible edge goes to the encoder output (summed over decoder layers 2, 1, 0 in that order,
+ * added before the encoder loop). As tmpnn_finetune_backward it writes the entries of grads that can be non-zero (the caller zeroes the
+ * slab). Deterministic, no float atomics;
+ * `saved` is written by the forward only, so a second backward over it gives the same bits. L in [2, 8192]; the sizers return 0
+ * outside it. Error codes before any launch as tmpnn_finetune_*. */
+int64_t tmpnn_seqloss_slab_numel(void);
+size_t tmpnn_seqloss_saved_bytes(int64_t L);
+size_t tmpnn_seqloss_scratch_bytes(int64_t L);
+int tmpnn_seqloss_forward(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
+                          int64_t L, int k_neighbors, const int32_t *ranks, const float *params, int64_t slab_numel, float p_mpnn,
+                          const float *keep_in, float *keep_out, uint64_t seed, uint64_t step, float *log_probs, int32_t *E_idx_opt,
+                          void *saved, size_t saved_bytes, tmpnn_stream_t stream);
+int tmpnn_seqloss_backward(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
+                           int64_t L, int k_neighbors, const int32_t *ranks, const float *params, int64_t slab_numel, float p_mpnn,
+                           const float *keep_in, uint64_t seed, uint64_t step, const float *dlog_probs, float *grads,
+                           const void *saved, size_t saved_bytes, void *scratch, size_t scratch_bytes, tmpnn_stream_t stream);
+
 /* ---- the fused path ------------------------------------------------------------------------------
  * Everything TransferModel.forward does on the device for a ragged batch of N proteins
  * (transfer_model.py:75-121 + protein_mpnn_utils.py:1222-1277), one call, 18 launches on `stream` (14 when every workgroup has at most one residue tile).

@@ -11,7 +11,11 @@ only W_s when num_final_layers is 0, then the head); its output is pred [M], one
 parameters into the flat fp32 slab (once per weight version) and runs ``tmpnn_finetune_forward`` into a per-call saved buffer; the
 backward runs ``tmpnn_finetune_backward`` from the upstream gradient dL/dpred into a fresh gradient slab and hands torch each
 parameter's gradient as a view of it. Torch accumulates into ``.grad`` itself, so hooks, ``torch.autograd.grad``, gradient
-accumulation and any optimiser work unchanged. W_out is not an input (it is not in the loss): its ``.grad`` stays None.
+accumulation and any optimiser work unchanged. W_out is not an input (it is not in the ddG loss): its ``.grad`` stays None.
+
+``model.sequence_log_probs(pdb, chain_M=None, randn=None)`` is the second differentiable output: ProteinMPNN's own objective,
+log_probs [L,21] under a random decoding order (``model_utils.SeqLossFunction`` over ``prot_mpnn``'s parameters, W_out included). A
+joint loss is two backward passes, one per Function, into the same ``.grad``s.
 
 Values come from the exact fp32 path, whatever ``model.precision`` says. Dropout follows the submodules' ``training`` flags:
 ``prot_mpnn.training`` -> p = 0.1 at ProteinMPNN's 15 sites, ``light_attention.training`` -> p = 0.25 on the head's centre tap. The
@@ -203,3 +207,28 @@ def transfer_forward(model, pdb, mutations):
     pred = FinetuneFunction.apply(plan, inp, bool(model.subtract_mut), p_mpnn, p_head, seed, step, mpnn_grads, *slab_params)
     pieces = iter(pred.split(1))
     return [None if m is None else {"ddG": next(pieces)} for m in mutations], None
+
+
+def transfer_sequence_log_probs(model, pdb, chain_M=None, randn=None):
+    """TransferModel.sequence_log_probs: log_probs [L,21] of one parsed structure with a graph over prot_mpnn's parameters."""
+    from . import model_utils as mu
+    from .pdb_io import tied_featurize
+    from .protein_mpnn_utils import decoding_ranks
+    if not getattr(model, "differentiable", False):
+        raise RuntimeError("sequence_log_probs is part of the gradient path: set model.differentiable = True")
+    params = [p for _, p in model.prot_mpnn.named_parameters()]
+    device = params[0].device
+    if device.type != "cuda":
+        raise RuntimeError("thermompnn_amd runs on MI355X only: move the model to a CUDA (ROCm) device with .cuda(); there is no "
+                           "CPU execution path")
+    feats = tied_featurize([pdb[0] if isinstance(pdb, (list, tuple)) else pdb], device, None, None, None, None, None, None, ca_only=False)
+    X, S, mask, chain_enc, residue_idx = feats[0][0], feats[1][0], feats[2][0], feats[5][0], feats[12][0]
+    cm = mask if chain_M is None else torch.as_tensor(chain_M, dtype=torch.float32, device=device) * mask
+    if randn is None:
+        randn = torch.randn(cm.shape, device=device)
+    ranks = decoding_ranks(cm, torch.as_tensor(randn, dtype=torch.float32).to(device))
+    plan = getattr(model, "_seqloss_plan", None)
+    if plan is None:
+        plan = model._seqloss_plan = mu.SeqPlan()
+    p_mpnn = MPNN_DROPOUT if model.prot_mpnn.training else 0.0
+    return mu.sequence_log_probs(plan, params, X, S, mask, residue_idx, chain_enc, ranks, model.prot_mpnn.k_neighbors, p_mpnn)

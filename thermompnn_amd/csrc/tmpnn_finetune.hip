@@ -31,6 +31,12 @@
 //   decoder layer l (0..2): 9 + 2 l + 0 dropout1 (dh [L,128]), 9 + 2 l + 1 dropout2 (FFN output [L,128]).
 // Injected / exported masks (keep_in, keep_out: 0 / 1 values) are one flat buffer, the sites in this order, each [rows, 128].
 // tests/test_gpu_finetune.py restates the generator in numpy bit for bit.
+//
+// The sequence loss (tmpnn_seqloss_forward / _backward, at the end of the file): ProteinMPNN's own objective, log p(S | X) under a decoding
+// order (/root/reference/model_utils.py:396-470), on the same kernels. Its decoder operand carries a per-edge-row order predicate
+// (FtSeg::vis, ft_row), the inverse-neighbour gathers of the backward take it too (FtCollect::vis), the output layer W_out with its
+// log-softmax closes the forward and seeds the backward from any dL / dlog_probs, and the slab is the whole state dict (sq_layout).
+// Every operand of the ddG path has vis = 0 and keeps its arithmetic.
 #include <math.h>
 #include <stdint.h>
 
@@ -82,14 +88,26 @@ __device__ __forceinline__ float ft_keep(const FtDrop &d, int site, int row, int
 // ---- gathered operand: the row of A for GEMM row m is up to 4 segments side by side ----------------------------------------------
 // mode 0: row m of p; 1: node row m / K (h_V_i); 2: node row E_idx[m] (h_V_j, h_S_j). masked: the segment is scaled by mask[m / K]
 // (the decoder's mask_bw). act 2: GELU on every element (the input of W2 / W3 / W_out is GELU of the saved pre-activation).
-struct FtSeg { const float *p; int ld, width, mode, masked, rows; };
-struct FtA { FtSeg s[4]; int n_seg, K, act; const int32_t *eidx; const float *mask; };
+// Order predicate (the sequence loss; ranks set): edge row m = (i, k) with j = eidx[m] is VISIBLE iff ranks[j] < ranks[i] (equal ranks
+// are not, the self edge included). vis 1: the segment is scaled by 0 on an invisible row (h_S_j); vis 2: an invisible row reads
+// p2 instead of p (h_V_j of the current layer / of the encoder). vis 0 (every fine-tune operand): the arithmetic is unchanged.
+struct FtSeg { const float *p; int ld, width, mode, masked, rows, vis; const float *p2; };
+struct FtA { FtSeg s[4]; int n_seg, K, act; const int32_t *eidx; const float *mask; const int32_t *ranks; };
+
+__device__ __forceinline__ bool ft_visible(const int32_t *ranks, const int32_t *eidx, int e, int K, int L) {
+    return ranks[min(max(eidx[e], 0), L - 1)] < ranks[e / K];
+}
 
 __device__ __forceinline__ const float *ft_row(const FtA &a, const FtSeg &s, int m, float *scale) {
     int r = s.mode == 0 ? m : s.mode == 1 ? m / a.K : a.eidx[m];
     r = min(max(r, 0), s.rows - 1);
     *scale = s.masked ? a.mask[m / a.K] : 1.f;
-    return s.p + (size_t)r * s.ld;
+    const float *base = s.p;
+    if (s.vis && !ft_visible(a.ranks, a.eidx, m, a.K, s.rows)) {
+        if (s.vis == 1) *scale = 0.f;
+        else base = s.p2;
+    }
+    return base + (size_t)r * s.ld;
 }
 
 __device__ __forceinline__ float ft_act(float v, int act) { return act == 2 ? ft_gelu(v) : v; }
@@ -382,7 +400,9 @@ __global__ __launch_bounds__(TM_THREADS) void ft_msg_expand_kernel(const float *
 
 // out[i, c] = (base ? base[i, c] : 0) + sum_k f(e) src[e, self + c] + sum_{e in inv(i)} f(e) src[e, nb + c]; f(e) = mask[e / K] when
 // masked, else 1; self / nb < 0: that term is absent. inv(i): the edges whose neighbour is i, in ascending edge order (the CSR).
-struct FtCollect { float *out; const float *base, *src; int lds, self, nb, masked; const float *mask; const int32_t *off, *list; int L, K; };
+// vis 1 / 2 (ranks set): the neighbour term takes only the visible / only the invisible edges, in the same order.
+struct FtCollect { float *out; const float *base, *src; int lds, self, nb, masked; const float *mask; const int32_t *off, *list; int L, K;
+                   int vis; const int32_t *ranks; };
 
 __global__ __launch_bounds__(TM_THREADS) void ft_collect_kernel(FtCollect a) {
     const int64_t n = (int64_t)a.L * FT_H, stride = (int64_t)tm_nblk() * TM_THREADS;
@@ -396,6 +416,7 @@ __global__ __launch_bounds__(TM_THREADS) void ft_collect_kernel(FtCollect a) {
         if (a.nb >= 0)
             for (int u = a.off[i]; u < a.off[i + 1]; ++u) {
                 const int e = a.list[u];
+                if (a.vis && (a.ranks[i] < a.ranks[e / a.K]) != (a.vis == 1)) continue;
                 const float f = a.masked ? a.mask[e / a.K] : 1.f;
                 s += f * a.src[(size_t)e * a.lds + a.nb + c];
             }
@@ -479,6 +500,26 @@ __global__ __launch_bounds__(TM_THREADS) void ft_csr_sort_kernel(const int32_t *
     }
 }
 
+// ---- the sequence loss's output layer: one thread per residue, sums over the 21 letters in index order -----------------------------
+__global__ __launch_bounds__(TM_THREADS) void sq_logsoftmax_kernel(float *lg, int L) {      // logits -> log_probs, in place
+    for (int i = tm_bid() * TM_THREADS + tm_tid(); i < L; i += tm_nblk() * TM_THREADS) {
+        float *x = lg + (size_t)i * TMPNN_VOCAB, mx = x[0], s = 0.f;
+        for (int a = 1; a < TMPNN_VOCAB; ++a) mx = fmaxf(mx, x[a]);
+        for (int a = 0; a < TMPNN_VOCAB; ++a) s += expf(x[a] - mx);
+        const float lse = mx + logf(s);
+        for (int a = 0; a < TMPNN_VOCAB; ++a) x[a] -= lse;
+    }
+}
+
+__global__ __launch_bounds__(TM_THREADS) void sq_dlogits_kernel(const float *dlp, const float *lp, int L, float *dlg) {
+    for (int i = tm_bid() * TM_THREADS + tm_tid(); i < L; i += tm_nblk() * TM_THREADS) {
+        const size_t o = (size_t)i * TMPNN_VOCAB;
+        float s = 0.f;
+        for (int a = 0; a < TMPNN_VOCAB; ++a) s += dlp[o + a];
+        for (int a = 0; a < TMPNN_VOCAB; ++a) dlg[o + a] = dlp[o + a] - expf(lp[o + a]) * s;
+    }
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------------------
 static int ft_dims_ok(int n_final, int n_layers, const int32_t *dims) {
     if (n_final < 0 || n_final > 3 || n_layers < 1 || n_layers > FT_MAX_LAYERS || !dims) return 0;
@@ -493,7 +534,7 @@ static int ft_dims_ok(int n_final, int n_layers, const int32_t *dims) {
 // W_s[S] only: W_s is then the one ProteinMPNN tensor in the slab.
 struct FtEncP { int64_t n1w, n1b, n2w, n2b, n3w, n3b, W1, b1, W2, b2, W3, b3, W11, b11, W12, b12, W13, b13, Win, bin, Wout, bout; };
 struct FtDecP { int64_t n1w, n1b, n2w, n2b, W1, b1, W2, b2, W3, b3, Win, bin, Wout, bout; };
-struct FtLayout { int64_t posw, posb, edgew, new_, neb, Wew, Web, Ws; FtEncP enc[3]; FtDecP dec[3]; int64_t head, total; };
+struct FtLayout { int64_t posw, posb, edgew, new_, neb, Wew, Web, Ws; FtEncP enc[3]; FtDecP dec[3]; int64_t head, total, Wo, bo; };
 
 static FtLayout ft_layout(int n_final) {
     FtLayout S{};
@@ -524,6 +565,16 @@ static FtLayout ft_layout(int n_final) {
     return S;
 }
 
+// The sequence loss's slab, a layout of its own: ProteinMPNN's tensors in state-dict order with W_out.weight [21,128] and W_out.bias
+// [21] at the end, and no head.
+static FtLayout sq_layout() {
+    FtLayout S = ft_layout(3);
+    S.Wo = S.head;
+    S.bo = S.Wo + TMPNN_VOCAB * FT_H;
+    S.total = S.bo + TMPNN_VOCAB;
+    return S;
+}
+
 static int ft_parts(int64_t M) {
     const int64_t p = (M + 63) / 64;
     return (int)(p < 1 ? 1 : p > FT_MAX_PARTS ? FT_MAX_PARTS : p);
@@ -548,18 +599,21 @@ struct FtWs {
     FtDecS dec[3];
     float *tm, *t1, *t2, *dA, *dE, *dE2, *dEd, *gx, *gb, *dEp, *dV, *dV2, *dh1, *dF, *dhS, *dH[3], *dG, *P, *CP;
     float *ftm, *fdh, *fdF;                       // the forward's temporaries: message / LayerNorm input, message sum, FFN output
+    float *lp, *dlg, *dVe;                        // the sequence loss: saved log_probs [L,21]; d logits; the encoder output's gradient
     void *head_ws, *head_ws_b;                    // the head's workspace of the forward / of the backward
     size_t head_bytes, saved_bytes, scratch_bytes, bytes;
 };
 
-static FtWs ft_carve2(void *saved, void *scratch, bool split, int64_t L, int64_t M, int lightattn, int n_layers, const int32_t *dims) {
+// seq: the sequence loss's buffers (tmpnn_seqloss_*): no mutants and no head (M = 0, dims unused), log_probs and two gradients more.
+static FtWs ft_carve2(void *saved, void *scratch, bool split, int64_t L, int64_t M, int lightattn, int n_layers, const int32_t *dims,
+                      bool seq = false) {
     FtWs w{};
     Carver sv(saved, false), sc(scratch, false);       // (a null base measures; the entries compare with the byte counts first)
     auto f = [&](int64_t n) { return sv.take<float>((size_t)n); };
     auto i32 = [&](int64_t n) { return sv.take<int32_t>((size_t)n); };
     auto fc = [&](int64_t n) { return sc.take<float>((size_t)n); };
     auto ic = [&](int64_t n) { return sc.take<int32_t>((size_t)n); };
-    const int64_t K = L < TM_KS ? L : TM_KS, E = L * K, H = FT_H, D0 = dims[0];
+    const int64_t K = L < TM_KS ? L : TM_KS, E = L * K, H = FT_H, D0 = seq ? 0 : dims[0];
     // saved
     w.offs = i32(2); w.E48 = i32(L * TM_KS); w.eidx = i32(E); w.cls = i32(E); w.rows_id = i32(M); w.status = i32(1);
     w.D48 = f(L * TM_KS); w.Ein = f(E * 416); w.E0 = f(E * H); w.nemu = f(E); w.ners = f(E); w.En = f(E * H);
@@ -577,8 +631,9 @@ static FtWs ft_carve2(void *saved, void *scratch, bool split, int64_t L, int64_t
         s.x1 = f(L * H); s.mu1 = f(L); s.rs1 = f(L); s.hV1 = f(L * H); s.fa = f(L * 4 * H); s.x2 = f(L * H); s.mu2 = f(L); s.rs2 = f(L);
         s.out = f(L * H);
     }
-    w.head_bytes = tmpnn_head_train_workspace_bytes(M, n_layers >= 1 ? (int)(D0 / H - 1) : 0, lightattn, n_layers, dims);
+    w.head_bytes = seq ? 0 : tmpnn_head_train_workspace_bytes(M, n_layers >= 1 ? (int)(D0 / H - 1) : 0, lightattn, n_layers, dims);
     w.head_ws = sv.take<char>(w.head_bytes);
+    if (seq) w.lp = f(L * TMPNN_VOCAB);
     if (split) { w.ftm = f(E * H); w.fdh = f(L * H); w.fdF = f(L * H); }
     // scratch
     w.cnt = ic(L + 1); w.cur = ic(L + 1); w.coff = ic(L + 1); w.clist = ic(E);
@@ -591,6 +646,7 @@ static FtWs ft_carve2(void *saved, void *scratch, bool split, int64_t L, int64_t
     const int64_t pe = std::max(ft_parts(E), ft_parts(L));
     w.P = fc(pe * std::max<int64_t>(H * (4 * H + 1), 4 * H * (H + 1)));
     w.CP = fc((int64_t)FT_CLS_PARTS * std::max<int64_t>(66 * 16, TMPNN_VOCAB * H));
+    if (seq) { w.dlg = fc(L * TMPNN_VOCAB); w.dVe = fc(L * H); }
     if (split) {
         w.head_ws_b = sc.take<char>(w.head_bytes);
     } else {
@@ -620,11 +676,13 @@ static int ft_grid_threads(int64_t n) {
 
 // One call's context: sizes, pointers, the dropout description.
 struct FtCtx {
-    int L, K, M, nf, lightattn, n_layers, subtract;
+    int L, K, M, nf, lightattn, n_layers, subtract, seq;
     int64_t E;
     const int32_t *dims;
     const float *X, *mask;
     const int32_t *S, *ridx, *cenc, *pos, *mut, *wt;
+    const float *dlp;                             // the sequence loss: upstream dL / dlog_probs [L,21] (backward)
+    const int32_t *ranks;                         // the sequence loss: decoding ranks [L] (null: every neighbour visible, the ddG path)
     const float *params;
     float *grads;
     FtLayout lay;
@@ -633,7 +691,7 @@ struct FtCtx {
     hipStream_t st;
 };
 
-static FtSeg ft_seg(const float *p, int ld, int width, int mode, int masked, int rows) { return FtSeg{p, ld, width, mode, masked, rows}; }
+static FtSeg ft_seg(const float *p, int ld, int width, int mode, int masked, int rows) { return FtSeg{p, ld, width, mode, masked, rows, 0, nullptr}; }
 static FtA ft_plain(const float *p, int ld, int width, int rows, int act = 0) {
     FtA a{};
     a.s[0] = ft_seg(p, ld, width, 0, 0, rows);
@@ -687,8 +745,8 @@ static void ft_ln_bwd(const FtCtx &c, const float *dy, const float *omask, const
     ft_class_sum(c, nullptr, c.w.gx, FT_H, 0, (int)R, FT_H, 1, c.grads + gofs, 0, 1);
     ft_class_sum(c, nullptr, c.w.gb, FT_H, 0, (int)R, FT_H, 1, c.grads + bofs, 0, 1);
 }
-static void ft_collect(const FtCtx &c, float *out, const float *base, const float *src, int lds, int self, int nb, int masked) {
-    FtCollect a{out, base, src, lds, self, nb, masked, c.mask, c.w.coff, c.w.clist, c.L, c.K};
+static void ft_collect(const FtCtx &c, float *out, const float *base, const float *src, int lds, int self, int nb, int masked, int vis = 0) {
+    FtCollect a{out, base, src, lds, self, nb, masked, c.mask, c.w.coff, c.w.clist, c.L, c.K, c.ranks ? vis : 0, c.ranks};
     ft_collect_kernel<<<ft_grid_threads((int64_t)c.L * FT_H), TM_THREADS, 0, c.st>>>(a);
 }
 static void ft_csr(const FtCtx &c, const int32_t *keys, int n, int nbins, int32_t *cnt, int32_t *cur, int32_t *off, int32_t *list) {
@@ -711,6 +769,12 @@ static FtA ft_msg_in(const FtCtx &c, const float *hV, const float *hE, const flo
         a.s[2] = ft_seg(hS, FT_H, FT_H, 2, 1, c.L);
         a.s[3] = ft_seg(hV, FT_H, FT_H, 2, 1, c.L);
         a.n_seg = 4;
+        if (c.ranks) {                            // the order-masked decoder: vis h_S_j | (vis ? h_V_j : h_V^enc_j)
+            a.ranks = c.ranks;
+            a.s[2].vis = 1;
+            a.s[3].vis = 2;
+            a.s[3].p2 = c.w.enc[2].out;
+        }
     } else {
         a.s[2] = ft_seg(hV, FT_H, FT_H, 2, 0, c.L);
         a.n_seg = 3;
@@ -804,6 +868,11 @@ static int ft_forward(const FtCtx &c) {
             hV = s.out;
         }
     }
+    if (c.seq) {                                  // logits = W_out h_V + b, log_probs = log_softmax(logits) (kept for the backward)
+        ft_linear(c, ft_plain(w.dec[2].out, FT_H, FT_H, L), P + S.Wo, P + S.bo, w.lp, TMPNN_VOCAB, L, TMPNN_VOCAB);
+        sq_logsoftmax_kernel<<<ft_grid_threads(L), TM_THREADS, 0, c.st>>>(w.lp, L);
+        return TMPNN_OK;
+    }
     FtHeadRows hr{{w.dec[0].out, w.dec[1].out, w.dec[2].out}, w.hS, c.pos, w.headX, w.rows_id, c.M, L, c.nf};
     ft_head_rows_kernel<<<ft_grid_threads((int64_t)c.M * FT_H * (c.nf + 1)), TM_THREADS, 0, c.st>>>(hr);
     return TMPNN_OK;
@@ -813,9 +882,18 @@ static void ft_backward(const FtCtx &c) {
     const FtWs &w = c.w;
     const FtLayout &S = c.lay;
     const int L = c.L, E = (int)c.E;
-    ft_csr(c, c.pos, c.M, L, w.mcnt, w.mcur, w.moff, w.mlist);
-    FtHeadScatter hs{w.dheadX, w.moff, w.mlist, {w.dH[0], w.dH[1], w.dH[2]}, w.dhS, L, c.nf};
-    ft_head_scatter_kernel<<<ft_grid_threads((int64_t)L * FT_H * (c.nf + 1)), TM_THREADS, 0, c.st>>>(hs);
+    if (c.seq) {
+        // the seed: dlogits = dlp - softmax sum(dlp); W_out's gradients; d h_V^dec3 = dlogits W_out. Nothing else reaches h_S or the
+        // earlier decoder outputs from outside, and the encoder output's own gradient starts at 0.
+        sq_dlogits_kernel<<<ft_grid_threads(L), TM_THREADS, 0, c.st>>>(c.dlp, w.lp, L, w.dlg);
+        ft_wgrad(c, w.dlg, TMPNN_VOCAB, ft_plain(w.dec[2].out, FT_H, FT_H, L), L, TMPNN_VOCAB, c.grads + S.Wo, c.grads + S.bo);
+        ft_linear_t(c, w.dlg, TMPNN_VOCAB, c.params + S.Wo, FT_H, w.dH[2], FT_H, L, TMPNN_VOCAB, FT_H);
+        for (float *z : {w.dH[0], w.dH[1], w.dhS, w.dVe}) (void)hipMemsetAsync(z, 0, (size_t)L * FT_H * 4, c.st);
+    } else {
+        ft_csr(c, c.pos, c.M, L, w.mcnt, w.mcur, w.moff, w.mlist);
+        FtHeadScatter hs{w.dheadX, w.moff, w.mlist, {w.dH[0], w.dH[1], w.dH[2]}, w.dhS, L, c.nf};
+        ft_head_scatter_kernel<<<ft_grid_threads((int64_t)L * FT_H * (c.nf + 1)), TM_THREADS, 0, c.st>>>(hs);
+    }
     if (c.nf > 0) {
         for (int l = 0; l < 3; ++l)                   // the decoder outputs the head does not read get no gradient from it
             if (l < 3 - c.nf) (void)hipMemsetAsync(w.dH[l], 0, (size_t)L * FT_H * 4, c.st);
@@ -834,13 +912,17 @@ static void ft_backward(const FtCtx &c) {
             ft_mlp3_bwd(c, in, w.tm, p.W1, p.b1, p.W2, p.b2, p.W3, p.b3, s.a1, s.a2);
             // dA = [d hV_i | d h_E | d h_S_j | d h_V_j] (the last three before the mask_i factor)
             ft_edge_add_kernel<<<ft_grid_threads((int64_t)E * FT_H), TM_THREADS, 0, c.st>>>(w.dEd, nullptr, w.dA, 4 * FT_H, FT_H, c.mask, 1, E, c.K);
-            ft_collect(c, w.dhS, w.dhS, w.dA, 4 * FT_H, -1, 2 * FT_H, 1);
+            // under an order (c.ranks): d h_S_j and the layer's d h_V_j take the visible edges only; d h_V_j of an invisible edge
+            // belongs to the encoder output and is summed into dVe, layer 2 first, then 1, then 0
+            ft_collect(c, w.dhS, w.dhS, w.dA, 4 * FT_H, -1, 2 * FT_H, 1, 1);
             // grad of the layer input = residual + self + neighbour terms (+ the head's, for an earlier decoder layer)
             ft_collect(c, w.dV2, w.dV2, w.dA, 4 * FT_H, 0, -1, 0);
-            ft_collect(c, w.dV, w.dV2, w.dA, 4 * FT_H, -1, 3 * FT_H, 1);
+            ft_collect(c, w.dV, w.dV2, w.dA, 4 * FT_H, -1, 3 * FT_H, 1, 1);
+            if (c.ranks) ft_collect(c, w.dVe, w.dVe, w.dA, 4 * FT_H, -1, 3 * FT_H, 1, 2);
             if (l > 0) ft_edge_add_kernel<<<ft_grid_threads((int64_t)L * FT_H), TM_THREADS, 0, c.st>>>(w.dV, nullptr, w.dH[l - 1], FT_H, 0, c.mask, 0, L, 1);
         }
         // encoder: dV = grad of the encoder output, dE = grad of h_E after the last encoder layer
+        if (c.ranks) ft_edge_add_kernel<<<ft_grid_threads((int64_t)L * FT_H), TM_THREADS, 0, c.st>>>(w.dV, nullptr, w.dVe, FT_H, 0, c.mask, 0, L, 1);
         (void)hipMemcpyAsync(w.dE, w.dEd, (size_t)E * FT_H * 4, hipMemcpyDeviceToDevice, c.st);
         for (int l = 2; l >= 0; --l) {
             const FtEncP &p = S.enc[l];
@@ -1083,4 +1165,75 @@ extern "C" int tmpnn_finetune_backward(const float *X, const int32_t *S, const f
                               mpnn_grads ? c.w.dheadX : nullptr, dpred));
     if (mpnn_grads) ft_backward(c);
     return tm_check_launch("finetune_backward");
+}
+
+// ---- the sequence loss: log p(S | X) under a decoding order, and its gradient ------------------------------------------------------
+extern "C" int64_t tmpnn_seqloss_slab_numel(void) { return sq_layout().total; }
+
+extern "C" size_t tmpnn_seqloss_saved_bytes(int64_t L) {
+    return L < 2 || L > FT_L_MAX ? 0 : ft_carve2(nullptr, nullptr, true, L, 0, 0, 0, nullptr, true).saved_bytes;
+}
+
+extern "C" size_t tmpnn_seqloss_scratch_bytes(int64_t L) {
+    return L < 2 || L > FT_L_MAX ? 0 : ft_carve2(nullptr, nullptr, true, L, 0, 0, 0, nullptr, true).scratch_bytes;
+}
+
+static int sq_check(const char *what, const float *X, const int32_t *S, const float *mask, const int32_t *ridx, const int32_t *cenc, int64_t L,
+                    int k_neighbors, const float *params, int64_t slab_numel, float p_mpnn, const void *saved, size_t saved_bytes) {
+    FT_REQUIRE(L >= 2 && L <= FT_L_MAX, "%s: protein length %lld outside [2, %lld]", what, (long long)L, (long long)FT_L_MAX);
+    FT_REQUIRE(k_neighbors >= 1 && k_neighbors <= TM_KS, "%s: k_neighbors %d outside [1, %d]", what, k_neighbors, TM_KS);
+    FT_REQUIRE(slab_numel == sq_layout().total, "%s: parameter slab holds %lld floats, ProteinMPNN with W_out needs %lld", what,
+               (long long)slab_numel, (long long)sq_layout().total);
+    FT_REQUIRE(X && S && mask && ridx && cenc && params, "%s: null pointer", what);       // (ranks may be null: every neighbour visible)
+    FT_REQUIRE(p_mpnn >= 0.f && p_mpnn < 1.f, "%s: dropout probability outside [0, 1)", what);
+    return ft_check_buf(what, "saved", (void *)saved, saved_bytes, tmpnn_seqloss_saved_bytes(L));
+}
+
+static FtCtx sq_ctx(const float *X, const int32_t *S, const float *mask, const int32_t *ridx, const int32_t *cenc, int64_t L, int k_neighbors,
+                    const int32_t *ranks, const float *params, float *grads, void *saved, void *scratch, hipStream_t st) {
+    FtCtx c{};
+    c.L = (int)L;
+    c.K = (int)(L < k_neighbors ? L : k_neighbors);
+    c.E = (int64_t)c.L * c.K;
+    c.nf = 3;
+    c.seq = 1;
+    c.X = X; c.S = S; c.mask = mask; c.ridx = ridx; c.cenc = cenc; c.ranks = ranks;
+    c.params = params;
+    c.grads = grads;
+    c.lay = sq_layout();
+    c.w = ft_carve2(saved, scratch, true, L, 0, 0, 0, nullptr, true);     // carved for K = 48: the buffers of a smaller K fit inside
+    c.st = st;
+    return c;
+}
+
+extern "C" int tmpnn_seqloss_forward(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
+                                     int64_t L, int k_neighbors, const int32_t *ranks, const float *params, int64_t slab_numel, float p_mpnn,
+                                     const float *keep_in, float *keep_out, uint64_t seed, uint64_t step, float *log_probs,
+                                     int32_t *E_idx_opt, void *saved, size_t saved_bytes, tmpnn_stream_t stream) {
+    FT_TRY(sq_check("seqloss_forward", X, S, mask, residue_idx, chain_enc, L, k_neighbors, params, slab_numel, p_mpnn, saved, saved_bytes));
+    FT_REQUIRE(log_probs, "seqloss_forward: null pointer");
+    FT_REQUIRE(!(keep_in && keep_out), "seqloss_forward: keep_in (injected masks) and keep_out (drawn masks) exclude each other");
+    FtCtx c = sq_ctx(X, S, mask, residue_idx, chain_enc, L, k_neighbors, ranks, params, nullptr, saved, nullptr, (hipStream_t)stream);
+    ft_set_drop(c, L, p_mpnn, keep_in, keep_out, seed, step);
+    if (keep_out) (void)hipMemsetAsync(keep_out, 0, (size_t)ft_mask_numel(L) * 4, c.st);   // (K < 48 leaves the edge sites' tails unwritten)
+    FT_TRY(ft_forward(c));
+    (void)hipMemcpyAsync(log_probs, c.w.lp, (size_t)L * TMPNN_VOCAB * 4, hipMemcpyDeviceToDevice, c.st);
+    if (E_idx_opt) (void)hipMemcpyAsync(E_idx_opt, c.w.eidx, (size_t)c.E * 4, hipMemcpyDeviceToDevice, c.st);
+    return tm_check_launch("seqloss_forward");
+}
+
+extern "C" int tmpnn_seqloss_backward(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
+                                      int64_t L, int k_neighbors, const int32_t *ranks, const float *params, int64_t slab_numel, float p_mpnn,
+                                      const float *keep_in, uint64_t seed, uint64_t step, const float *dlog_probs, float *grads,
+                                      const void *saved, size_t saved_bytes, void *scratch, size_t scratch_bytes, tmpnn_stream_t stream) {
+    FT_TRY(sq_check("seqloss_backward", X, S, mask, residue_idx, chain_enc, L, k_neighbors, params, slab_numel, p_mpnn, saved, saved_bytes));
+    FT_REQUIRE(dlog_probs && grads, "seqloss_backward: null pointer");
+    FT_TRY(ft_check_buf("seqloss_backward", "scratch", scratch, scratch_bytes, tmpnn_seqloss_scratch_bytes(L)));
+    // the saved part is only read: its one writer is the forward
+    FtCtx c = sq_ctx(X, S, mask, residue_idx, chain_enc, L, k_neighbors, ranks, params, grads, const_cast<void *>(saved), scratch,
+                     (hipStream_t)stream);
+    c.dlp = dlog_probs;
+    ft_set_drop(c, L, p_mpnn, keep_in, nullptr, seed, step);
+    ft_backward(c);
+    return tm_check_launch("seqloss_backward");
 }
