@@ -425,6 +425,36 @@ int tmpnn_sample_tied(const tmpnn_weights_t *w, const void *ctx, size_t ctx_byte
                       const float *pssm_bias_opt /* [T,21] */, const float *pssm_keep_opt /* [T,21] pssm_log_odds_mask */,
                       int32_t *S_out /* [N,T] */, float *probs_opt /* [N,T,21] */,
                       int32_t *status_opt, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream);
+/* The two samplers for EVERY PROTEIN of a packed batch over its own steps, in ONE launch: many backbones, a few chains each. The ctx
+ * is tmpnn_encode's for P proteins (offsets [P+1], on the device) and every [N,T] / [T,21] / [T] array keeps its meaning and its
+ * full-batch shape; chain n's schedule for protein b is order[n, t0:t1] with t0 = offsets[b], t1 = offsets[b+1] — a permutation of
+ * the packed indices t0 .. t1-1 — and the kernel's work item is (protein b, block of 16 chains), which runs the steps s in [t0, t1)
+ * only: the grid is (p1 - p0) * ceil(N / 16) workgroups for the protein range [p0, p1). A neighbour is visible iff its step is below
+ * s (packed s); all arithmetic of a step is tmpnn_sample's, so a (protein, chain) pair has the bits tmpnn_sample gives for that
+ * protein encoded alone with the segment's order shifted to local indices, whatever P, N, the range, the slot and sched_opt are.
+ * sched_opt [p1 - p0] (device) is the launch order as protein indices (longest first keeps the tail short), NULL = index order; an
+ * entry outside [p0, p1) makes its workgroups do nothing. The scratch is sized by the RANGE: row0 = offsets[p0] and
+ * rows = offsets[p1] - offsets[p0] as host integers (0 <= row0, row0 + rows <= T); the bound 3 * N * rows < 2^24 holds per launch
+ * (TMPNN_E_UNSUPPORTED beyond it, the workspace size is then 0). A step whose residue lies outside its protein or outside
+ * [row0, row0 + rows) is skipped, so a wrong pair cannot overrun the workspace. S_out / probs_opt are written for the rows of
+ * [p0, p1) only. Tied form: groups live inside one protein; close[n, t1-1] must be 1 for every protein (the caller checks it; the
+ * kernel treats a segment's last step as closing regardless). Errors, the fp32 refusal ("bf16x3"), status_opt and the no-op on
+ * N == 0, rows == 0 or p0 == p1 as tmpnn_sample; additionally TMPNN_E_INVALID for p0 > p1, p1 > P or a negative size. */
+size_t tmpnn_sample_each_workspace_bytes(int64_t rows, int64_t N);        /* 0 = unsupported sizes */
+int tmpnn_sample_each(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const float *mask, int64_t T,
+                      const int32_t *offsets /* device [P+1] */, int64_t P, int64_t p0, int64_t p1, int64_t row0, int64_t rows,
+                      const int32_t *sched_opt /* device [p1-p0] */, int64_t N, const int32_t *order, const int32_t *S_fixed,
+                      const float *free, const float *u, float inv_temperature, const float *bias_opt, const float *allowed_opt,
+                      int32_t *S_out, float *probs_opt, int32_t *status_opt, void *workspace, size_t workspace_bytes,
+                      tmpnn_stream_t stream);
+size_t tmpnn_sample_tied_each_workspace_bytes(int64_t rows, int64_t N);   /* 0 = unsupported sizes */
+int tmpnn_sample_tied_each(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const float *mask, int64_t T,
+                           const int32_t *offsets /* device [P+1] */, int64_t P, int64_t p0, int64_t p1, int64_t row0, int64_t rows,
+                           const int32_t *sched_opt /* device [p1-p0] */, int64_t N, const int32_t *order, const int32_t *close,
+                           const int32_t *S_fixed, const float *free, const float *u, float inv_temperature, const float *weight_opt,
+                           const float *bias_opt, const float *allowed_opt, const float *pssm_mix_opt, const float *pssm_bias_opt,
+                           const float *pssm_keep_opt, int32_t *S_out, float *probs_opt, int32_t *status_opt, void *workspace,
+                           size_t workspace_bytes, tmpnn_stream_t stream);
 
 /* ---- host side: native PDB reader + packer ------------------------------------------
  * Replaces alt_parse_PDB (protein_mpnn_utils.py:183-350) + the packing of tied_featurize (:353-605) for one

@@ -108,6 +108,12 @@ SIGNATURES = {
     "tmpnn_sample": (_i, [_p, _p, _sz, _p, _i64, _i64, _p, _p, _p, _p, C.c_float, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "tmpnn_sample_tied_workspace_bytes": (_sz, [_i64, _i64]),
     "tmpnn_sample_tied": (_i, [_p, _p, _sz, _p, _i64, _i64, _p, _p, _p, _p, _p, C.c_float, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "tmpnn_sample_each_workspace_bytes": (_sz, [_i64, _i64]),
+    "tmpnn_sample_each": (_i, [_p, _p, _sz, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p, C.c_float, _p, _p, _p, _p,
+                               _p, _p, _sz, _p]),
+    "tmpnn_sample_tied_each_workspace_bytes": (_sz, [_i64, _i64]),
+    "tmpnn_sample_tied_each": (_i, [_p, _p, _sz, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p, _p, C.c_float, _p, _p,
+                                    _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
 }
 # include/tmpnn_debug.h: measurement / experiment hooks (bench.py's per-kernel timing, tools/); not the operator boundary
 DEBUG_SIGNATURES = {

@@ -837,50 +837,65 @@ extern "C" size_t tmpnn_sample_workspace_bytes(int64_t T, int64_t N) {
     return sample_ws(Carver(), T, N).bytes + 256;
 }
 
-// The body of tmpnn_sample (tied == null) and tmpnn_sample_tied (`what` names the entry in messages): the same checks, workspace
-// layout and encoder-state projections; the tied form's arrays travel to the chain kernel's second form.
-static int sample_rows(const char *what, const SampleTied *tied, const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes,
-                       const float *mask, int64_t T, int64_t N, const int32_t *order, const int32_t *S_fixed, const float *free_,
-                       const float *u, float inv_temperature, const float *bias_opt, const float *allowed_opt, int32_t *S_out,
-                       float *probs_opt, int32_t *status_opt, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream) {
+// The body of tmpnn_sample (tied == null), tmpnn_sample_tied and their per-protein forms (`what` names the entry in messages): the
+// same checks, workspace layout and encoder-state projections; the tied form's arrays travel to the chain kernel's second form.
+// each != null (with P proteins): proteins [p0, p1) over the rows [row0, row0 + rows) of the batch — R below is the number of rows
+// the scratch holds (T, or `rows`), and sample_ws is the one layout of all four entries.
+static int sample_rows(const char *what, const SampleTied *tied, const SampleEach *each, int64_t P, const tmpnn_weights_t *w, const void *ctx,
+                       size_t ctx_bytes, const float *mask, int64_t T, int64_t N, const int32_t *order, const int32_t *S_fixed,
+                       const float *free_, const float *u, float inv_temperature, const float *bias_opt, const float *allowed_opt,
+                       int32_t *S_out, float *probs_opt, int32_t *status_opt, void *workspace, size_t workspace_bytes,
+                       tmpnn_stream_t stream) {
     REQUIRE(w, "%s: null weight handle", what);
     REQUIRE(T >= 0 && T <= T_MAX && N >= 0, "%s: bad sizes (T=%lld, N=%lld)", what, (long long)T, (long long)N);
-    if (T == 0 || N == 0) return TMPNN_OK;            // nothing to sample (pointers may be null)
-    if (T > SAMPLE_ROWS_MAX / 3 / N)
-        return tm_set_error(TMPNN_E_UNSUPPORTED, "%s: 3 * N * T = 3 * %lld * %lld rows exceed %lld (sample the chains in chunks)", what,
-                            (long long)N, (long long)T, (long long)SAMPLE_ROWS_MAX);
-    REQUIRE(mask && order && S_fixed && free_ && u && S_out && (!tied || tied->close), "%s: null input pointer", what);
+    if (each) {
+        REQUIRE(P >= 0 && each->p0 >= 0 && each->p0 <= each->p1 && each->p1 <= P, "%s: bad protein range (p0=%lld, p1=%lld, P=%lld)", what,
+                (long long)each->p0, (long long)each->p1, (long long)P);
+        REQUIRE(each->rows >= 0 && each->row0 >= 0 && each->rows <= T - each->row0, "%s: bad row range (row0=%lld, rows=%lld, T=%lld)", what,
+                (long long)each->row0, (long long)each->rows, (long long)T);
+    }
+    const int64_t R = each ? each->rows : T, row0 = each ? each->row0 : 0;
+    if (R == 0 || N == 0 || (each && each->p0 == each->p1)) return TMPNN_OK;      // nothing to sample (pointers may be null)
+    if (R > SAMPLE_ROWS_MAX / 3 / N)
+        return tm_set_error(TMPNN_E_UNSUPPORTED, "%s: 3 * N * %s = 3 * %lld * %lld rows exceed %lld (sample the chains in chunks)", what,
+                            each ? "rows" : "T", (long long)N, (long long)R, (long long)SAMPLE_ROWS_MAX);
+    if (each && (each->p1 - each->p0) > (int64_t)0x7fffffff / ((N + 15) / 16))
+        return tm_set_error(TMPNN_E_UNSUPPORTED, "%s: %lld proteins times %lld chain blocks exceed one grid (sample the proteins in chunks)",
+                            what, (long long)(each->p1 - each->p0), (long long)((N + 15) / 16));
+    REQUIRE(mask && order && S_fixed && free_ && u && S_out && (!tied || tied->close) && (!each || each->offsets), "%s: null input pointer",
+            what);
     REQUIRE(inv_temperature > 0.f && inv_temperature <= 3.0e38f, "%s: inv_temperature must be positive and finite", what);
     REQUIRE(!tied || (tied->pssm_mix != nullptr) == (tied->pssm_bias != nullptr), "%s: pssm_bias goes with pssm_mix (give both or neither)", what);
     EncCtx c;
     TRY(carve_ctx(what, const_cast<void *>(ctx), ctx_bytes, T, &c));
-    const size_t need = tmpnn_sample_workspace_bytes(T, N);
+    const size_t need = tmpnn_sample_workspace_bytes(R, N);
     if (!workspace || workspace_bytes < need)
         return tm_set_error(TMPNN_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
-    const SampleWs s = sample_ws(Carver(workspace, true), T, N);
+    const SampleWs s = sample_ws(Carver(workspace, true), R, N);
     // (the handle is read only now: every check above works on the arguments alone)
     if (w->mode == TM_MM_FP32)
         return tm_set_error(TMPNN_E_UNSUPPORTED, "%s: the chain kernel has no fp32 form; create the handle with precision \"bf16x3\" (or \"f16x2\")", what);
     hipStream_t st = (hipStream_t)stream;
     if (status_opt && hipMemsetAsync(status_opt, 0, 4, st) != hipSuccess) return tm_check_launch("sample: status memset");
     // residue -> step, scattered from `order` by the chain kernel's prologue; "not decoded" everywhere else
-    if (hipMemsetAsync(s.rank, 0x7f, (size_t)N * T * 4, st) != hipSuccess) return tm_check_launch("sample: rank memset");
+    if (hipMemsetAsync(s.rank, 0x7f, (size_t)N * R * 4, st) != hipSuccess) return tm_check_launch("sample: rank memset");
+    const float *hV = c.hV + (size_t)row0 * TMPNN_HID;
     {   // the later layers' projections of the ENCODER state (layer 0's is the ctx's P0), as the ordered decode makes them
         const NodeProj p1 = dec_msg_proj(w, 1, s.Penc1, nullptr), p2 = dec_msg_proj(w, 2, s.Penc2, nullptr);
-        TRY(launch_node_proj(c.hV, p1, T, st));
-        TRY(launch_node_proj(c.hV, p2, T, st));
+        TRY(launch_node_proj(hV, p1, R, st));
+        TRY(launch_node_proj(hV, p2, R, st));
     }
-    const float *Penc[3] = {c.P0, s.Penc1, s.Penc2};
+    const float *Penc[3] = {c.P0 + (size_t)row0 * 256, s.Penc1, s.Penc2};
     return launch_sample_chains(w, c.hE, c.E_idx, c.hV, c.P0, Penc, mask, T, N, order, S_fixed, free_, u, inv_temperature, bias_opt,
-                                allowed_opt, S_out, probs_opt, status_opt, s.tab, s.rank, tied, st);
+                                allowed_opt, S_out, probs_opt, status_opt, s.tab, s.rank, tied, each, st);
 }
 
 extern "C" int tmpnn_sample(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const float *mask, int64_t T, int64_t N,
                             const int32_t *order, const int32_t *S_fixed, const float *free_, const float *u, float inv_temperature,
                             const float *bias_opt, const float *allowed_opt, int32_t *S_out, float *probs_opt, int32_t *status_opt,
                             void *workspace, size_t workspace_bytes, tmpnn_stream_t stream) {
-    return sample_rows("sample", nullptr, w, ctx, ctx_bytes, mask, T, N, order, S_fixed, free_, u, inv_temperature, bias_opt, allowed_opt,
-                       S_out, probs_opt, status_opt, workspace, workspace_bytes, stream);
+    return sample_rows("sample", nullptr, nullptr, 0, w, ctx, ctx_bytes, mask, T, N, order, S_fixed, free_, u, inv_temperature, bias_opt,
+                       allowed_opt, S_out, probs_opt, status_opt, workspace, workspace_bytes, stream);
 }
 
 // The tied form has tmpnn_sample's workspace (one layout, sample_ws): a chain's group state lives in the chain kernel's LDS.
@@ -892,6 +907,34 @@ extern "C" int tmpnn_sample_tied(const tmpnn_weights_t *w, const void *ctx, size
                                  const float *pssm_mix_opt, const float *pssm_bias_opt, const float *pssm_keep_opt, int32_t *S_out,
                                  float *probs_opt, int32_t *status_opt, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream) {
     const SampleTied tied{close, weight_opt, pssm_mix_opt, pssm_bias_opt, pssm_keep_opt};
-    return sample_rows("sample_tied", &tied, w, ctx, ctx_bytes, mask, T, N, order, S_fixed, free_, u, inv_temperature, bias_opt, allowed_opt,
-                       S_out, probs_opt, status_opt, workspace, workspace_bytes, stream);
+    return sample_rows("sample_tied", &tied, nullptr, 0, w, ctx, ctx_bytes, mask, T, N, order, S_fixed, free_, u, inv_temperature, bias_opt,
+                       allowed_opt, S_out, probs_opt, status_opt, workspace, workspace_bytes, stream);
+}
+
+// ---- the same for every protein of a packed batch over its own steps ----------------------------------------------------------
+// sample_ws again, with the range's rows where the whole-axis entries have T: the scratch is sized by the protein range.
+extern "C" size_t tmpnn_sample_each_workspace_bytes(int64_t rows, int64_t N) { return tmpnn_sample_workspace_bytes(rows, N); }
+extern "C" size_t tmpnn_sample_tied_each_workspace_bytes(int64_t rows, int64_t N) { return tmpnn_sample_workspace_bytes(rows, N); }
+
+extern "C" int tmpnn_sample_each(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const float *mask, int64_t T,
+                                 const int32_t *offsets, int64_t P, int64_t p0, int64_t p1, int64_t row0, int64_t rows,
+                                 const int32_t *sched_opt, int64_t N, const int32_t *order, const int32_t *S_fixed, const float *free_,
+                                 const float *u, float inv_temperature, const float *bias_opt, const float *allowed_opt, int32_t *S_out,
+                                 float *probs_opt, int32_t *status_opt, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream) {
+    const SampleEach each{offsets, sched_opt, p0, p1, row0, rows};
+    return sample_rows("sample_each", nullptr, &each, P, w, ctx, ctx_bytes, mask, T, N, order, S_fixed, free_, u, inv_temperature, bias_opt,
+                       allowed_opt, S_out, probs_opt, status_opt, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tmpnn_sample_tied_each(const tmpnn_weights_t *w, const void *ctx, size_t ctx_bytes, const float *mask, int64_t T,
+                                      const int32_t *offsets, int64_t P, int64_t p0, int64_t p1, int64_t row0, int64_t rows,
+                                      const int32_t *sched_opt, int64_t N, const int32_t *order, const int32_t *close,
+                                      const int32_t *S_fixed, const float *free_, const float *u, float inv_temperature,
+                                      const float *weight_opt, const float *bias_opt, const float *allowed_opt, const float *pssm_mix_opt,
+                                      const float *pssm_bias_opt, const float *pssm_keep_opt, int32_t *S_out, float *probs_opt,
+                                      int32_t *status_opt, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream) {
+    const SampleTied tied{close, weight_opt, pssm_mix_opt, pssm_bias_opt, pssm_keep_opt};
+    const SampleEach each{offsets, sched_opt, p0, p1, row0, rows};
+    return sample_rows("sample_tied_each", &tied, &each, P, w, ctx, ctx_bytes, mask, T, N, order, S_fixed, free_, u, inv_temperature,
+                       bias_opt, allowed_opt, S_out, probs_opt, status_opt, workspace, workspace_bytes, stream);
 }

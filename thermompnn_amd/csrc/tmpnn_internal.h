@@ -198,10 +198,14 @@ int launch_variant_hidden(const float *const *h, int64_t T, int64_t V, float *ou
 // (tmpnn_sample). Penc[l] [T,256]: projections of the encoder state; rank [N,T] (pre-filled with a large value) and tab [N,3,T,128]: scratch
 // the tied form's extra arrays (tmpnn_sample_tied): close [N,T]; weight [N,T] by residue or null; the PSSM tables or null
 struct SampleTied { const int32_t *close; const float *weight, *pssm_mix, *pssm_bias, *pssm_keep; };
+// the per-protein form (tmpnn_sample_each): proteins [p0, p1) of offsets [P+1], each over its own steps; Penc / rank / tab then hold
+// the rows [row0, row0 + rows) only; sched [p1 - p0] or null: the launch order as protein indices
+struct SampleEach { const int32_t *offsets, *sched; int64_t p0, p1, row0, rows; };
 int launch_sample_chains(const tmpnn_weights *w, const float *hE, const int32_t *E_idx, const float *hV, const float *P0,
                          const float *const *Penc, const float *mask, int64_t T, int64_t N, const int32_t *order, const int32_t *S_fixed,
                          const float *free_, const float *u, float inv_temp, const float *bias, const float *allowed, int32_t *S_out,
-                         float *probs, int32_t *status, float *tab, int32_t *rank, const SampleTied *tied, hipStream_t st);
+                         float *probs, int32_t *status, float *tab, int32_t *rank, const SampleTied *tied, const SampleEach *each,
+                         hipStream_t st);
 int launch_selftest(int32_t *status, hipStream_t st);
 int tm_num_cus();
 // Kernel-form switches (TMPNN_KNN_REG, TMPNN_NODE_DEEP, TMPNN_FUSE_SMALL ...) and the per-phase timers (TMPNN_*_PROF, which

@@ -1,5 +1,5 @@
-// Autoregressive sampling over one encoded backbone (tmpnn_sample, tmpnn_sample_tied; protein_mpnn_utils.py:1279-1494):
-// sample_chain_kernel<SP, TIED>.
+// Autoregressive sampling over one encoded backbone (tmpnn_sample, tmpnn_sample_tied; protein_mpnn_utils.py:1279-1494) and over
+// every protein of a packed batch on its own steps (tmpnn_sample_each, tmpnn_sample_tied_each): sample_chain_kernel<SP, TIED, EACH>.
 //
 // A CHAIN is one sequence being sampled over the packed residue axis (T rows); N chains per call, each with its own decoding order,
 // fixed positions and uniform draws. One workgroup (512 threads, 8 wavefronts) owns a group of up to 16 chains and loops over the T
@@ -39,7 +39,22 @@
 // load and a store of the same address by the lanes that stored the row before (the chain's half-wavefront), in program order. Rows
 // are whole 128-byte lines (512 bytes, 256-byte-aligned base), so no line holds part of a row already written and part of one still
 // to be written. The rank array (residue -> step, the host fills it with a large value, the prologue scatters `order` into it) is
-// complete before its first load.
+// complete before its first load. All of this holds for the per-protein form as it stands: a work item there is one workgroup too,
+// the rows of the table and of the rank array it touches are those of ITS chains at ITS protein's residues (a step or a neighbour
+// outside [t0, t1) is skipped before anything is indexed with it), so no two workgroups share a row, and the same release ->
+// barrier -> acquire stands between a step's writes and the next step's gathers.
+//
+// Per-protein form (sample_chain_kernel<SP, TIED, true>; tmpnn_sample_each, tmpnn_sample_tied_each). The ctx is a packed batch of P
+// proteins and a WORK ITEM is (protein b, block of 16 chains): workgroup i of the (p1 - p0) * ceil(N / 16) takes the protein
+// sched[i / nblk] (or p0 + i / nblk) and the chain block i % nblk, reads t0 = offsets[b], t1 = offsets[b + 1] and runs the prologue
+// and the step loop for s in [t0, t1) only; chain n's schedule for the protein is order[n, t0:t1], a permutation of t0..t1-1.
+// Every [N,T] / [T,21] array is indexed by the packed residue as before; the scratch (table, rank array, the encoder state's
+// projections) holds the rows [row0, row0 + rows) of the launch's protein range and is indexed with t - row0, [t0, t1) is clipped to
+// that window, and a step whose residue falls outside it is skipped as an out-of-range entry is. Visibility is rank < s with the
+// packed s, which compares as the local step does; the arithmetic of a step is untouched and E_idx never leaves the protein, so a
+// (protein, chain) pair has the bits of tmpnn_sample on that protein encoded alone. Tied: the first group opens at s = t0 and
+// the segment's last step closes regardless of `close` (the host refuses a batch where it would not). The EACH = false forms take
+// t0 = 0, t1 = T, row0 = 0, rows = T as constants: they are the kernels as they were.
 //
 // Safe indices. An `order` entry outside [0, T) skips the step for that chain (nothing is dereferenced with it); letters are clamped to
 // [0, 21) before they reach a table; non-finite logits or probabilities OR TMPNN_STATUS_RANGE and the step takes S_fixed.
@@ -79,6 +94,9 @@ struct SampleArgs {
     const int32_t *close;                            // [N,T] 1 = the step ends its group
     const float *weight;                             // [N,T] by residue, or null (1)
     const float *pssm_mix, *pssm_bias, *pssm_keep;   // [T], [T,21], [T,21] or null
+    // per-protein form only (sample_chain_kernel<SP, TIED, true>): tab / rank / Penc hold the rows [row0, row0 + rows) of the batch
+    const int32_t *offsets, *sched;                  // [P+1]; [np] launch order as protein indices, or null (index order)
+    int p0, np, row0, rows;
 };
 
 // 16-row fp32 GEMM unit: columns [n0 + 16 wv, +16) of W (rows of the weight matrix) against the swizzled [16,128] tile
@@ -199,7 +217,7 @@ __device__ __forceinline__ void tied_epilogue(const SampleArgs &a, int c, int t,
     for (int k = 0; k < TMPNN_VOCAB; ++k) logit[k] = p[k];
 }
 
-template <typename SP, bool TIED>
+template <typename SP, bool TIED, bool EACH>
 __global__ __launch_bounds__(512) void sample_chain_kernel(SampleArgs a) {
     constexpr int TILEB = SP::NP * SPLIT_PLANE_BYTES, NC = TM_SAMPLE_CHAINS;
     constexpr bool PERM = SP::NP == 2;
@@ -222,31 +240,47 @@ __global__ __launch_bounds__(512) void sample_chain_kernel(SampleArgs a) {
     const int ncol = 16 * wv + 4 * q, c4 = 4 * wv + q;
     const int c4s = PERM ? perm_c4(c4) : c4;
     const int c32 = lane & 31, hw = tid >> 5;                       // row phases: half-wavefront hw owns row hw
-    const int T = a.T, cg0 = tm_bid() * NC;
+    const int T = a.T;
     const f4 z4 = f4{0.f, 0.f, 0.f, 0.f};
+    // steps [t0, t1) over residues [t0, t1); scratch rows are t - r0 of TR (the whole axis unless EACH)
+    int cg0 = tm_bid() * NC, t0 = 0, t1 = T, r0 = 0, TR = T;
+    if constexpr (EACH) {                                           // work item (protein b, block of 16 chains); all of it workgroup-uniform
+        const int nblk = (a.N + NC - 1) / NC, pi = tm_bid() / nblk;
+        cg0 = (tm_bid() - pi * nblk) * NC;
+        const int b = a.sched ? a.sched[pi] : a.p0 + pi;
+        if (b < a.p0 || b >= a.p0 + a.np) return;
+        r0 = a.row0;
+        TR = a.rows;
+        const int lo = r0 > 0 ? r0 : 0, hi = r0 + TR < T ? r0 + TR : T;     // a step outside the scratch's rows is skipped
+        t0 = a.offsets[b];
+        t1 = a.offsets[b + 1];
+        t0 = t0 > lo ? t0 : lo;
+        t1 = t1 < hi ? t1 : hi;
+        if (t1 <= t0) return;
+    }
 
     // ---- prologue: rank[c][order[c][s]] = s
     for (int r = 0; r < NC; ++r) {
         const int c = cg0 + r;
         if (c >= a.N) break;
-        for (int s = tid; s < T; s += 512) {
+        for (int s = t0 + tid; s < t1; s += 512) {
             const int t = a.order[(size_t)c * T + s];
-            if (t >= 0 && t < T) a.rank[(size_t)c * T + t] = s;
+            if (t >= t0 && t < t1) a.rank[(size_t)c * TR + (t - r0)] = s;
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 
-    for (int s = 0; s < T; ++s) {
+    for (int s = t0; s < t1; ++s) {
         // ---- the step's residues
         if (tid < NC) {
             const int c = cg0 + tid, cc = c < a.N ? c : a.N - 1;
             const int t = a.order[(size_t)cc * T + s];
-            const bool ok = c < a.N && t >= 0 && t < T;
+            const bool ok = c < a.N && t >= t0 && t < t1;
             s_t[tid] = ok ? t : -1;
             if constexpr (TIED) {
-                if (s == 0 || s_close[tid]) {                       // the step before closed a group: a new one opens here
+                if (s == t0 || s_close[tid]) {                       // the step before closed a group: a new one opens here
                     s_gs[tid] = s;
                     s_dead[tid] = 0;
                     s_bad[tid] = 0;
@@ -254,6 +288,9 @@ __global__ __launch_bounds__(512) void sample_chain_kernel(SampleArgs a) {
                     for (int k = 0; k < TMPNN_VOCAB; ++k) s_acc[tid][k] = 0.f;
                 }
                 s_close[tid] = c < a.N ? (a.close[(size_t)cc * T + s] != 0 ? 1 : 0) : 1;
+                if constexpr (EACH) {
+                    if (s == t1 - 1) s_close[tid] = 1;              // a segment's last step closes regardless
+                }
                 const float mk = ok ? a.mask[t] : 0.f;
                 if (ok && !s_dead[tid] && mk == 0.f) {              // the reference's break (:1444-1450): the group is dead from t on
                     s_dead[tid] = 1;
@@ -272,10 +309,13 @@ __global__ __launch_bounds__(512) void sample_chain_kernel(SampleArgs a) {
                 const int c = cg0 + r, cc = c < a.N ? c : a.N - 1;
                 int j = -1;
                 if (lane < TM_KS) j = a.E_idx[(size_t)tt * TM_KS + lane];
-                if (j >= T) j = -1;                                 // (never on a ctx of tmpnn_encode)
+                if (j >= t1) j = -1;                                // (never on a ctx of tmpnn_encode)
+                if constexpr (EACH) {
+                    if (j < t0) j = -1;                             // (nor this: E_idx never leaves the protein)
+                }
                 const unsigned long long have = __ballot(j >= 0);
                 int vis = 0;
-                if (j >= 0) vis = a.rank[(size_t)cc * T + j] < s ? 1 : 0;
+                if (j >= 0) vis = a.rank[(size_t)cc * TR + (j - r0)] < s ? 1 : 0;
                 if (lane < TM_KS) {
                     s_j[r][lane] = j;
                     s_vis[r][lane] = vis;
@@ -319,7 +359,7 @@ __global__ __launch_bounds__(512) void sample_chain_kernel(SampleArgs a) {
 #pragma unroll
                     for (int it = 0; it < 3; ++it) store_split<SP>(tA[1], prow + 2 * it, pcs, e[it]);
                     __syncthreads();                                // e planes complete; tA[0] free (every wavefront is past GEMM 2 of the row before)
-                    const float *tabc = a.tab + ((size_t)c * 3 + l) * (size_t)T * TM_H;
+                    const float *tabc = a.tab + ((size_t)c * 3 + l) * (size_t)TR * TM_H;
                     f4 gj[3];
                     float ma[3];
 #pragma unroll
@@ -327,7 +367,7 @@ __global__ __launch_bounds__(512) void sample_chain_kernel(SampleArgs a) {
                         const int j0 = s_j[r][16 * rb + m];
                         const int jj = j0 < 0 ? t : j0;
                         ma[rb] = j0 < 0 ? 0.f : 1.f;
-                        const float *p = s_vis[r][16 * rb + m] ? tabc + (size_t)jj * TM_H + ncol : L.Penc + (size_t)jj * 256 + 128 + ncol;
+                        const float *p = s_vis[r][16 * rb + m] ? tabc + (size_t)(jj - r0) * TM_H + ncol : L.Penc + (size_t)(jj - r0) * 256 + 128 + ncol;
                         gj[rb] = ld4(p);
                     }
                     const f4 g0 = ld4(s_own + r * TM_H + ncol);
@@ -505,32 +545,32 @@ __global__ __launch_bounds__(512) void sample_chain_kernel(SampleArgs a) {
             if (c < a.N) {
                 const bool closing = s_close[hw] != 0;
                 const int S = s_S[hw];
-                float *tabc = a.tab + (size_t)c * 3 * (size_t)T * TM_H + 4 * c32;
+                float *tabc = a.tab + (size_t)c * 3 * (size_t)TR * TM_H + 4 * c32;
                 const float *sq0 = a.L[0].seq_tab + S * TM_H + 4 * c32, *sq1 = a.L[1].seq_tab + S * TM_H + 4 * c32,
                             *sq2 = a.L[2].seq_tab + S * TM_H + 4 * c32;
                 if (t >= 0) {
-                    float *row = tabc + (size_t)t * TM_H;
+                    float *row = tabc + (size_t)(t - r0) * TM_H;
                     const f4 n0 = ld4(a.P0 + (size_t)t * 256 + 128 + 4 * c32);
                     const f4 n1 = ld4(s_nb[0] + hw * TM_H + 4 * c32), n2 = ld4(s_nb[1] + hw * TM_H + 4 * c32);
                     if (closing) {
                         st4(row, ld4(sq0) + n0);
-                        st4(row + (size_t)T * TM_H, ld4(sq1) + n1);
-                        st4(row + 2 * (size_t)T * TM_H, ld4(sq2) + n2);
+                        st4(row + (size_t)TR * TM_H, ld4(sq1) + n1);
+                        st4(row + 2 * (size_t)TR * TM_H, ld4(sq2) + n2);
                     } else {
                         st4(row, n0);
-                        st4(row + (size_t)T * TM_H, n1);
-                        st4(row + 2 * (size_t)T * TM_H, n2);
+                        st4(row + (size_t)TR * TM_H, n1);
+                        st4(row + 2 * (size_t)TR * TM_H, n2);
                     }
                 }
                 if (closing) {
                     for (int sp = s_gs[hw]; sp <= s; ++sp) {
                         const int tp = a.order[(size_t)c * T + sp];
-                        if (tp < 0 || tp >= T) continue;
+                        if (tp < t0 || tp >= t1) continue;
                         if (sp < s) {
-                            float *row = tabc + (size_t)tp * TM_H;
+                            float *row = tabc + (size_t)(tp - r0) * TM_H;
                             st4(row, ld4(row) + ld4(sq0));
-                            st4(row + (size_t)T * TM_H, ld4(row + (size_t)T * TM_H) + ld4(sq1));
-                            st4(row + 2 * (size_t)T * TM_H, ld4(row + 2 * (size_t)T * TM_H) + ld4(sq2));
+                            st4(row + (size_t)TR * TM_H, ld4(row + (size_t)TR * TM_H) + ld4(sq1));
+                            st4(row + 2 * (size_t)TR * TM_H, ld4(row + 2 * (size_t)TR * TM_H) + ld4(sq2));
                         }
                         const size_t cp = (size_t)c * T + tp;
                         if (c32 == 0) a.S_out[cp] = S;
@@ -542,11 +582,11 @@ __global__ __launch_bounds__(512) void sample_chain_kernel(SampleArgs a) {
             const int t = s_t[hw];
             if (t >= 0) {
                 const int S = s_S[hw];
-                float *row = a.tab + (size_t)(cg0 + hw) * 3 * (size_t)T * TM_H + (size_t)t * TM_H + 4 * c32;
+                float *row = a.tab + (size_t)(cg0 + hw) * 3 * (size_t)TR * TM_H + (size_t)(t - r0) * TM_H + 4 * c32;
                 const f4 n0 = ld4(a.P0 + (size_t)t * 256 + 128 + 4 * c32);
                 st4(row, ld4(a.L[0].seq_tab + S * TM_H + 4 * c32) + n0);
-                st4(row + (size_t)T * TM_H, ld4(a.L[1].seq_tab + S * TM_H + 4 * c32) + ld4(s_nb[0] + hw * TM_H + 4 * c32));
-                st4(row + 2 * (size_t)T * TM_H, ld4(a.L[2].seq_tab + S * TM_H + 4 * c32) + ld4(s_nb[1] + hw * TM_H + 4 * c32));
+                st4(row + (size_t)TR * TM_H, ld4(a.L[1].seq_tab + S * TM_H + 4 * c32) + ld4(s_nb[0] + hw * TM_H + 4 * c32));
+                st4(row + 2 * (size_t)TR * TM_H, ld4(a.L[2].seq_tab + S * TM_H + 4 * c32) + ld4(s_nb[1] + hw * TM_H + 4 * c32));
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -557,11 +597,20 @@ __global__ __launch_bounds__(512) void sample_chain_kernel(SampleArgs a) {
 
 // Precision by the handle's mode (f16x2 | bf16x3; the caller refuses fp32). Penc[l]: [T,256] projections of the encoder state
 // (layer 0: the ctx's P0). rank [N,T] and tab [N,3,T,128] are scratch. `tied` (or null) selects the tied form and carries its
-// arrays. Reads no environment, allocates nothing, never synchronises.
+// arrays. `each` (or null) selects the per-protein form: the grid is (p1 - p0) * ceil(N / 16) workgroups, and Penc[l], rank and tab
+// then hold the rows [row0, row0 + rows) only ([rows,256], [N,rows], [N,3,rows,128]; Penc[0] = P0 + 256 row0).
+// Reads no environment, allocates nothing, never synchronises.
+template <bool TIED, bool EACH>
+static void sample_chains_go(bool h2, int grid, const SampleArgs &a, hipStream_t st) {
+    if (h2) sample_chain_kernel<SplitH2, TIED, EACH><<<grid, 512, 0, st>>>(a);
+    else sample_chain_kernel<SplitBF3, TIED, EACH><<<grid, 512, 0, st>>>(a);
+}
+
 int launch_sample_chains(const tmpnn_weights *w, const float *hE, const int32_t *E_idx, const float *hV, const float *P0,
                          const float *const *Penc, const float *mask, int64_t T, int64_t N, const int32_t *order, const int32_t *S_fixed,
                          const float *free_, const float *u, float inv_temp, const float *bias, const float *allowed, int32_t *S_out,
-                         float *probs, int32_t *status, float *tab, int32_t *rank, const SampleTied *tied, hipStream_t st) {
+                         float *probs, int32_t *status, float *tab, int32_t *rank, const SampleTied *tied, const SampleEach *each,
+                         hipStream_t st) {
     SampleArgs a{};
     const bool h2 = w->mode == TM_MM_F16X2;
     for (int l = 0; l < 3; ++l) {
@@ -583,18 +632,21 @@ int launch_sample_chains(const tmpnn_weights *w, const float *hE, const int32_t 
     a.order = order; a.S_fixed = S_fixed; a.free_ = free_; a.u = u; a.inv_temp = inv_temp; a.bias = bias; a.allowed = allowed;
     a.S_out = S_out; a.probs = probs; a.status = status; a.tab = tab; a.rank = rank;
     a.T = (int)T; a.N = (int)N;
-    const int grid = (int)((N + TM_SAMPLE_CHAINS - 1) / TM_SAMPLE_CHAINS);
+    int grid = (int)((N + TM_SAMPLE_CHAINS - 1) / TM_SAMPLE_CHAINS);
+    if (each) {
+        a.offsets = each->offsets; a.sched = each->sched;
+        a.p0 = (int)each->p0; a.np = (int)(each->p1 - each->p0); a.row0 = (int)each->row0; a.rows = (int)each->rows;
+        grid *= a.np;
+    }
     if (tied) {
         a.close = tied->close; a.weight = tied->weight; a.pssm_mix = tied->pssm_mix; a.pssm_bias = tied->pssm_bias; a.pssm_keep = tied->pssm_keep;
-        tm_prof_begin("sample_chains_tied", st);
-        if (h2) sample_chain_kernel<SplitH2, true><<<grid, 512, 0, st>>>(a);
-        else sample_chain_kernel<SplitBF3, true><<<grid, 512, 0, st>>>(a);
-        tm_prof_end(st);
-        return tm_check_launch("sample_chains_tied");
     }
-    tm_prof_begin("sample_chains", st);
-    if (h2) sample_chain_kernel<SplitH2, false><<<grid, 512, 0, st>>>(a);
-    else sample_chain_kernel<SplitBF3, false><<<grid, 512, 0, st>>>(a);
+    const char *name = tied ? (each ? "sample_chains_tied_each" : "sample_chains_tied") : each ? "sample_chains_each" : "sample_chains";
+    tm_prof_begin(name, st);
+    if (tied && each) sample_chains_go<true, true>(h2, grid, a, st);
+    else if (tied) sample_chains_go<true, false>(h2, grid, a, st);
+    else if (each) sample_chains_go<false, true>(h2, grid, a, st);
+    else sample_chains_go<false, false>(h2, grid, a, st);
     tm_prof_end(st);
-    return tm_check_launch("sample_chains");
+    return tm_check_launch(name);
 }

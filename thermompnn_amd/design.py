@@ -80,8 +80,8 @@ class ProteinMPNNDesign(ProteinMPNN):
     """``ProteinMPNN`` with the reference's ``tied_sample`` and the PSSM flags of ``sample``."""
 
     def _run_tied(self, what, X, S_true, chain_encoding_all, residue_idx, mask, temperature, pk, generator, uniforms):
-        """The members as chains of ``Engine.sample_tied``: one encode when they share the structure and the per-residue tables,
-        one per member otherwise. -> (S [B,L] int64, probs [B,L,21])."""
+        """The members as chains of ``Engine.sample_tied``: one encode when they share the structure and the per-residue tables;
+        otherwise one padded encode and ``Engine.sample_tied_each``, member b as one chain over protein b's own steps. -> (S [B,L] int64, probs [B,L,21])."""
         if not float(temperature) > 0.0:
             raise ValueError(f"{what}: temperature must be positive, got {temperature!r}")
         eng = self.engine()
@@ -98,17 +98,20 @@ class ProteinMPNNDesign(ProteinMPNN):
             same = lambda t: t is None or bool((t[1:] == t[:1]).all())
             shared = B > 1 and all(same(t) for t in (X.to(dev), mask.to(dev), residue_idx.to(dev), chain_encoding_all.to(dev),
                                                      *(pk[k] for k in tables)))
-            groups = [slice(0, B)] if shared or B == 1 else [slice(b, b + 1) for b in range(B)]
-            S = torch.empty((B, L), dtype=torch.int64, device=dev)
-            probs = torch.empty((B, L, 21), dtype=torch.float32, device=dev)
-            for g in groups:
-                b = g.start
-                enc = self._encode_padded(eng, X[b:b + 1], mask[b:b + 1], residue_idx[b:b + 1], chain_encoding_all[b:b + 1])
-                r = eng.sample_tied(enc, pk["decoding_order"][g], pk["close"][g], S_true[g], pk["free"][g], u[g],
-                                    temperature=float(temperature), weight=None if pk["weight"] is None else pk["weight"][g],
-                                    **{k: None if pk[k] is None else pk[k][b] for k in tables})
-                S[g], probs[g] = r["S"].to(torch.int64), r["probs"]
-        return S, probs
+            if shared or B == 1:
+                enc = self._encode_padded(eng, X[:1], mask[:1], residue_idx[:1], chain_encoding_all[:1])
+                r = eng.sample_tied(enc, pk["decoding_order"], pk["close"], S_true, pk["free"], u, temperature=float(temperature),
+                                    weight=pk["weight"], **{k: None if pk[k] is None else pk[k][0] for k in tables})
+                return r["S"].to(torch.int64), r["probs"]
+            # ONE padded encode and ONE launch: member b is protein b of the packed axis, one chain over its own steps
+            enc = self._encode_padded(eng, X, mask, residue_idx, chain_encoding_all)
+            flat = lambda t: None if t is None else t.reshape(B * L, *t.shape[2:])
+            order = pk["decoding_order"]
+            shift = (torch.arange(B, device=dev, dtype=order.dtype) * L)[:, None]
+            row = lambda t: None if t is None else flat(t)[None]
+            r = eng.sample_tied_each(enc, row(order + shift), row(pk["close"]), row(S_true), row(pk["free"]), row(u),
+                                     temperature=float(temperature), weight=row(pk["weight"]), **{k: flat(pk[k]) for k in tables})
+        return r["S"].view(B, L).to(torch.int64), r["probs"].view(B, L, 21)
 
     def tied_sample(self, X, randn, S_true, chain_mask, chain_encoding_all, residue_idx, mask=None, temperature=1.0,
                     omit_AAs_np=None, bias_AAs_np=None, chain_M_pos=None, omit_AA_mask=None, pssm_coef=None,

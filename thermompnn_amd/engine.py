@@ -441,6 +441,10 @@ class Engine:
         """``launch(e, w, ws, i0, i1)`` for every chunk of at most ``per`` of ``n`` items, each with the engine's status word, on
         ``enc`` and a workspace of ``need`` bytes; the OR of the chunks' words (one read-back) goes through ``range_retry``, whose
         rerun encodes the backbone again at the retry precision. ``stacklevel``: as ``warnings.warn`` counts from the caller."""
+        self._chunks(what, enc, [(i0, min(n, i0 + per)) for i0 in range(0, n, per)], need, launch, check_status, stacklevel + 1)
+
+    def _chunks(self, what: str, enc: "EncodedBackbone", chunks, need: int, launch, check_status: bool, stacklevel: int):
+        """``launch(e, w, ws, *chunk)`` for every chunk (the body of ``_chunked``; ``sample_each`` plans its own chunks)."""
         def run(precision: str) -> int:
             e = enc
             if precision != enc.precision:
@@ -448,8 +452,8 @@ class Engine:
                 e = self.encode(X, enc.mask, ridx, cenc, enc.offsets, max_len=max_len, precision=precision)
             w, ws = self.weights_for(precision), self._workspace(need)
             status = torch.zeros(1, dtype=torch.int32, device=self.device)
-            for i0 in range(0, n, per):
-                launch(e, w, ws, i0, min(n, i0 + per))
+            for chunk in chunks:
+                launch(e, w, ws, *chunk)
                 status.bitwise_or_(self._status)
             return int(status.item()) if check_status else 0
 
@@ -571,6 +575,107 @@ class Engine:
         self._chunked("sample_tied", enc, N, per, need, launch, check_status, stacklevel=2)
         return res
 
+    # -- the samplers for every protein of a packed batch over its own steps -------------------------------------------
+    def sample_each(self, enc: "EncodedBackbone", order, S_fixed, free, u, temperature: float = 1.0, bias=None, allowed=None,
+                    max_rows: Optional[int] = None, check_status: bool = True):
+        """``sample`` for MANY backbones at once (tmpnn_sample_each): ``enc`` is a packed batch of P proteins, every argument keeps
+        ``sample``'s meaning and full-batch shape, and chain n's schedule for protein b is ``order[n, t0:t1]`` (t0, t1 =
+        offsets[b], offsets[b + 1]), a permutation of the packed indices t0..t1-1. A workgroup owns (protein, 16 chains) and walks
+        the protein's own steps, so a launch runs P * ceil(N / 16) workgroups over max(L) steps where ``sample`` on the packed
+        context runs ceil(N / 16) over T. -> dict(S [N,T] int32, probs [N,T,21]); a (protein, chain) result has the bits
+        ``sample`` gives for that protein encoded alone with the segment's order shifted to local indices. A chunk is a protein
+        range times a chain range of at most ``max_rows`` rows (chains * residues of the range; default 2**18; one protein and
+        one chain at least), long proteins launched first; results do not depend on the chunking. Range contract as ``sample``."""
+        return self._sample_each("sample_each", None, enc, order, S_fixed, free, u, temperature, None, bias, allowed, None, None, None,
+                                 max_rows, check_status)
+
+    def sample_tied_each(self, enc: "EncodedBackbone", order, close, S_fixed, free, u, temperature: float = 1.0, weight=None, bias=None,
+                         allowed=None, pssm_mix=None, pssm_bias=None, pssm_keep=None, max_rows: Optional[int] = None,
+                         check_status: bool = True):
+        """``sample_tied`` for every protein of a packed batch over its own steps (tmpnn_sample_tied_each): arguments as
+        ``sample_tied``, schedule, chunking and bits as ``sample_each``. Groups live inside one protein: every protein's last step
+        must close (close[n, offsets[b + 1] - 1] == 1)."""
+        return self._sample_each("sample_tied_each", close, enc, order, S_fixed, free, u, temperature, weight, bias, allowed, pssm_mix,
+                                 pssm_bias, pssm_keep, max_rows, check_status)
+
+    def _sample_each(self, what: str, close, enc: "EncodedBackbone", order, S_fixed, free, u, temperature, weight, bias, allowed,
+                     pssm_mix, pssm_bias, pssm_keep, max_rows: Optional[int], check_status: bool):
+        """The body of sample_each (close is None) and sample_tied_each."""
+        tied = close is not None
+        T, dev = enc.T, self.device
+        O, S0 = self._i32(order), self._i32(S_fixed)
+        Cl = self._i32(close) if tied else None
+        Fr, U = self._f32(free), self._f32(u)
+        Wt = None if weight is None else self._f32(weight)
+        for name, t in (("order", O), ("close", Cl), ("S_fixed", S0), ("free", Fr), ("u", U), ("weight", Wt)):
+            if t is not None and (t.dim() != 2 or t.shape[1] != T or t.shape[0] != O.shape[0]):
+                raise TmpnnError(f"{what}: {name} must be [N, {T}] like order, got {tuple(t.shape)}")
+        if not float(temperature) > 0.0 or not np.isfinite(float(temperature)):
+            raise TmpnnError(f"{what}: temperature must be positive and finite, got {temperature!r}")
+        if (pssm_mix is None) != (pssm_bias is None):
+            raise TmpnnError(f"{what}: pssm_bias goes with pssm_mix (give both or neither)")
+        tabs = {}
+        for name, t, shape in (("bias", bias, (T, VOCAB)), ("allowed", allowed, (T, VOCAB)), ("pssm_mix", pssm_mix, (T,)),
+                               ("pssm_bias", pssm_bias, (T, VOCAB)), ("pssm_keep", pssm_keep, (T, VOCAB))):
+            tabs[name] = None if t is None else self._f32(t)
+            if t is not None and tuple(tabs[name].shape) != shape:
+                raise TmpnnError(f"{what}: {name} must be {list(shape)}, got {tuple(tabs[name].shape)}")
+        N, P = O.shape[0], enc.offsets.numel() - 1
+        res = {"S": torch.empty((N, T), dtype=torch.int32, device=dev), "probs": torch.empty((N, T, VOCAB), dtype=torch.float32, device=dev)}
+        if N == 0 or T == 0 or P <= 0:
+            return res
+        _need_cuda(enc.ctx)
+        # one device pass, ONE read-back: the verdicts and the offsets the chunk plan needs on the host
+        verdicts = each_verdicts(O, S0, Cl, enc.offsets)
+        back = torch.cat([verdicts.to(torch.int64), enc.offsets.to(torch.int64)]).tolist()
+        ok, offs = back[: verdicts.numel()], back[verdicts.numel():]
+        if offs[0] != 0 or offs[-1] != T or any(b < a for a, b in zip(offs, offs[1:])):
+            raise TmpnnError(f"{what}: offsets must rise from 0 to T = {T}")
+        if not ok[0]:
+            raise TmpnnError(f"{what}: every row of order must be a permutation of 0..{T - 1}")
+        if not ok[1]:
+            raise TmpnnError(f"{what}: every entry of order must stay inside the protein of its position (order[n, t0:t1] is a "
+                             f"permutation of t0..t1-1)")
+        if not ok[2]:
+            raise TmpnnError(f"{what}: residue indices must lie in [0, {VOCAB})")
+        if tied and not ok[3]:
+            raise TmpnnError(f"{what}: close must hold 0 or 1")
+        if tied and not ok[4]:
+            raise TmpnnError(f"{what}: every protein's last step must close (close[n, offsets[b + 1] - 1] == 1): a group lives inside "
+                             f"one protein")
+        chunks = plan_each_chunks(offs, N, max_rows)
+        sizer = self.lib.tmpnn_sample_tied_each_workspace_bytes if tied else self.lib.tmpnn_sample_each_workspace_bytes
+        need = 0
+        for p0, p1, n0, n1 in chunks:
+            b = sizer(offs[p1] - offs[p0], n1 - n0)
+            if b == 0:
+                raise TmpnnError(f"{what}: {n1 - n0} chain(s) of the {offs[p1] - offs[p0]} residues of proteins [{p0}, {p1}) exceed one "
+                                 f"launch's table")
+            need = max(need, b)
+        # the launch order of every chunk's proteins, longest first: one upload
+        sched = torch.as_tensor(np.concatenate([each_schedule(offs, p0, p1) for p0, p1, _, _ in chunks]), dtype=torch.int32).to(dev)
+        at, pos = {}, 0
+        for p0, p1, n0, n1 in chunks:
+            at[(p0, p1, n0, n1)] = pos
+            pos += p1 - p0
+
+        def launch(e: "EncodedBackbone", w: Weights, ws: torch.Tensor, p0: int, p1: int, n0: int, n1: int):
+            k = at[(p0, p1, n0, n1)]
+            head = (w.handle, _ptr(e.ctx), e.ctx.numel(), _ptr(e.mask), T, _ptr(e.offsets), P, p0, p1, offs[p0], offs[p1] - offs[p0],
+                    _ptr(sched[k:k + p1 - p0]), n1 - n0, _ptr(O[n0:n1]))
+            tail = (_ptr(res["S"][n0:n1]), _ptr(res["probs"][n0:n1]), _ptr(self._status), _ptr(ws), ws.numel(), _stream())
+            if tied:
+                check(self.lib.tmpnn_sample_tied_each(*head, _ptr(Cl[n0:n1]), _ptr(S0[n0:n1]), _ptr(Fr[n0:n1]), _ptr(U[n0:n1]),
+                                                      1.0 / float(temperature), _ptr(None if Wt is None else Wt[n0:n1]), _ptr(tabs["bias"]),
+                                                      _ptr(tabs["allowed"]), _ptr(tabs["pssm_mix"]), _ptr(tabs["pssm_bias"]),
+                                                      _ptr(tabs["pssm_keep"]), *tail), "tmpnn_sample_tied_each")
+            else:
+                check(self.lib.tmpnn_sample_each(*head, _ptr(S0[n0:n1]), _ptr(Fr[n0:n1]), _ptr(U[n0:n1]), 1.0 / float(temperature),
+                                                 _ptr(tabs["bias"]), _ptr(tabs["allowed"]), *tail), "tmpnn_sample_each")
+
+        self._chunks(what, enc, chunks, need, launch, check_status, stacklevel=3)
+        return res
+
     def capture_graph(self, X, S, mask, residue_idx, chain_enc, offsets, max_len: int, out: Optional[dict] = None, **want):
         """Capture ONE fused forward (its ~20 launches + the status memset) into a hipGraph: -> (graph, out). ``graph.replay()``
         reruns it on the captured tensors — refill X / S / ... in place for a new protein of the same length. The C-ABI
@@ -617,6 +722,54 @@ class Engine:
 
 
 # module-level gathers with the reference's signatures (protein_mpnn_utils.py:763-791)
+# -- host side of sample_each: the checks, the chunk plan and the launch order (plain torch / numpy: they run without a GPU) -------
+EACH_ROWS_MAX = ((1 << 24) - 1) // 3          # chains * rows of one launch (3 * N * rows < 2**24, the chain kernel's row arithmetic)
+
+
+def each_verdicts(order: torch.Tensor, S_fixed: torch.Tensor, close: Optional[torch.Tensor], offsets: torch.Tensor) -> torch.Tensor:
+    """The checks of sample_each / sample_tied_each in one pass on the arrays' device -> bool [3] (or [5] with ``close``): every row
+    of ``order`` [N,T] a permutation of 0..T-1; every entry inside the protein of its position (seg[order] == seg[position] — with
+    the first, order[n, t0:t1] is a permutation of t0..t1-1); letters in [0, 21); close 0 / 1; every non-empty protein's last step
+    closing (so no group spans two proteins)."""
+    N, T = order.shape
+    dev = order.device
+    offsets = offsets.to(device=dev, dtype=torch.int64)
+    steps = torch.arange(T, dtype=torch.int64, device=dev)
+    seg = torch.bucketize(steps, offsets[1:].contiguous(), right=True)                      # position -> protein
+    O = order.to(torch.int64)
+    perm = (torch.sort(O, dim=1).values == steps).all()
+    inside = (seg[O.clamp(0, max(T - 1, 0))] == seg).all()
+    out = [perm, inside, ((S_fixed >= 0) & (S_fixed < VOCAB)).all()]
+    if close is not None:
+        last = (offsets[1:] - 1)[offsets[1:] > offsets[:-1]].clamp(0, max(T - 1, 0))        # the last position of every non-empty protein
+        out += [((close == 0) | (close == 1)).all(), (close[:, last] == 1).all()]
+    return torch.stack(out)
+
+
+def plan_each_chunks(offsets: Sequence[int], N: int, max_rows: Optional[int] = None) -> List[tuple]:
+    """Chunks (p0, p1, n0, n1) — a protein range times a chain range — that cover every (protein, chain) pair exactly once, with
+    (n1 - n0) * rows <= min(max_rows, EACH_ROWS_MAX) for rows = offsets[p1] - offsets[p0] wherever one protein and one chain fit that;
+    a protein longer than the bound still gets chunks of one chain. Greedy: as many proteins as hold all N chains, else one protein
+    and as many chains as fit."""
+    cap = min(int(max_rows) if max_rows is not None else 1 << 18, EACH_ROWS_MAX)
+    P, chunks, p0 = len(offsets) - 1, [], 0
+    while p0 < P and N > 0:
+        p1 = p0 + 1
+        while p1 < P and (offsets[p1 + 1] - offsets[p0]) * N <= cap:
+            p1 += 1
+        rows = offsets[p1] - offsets[p0]
+        per = N if rows * N <= cap else max(1, cap // max(rows, 1))
+        chunks += [(p0, p1, n0, min(N, n0 + per)) for n0 in range(0, N, per)]
+        p0 = p1
+    return chunks
+
+
+def each_schedule(offsets: Sequence[int], p0: int, p1: int) -> np.ndarray:
+    """The launch order of proteins [p0, p1): indices by descending length (ties in index order), so the long ones start first."""
+    o = np.asarray(offsets[p0:p1 + 1], dtype=np.int64)
+    return (p0 + np.argsort(-(o[1:] - o[:-1]), kind="stable")).astype(np.int32)
+
+
 def gather_nodes(nodes: torch.Tensor, neighbor_idx: torch.Tensor) -> torch.Tensor:
     _need_cuda(nodes, neighbor_idx)
     lib = _lib.load()

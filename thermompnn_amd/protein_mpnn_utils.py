@@ -184,7 +184,8 @@ class ProteinMPNN(_EngineOwner):
         sampled autoregressively on the device — residue by residue in the reference's decoding order, each letter fed to the
         residues decoded after it — inside one launch (``Engine.sample``). When all members share ``X / mask / residue_idx /
         chain_encoding_all`` and the per-residue tables (the usual batch of copies of one structure) the structure is encoded once
-        and the B members run as B chains; otherwise each member gets its own encode.
+        and the B members run as B chains; otherwise the padded batch is encoded once and member b is sampled as one chain over
+        protein b's own steps, all members inside one launch (``Engine.sample_each``) — the bits of B calls with one member each.
 
         Random stream: one uniform per (member, residue) from ``torch.rand(..., generator=generator)`` on the device picks the
         letter by inverse CDF (the smallest a whose running sum of probs exceeds u * total). The DISTRIBUTION is the
@@ -217,13 +218,16 @@ class ProteinMPNN(_EngineOwner):
             u = torch.as_tensor(uniforms).to(device=dev, dtype=torch.float32).reshape(B, L)
             same = lambda t: t is None or bool((t[1:] == t[:1]).all())
             shared = B > 1 and all(same(t) for t in (X.to(dev), mask.to(dev), residue_idx.to(dev), chain_encoding_all.to(dev), bias, allowed))
-            groups = [slice(0, B)] if shared or B == 1 else [slice(b, b + 1) for b in range(B)]
-            S = torch.empty((B, L), dtype=torch.int64, device=dev)
-            probs = torch.empty((B, L, 21), dtype=torch.float32, device=dev)
-            for g in groups:
-                b = g.start
-                enc = self._encode_padded(eng, X[b:b + 1], mask[b:b + 1], residue_idx[b:b + 1], chain_encoding_all[b:b + 1])
-                r = eng.sample(enc, order[g], S_true[g], free[g], u[g], temperature=float(temperature), bias=bias[b],
-                               allowed=None if allowed is None else allowed[b])
-                S[g], probs[g] = r["S"].to(torch.int64), r["probs"]
+            if shared or B == 1:
+                enc = self._encode_padded(eng, X[:1], mask[:1], residue_idx[:1], chain_encoding_all[:1])
+                r = eng.sample(enc, order, S_true, free, u, temperature=float(temperature), bias=bias[0],
+                               allowed=None if allowed is None else allowed[0])
+                S, probs = r["S"].to(torch.int64), r["probs"]
+            else:       # ONE padded encode and ONE launch: member b is protein b of the packed axis, sampled as one chain over its own steps
+                enc = self._encode_padded(eng, X, mask, residue_idx, chain_encoding_all)
+                flat = lambda t: None if t is None else t.reshape(B * L, *t.shape[2:])
+                shift = (torch.arange(B, device=dev, dtype=order.dtype) * L)[:, None]
+                r = eng.sample_each(enc, flat(order + shift)[None], flat(S_true)[None], flat(free)[None], flat(u)[None],
+                                    temperature=float(temperature), bias=flat(bias), allowed=flat(allowed))
+                S, probs = r["S"].view(B, L).to(torch.int64), r["probs"].view(B, L, 21)
         return {"S": S, "probs": probs, "decoding_order": order}
