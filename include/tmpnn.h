@@ -111,6 +111,52 @@ int tmpnn_weights_create_p(tmpnn_weights_t **out, const float *const *tensors, i
 const char *tmpnn_weights_precision(const tmpnn_weights_t *w);
 void tmpnn_weights_destroy(tmpnn_weights_t *w);
 
+/* ---- the C-alpha-only flavour (ProteinMPNN(ca_only=True), ca_model_weights/v_48_*) ----------------------------------------------
+ * Replaces CA_ProteinFeatures (protein_mpnn_utils.py:911-1081) behind the constructor switch of :1195-1197. Only the featurizer
+ * differs between the flavours: the k-NN graph is the same function of the C-alpha atoms, the encoder, the decoder, W_s and W_out
+ * have the same shapes. A CA handle takes the 118 ProteinMPNN tensors in the canonical order with entry 2
+ * (features.edge_embedding.weight) of shape 128 x 167 — tmpnn_tensor_numel_ca(i), -1 outside [0, 118). The reference's CA model
+ * registers five more parameters (features.node_embedding.weight, features.norm_nodes.{weight,bias}, W_v.{weight,bias}) that its
+ * forward never reads: the host drops them. ThermoMPNN has no CA flavour: n_tensors other than 118 is TMPNN_E_INVALID, and so is a
+ * ddg output of tmpnn_ssm_forward with a CA handle. `packed` needs tmpnn_weights_ca_packed_bytes_p(precision) bytes (0 = unknown name).
+ *
+ * X stays [T,4,3] with only slot 1 (C-alpha) read, so tmpnn_knn_topk, the PDB packer and every X argument are as for the full
+ * backbone. SEGMENTS: the reference shifts and differences C-alpha along the padded length axis, with zero coordinates in front of
+ * row 0 and behind the last row and zero frames on rows 0, L-2 and L-1. Here a segment is one protein [offsets[p], offsets[p+1]) of
+ * the packed axis: a padded [B, L] batch laid out as B segments of L rows (padding rows at coordinate 0, as tied_featurize leaves
+ * them) reproduces the reference's padded result, a ragged batch reproduces each protein run alone. A segment of fewer than 3 rows
+ * (the reference fails there) has zero frames; nothing outside a row's segment is read.
+ *
+ * tmpnn_encode and tmpnn_ssm_forward read the handle's flavour. With a CA handle they launch: the k-NN kernel, ca_frames, the CA
+ * edge kernel (at every launch size: the small-launch form that computes the k-NN rows inside the featurizer is full-backbone
+ * only), then the encoder and decoder launches of a full-backbone handle. The frames live in the existing workspace; the sizers
+ * return what they return for a full-backbone handle. A protein's result does not depend on the batch it is packed into.
+ * Everything that reads an encoded ctx (tmpnn_decode_variants, tmpnn_decode_ordered, tmpnn_sample*) works on a CA ctx as it is.
+ * PARITY is judged edge by edge against the reference evaluated in float64 (tests/test_gpu_ca.py). The quaternion's sign() and
+ * sqrt(|.|) make an edge ill-conditioned in fp32 for any implementation — the self edge, pairs of parallel frames — when, in float64,
+ * one of the three radicands, the three sign differences or 1 + tr R is neither 0 nor at least 1e-3 in magnitude. Well-conditioned
+ * edges are within 1e-5; the others within 2.5 x the reference-fp32's own distance from float64. The operands of sign(), of the
+ * 3.6 / 4.0 window and of relu() are computed in the association of the torch expressions, without fma contraction, by one set of
+ * device functions shared by the pre-pass and the edge kernels of every precision.
+ * tmpnn_edge_featurize cannot serve a CA handle (it has no offsets): TMPNN_E_INVALID; use the two entries below.
+ * The training entries (tmpnn_finetune_*, tmpnn_seqloss_*, the head trainers) take no handle and are full-backbone only. */
+size_t tmpnn_weights_ca_packed_bytes_p(const char *precision);
+int tmpnn_weights_create_ca(tmpnn_weights_t **out, const float *const *tensors, int n_tensors /* 118 */, void *packed,
+                            size_t packed_bytes, const char *precision, tmpnn_stream_t stream);
+int tmpnn_weights_is_ca(const tmpnn_weights_t *w);       /* 1 for a handle of tmpnn_weights_create_ca, else 0 */
+int64_t tmpnn_tensor_numel_ca(int index);
+/* _orientations_coarse's frames (protein_mpnn_utils.py:960-989): O [T,9] = rows (o, n, o x n) with U = normalize(dX), dX[t] =
+ * Ca[t+1] - Ca[t] zeroed unless 3.6 < |dX| < 4.0, o = normalize(U[t-1] - U[t]), n = normalize(U[t-1] x U[t]) on rows 1 .. n-3 of a
+ * segment of n rows; 0 on its rows 0, n-2, n-1. */
+int tmpnn_ca_frames(const float *X, const int32_t *offsets, int n_proteins, int64_t T, float *O /* [T,9] */,
+                    tmpnn_stream_t stream);
+/* CA_ProteinFeatures.forward after top-k (protein_mpnn_utils.py:1046-1079: 9 RBF blocks, dU and Q of :998-1002, PositionalEncodings,
+ * edge_embedding, norm_edges) fused with W_e (:1229); arguments as tmpnn_edge_featurize plus the segments and O from tmpnn_ca_frames
+ * on the same X / offsets. */
+int tmpnn_edge_featurize_ca(const tmpnn_weights_t *w, const float *X, const int32_t *residue_idx, const int32_t *chain_enc,
+                            const int32_t *offsets, int n_proteins, const int32_t *E_idx, const float *D_nb, const float *O,
+                            int64_t T, float *h_E, float *E_opt, tmpnn_stream_t stream);
+
 /* ---- graph construction ------------------------------------------------------------------------
  * Replaces ProteinFeatures._dist + torch.topk (protein_mpnn_utils.py:1101-1109).
  * X [T,4,3] (N,CA,C,O; NaN already zeroed as tied_featurize does, :577), mask [T].

@@ -37,6 +37,12 @@ SIGNATURES = {
     "tmpnn_weights_create_p": (_i, [C.POINTER(_p), C.POINTER(_p), _i, _p, _sz, C.c_char_p, _p]),
     "tmpnn_weights_precision": (C.c_char_p, [_p]),
     "tmpnn_weights_destroy": (None, [_p]),
+    "tmpnn_weights_ca_packed_bytes_p": (_sz, [C.c_char_p]),
+    "tmpnn_weights_create_ca": (_i, [C.POINTER(_p), C.POINTER(_p), _i, _p, _sz, C.c_char_p, _p]),
+    "tmpnn_weights_is_ca": (_i, [_p]),
+    "tmpnn_tensor_numel_ca": (_i64, [_i]),
+    "tmpnn_ca_frames": (_i, [_p, _p, _i, _i64, _p, _p]),
+    "tmpnn_edge_featurize_ca": (_i, [_p, _p, _p, _p, _p, _i, _p, _p, _p, _i64, _p, _p, _p]),
     "tmpnn_knn_topk": (_i, [_p, _p, _p, _i, _i64, _i, _i, _p, _p, _p, _p]),
     "tmpnn_centrality": (_i, [_p, _p, _p, _i, _i64, C.c_float, _p, _p]),
     "tmpnn_edge_featurize": (_i, [_p, _p, _p, _p, _p, _p, _i64, _p, _p, _p]),

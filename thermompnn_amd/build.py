@@ -14,7 +14,7 @@ LIB = os.path.join(HERE, "libtmpnn.so")
 # the shipped library does not contain (its launchers never read the environment, allocate or synchronise). A/B tests, tools/dbg_*.py
 # and tools/phase_prof.py load it through TMPNN_LIB.
 DEBUG_LIB = os.path.join(HERE, "libtmpnn_debug.so")
-SOURCES = ["tmpnn_api.hip", "tmpnn_graph.hip", "tmpnn_layers.hip", "tmpnn_head.hip", "tmpnn_split.hip", "tmpnn_edge.hip", "tmpnn_msg.hip",
+SOURCES = ["tmpnn_api.hip", "tmpnn_graph.hip", "tmpnn_graph_ca.hip", "tmpnn_layers.hip", "tmpnn_head.hip", "tmpnn_split.hip", "tmpnn_edge.hip", "tmpnn_msg.hip",
            "tmpnn_edge_msg.hip", "tmpnn_node.hip", "tmpnn_variants.hip", "tmpnn_sample.hip", "tmpnn_train.hip", "tmpnn_finetune.hip", "tmpnn_pdb.cpp",
            "tmpnn_csv.cpp"]
 HEADERS = ["tmpnn_common.h", "tmpnn_split.h", "tmpnn_internal.h", "tmpnn_head_body.h", os.path.join("..", "..", "include", "tmpnn.h"),

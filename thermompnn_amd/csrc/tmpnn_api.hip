@@ -205,7 +205,12 @@ extern "C" int64_t tmpnn_tensor_numel(int i) {
 
 static const size_t POS_TABLE_FLOATS = 66 * TMPNN_HID, SEQ_TABLE_FLOATS = TMPNN_VOCAB * TMPNN_HID,
                     CONV_CENTER_FLOATS = 384 * 384;
-static size_t packed_bytes_for(int mode) {    // the f16 fragment images exist for f16x2 handles only (nothing else reads them)
+// A CA handle (tmpnn_weights_create_ca): no head, so no centre tap and no head images; edge_ca [128,160] behind the tables; two
+// featurizer images (the K blocks of edge_ca) instead of four.
+static const size_t EDGE_CA_FLOATS = 128 * 160;
+enum { TM_N_IMG_CA = TM_N_IMG - TM_N_HEAD_IMG - 2 };
+static size_t packed_bytes_for(int mode, bool ca = false) {    // the f16 fragment images exist for f16x2 handles only (nothing else reads them)
+    if (ca) return (POS_TABLE_FLOATS + 3 * SEQ_TABLE_FLOATS + EDGE_CA_FLOATS) * sizeof(float) + (mode == TM_MM_F16X2 ? (size_t)TM_N_IMG_CA * TM_WIMG_BYTES : 0);
     return (POS_TABLE_FLOATS + 3 * SEQ_TABLE_FLOATS + CONV_CENTER_FLOATS) * sizeof(float) +
            (mode == TM_MM_F16X2 ? (size_t)TM_N_IMG * TM_WIMG_BYTES : 0);
 }
@@ -215,25 +220,50 @@ extern "C" size_t tmpnn_weights_packed_bytes_p(const char *precision) {
     return mode < 0 ? 0 : packed_bytes_for(mode);
 }
 
+extern "C" size_t tmpnn_weights_ca_packed_bytes_p(const char *precision) {
+    const int mode = precision ? parse_mode(precision) : default_mode();
+    return mode < 0 ? 0 : packed_bytes_for(mode, true);
+}
+extern "C" int64_t tmpnn_tensor_numel_ca(int i) {     // the 118 ProteinMPNN tensors; entry 2 is edge_embedding.weight [128,167]
+    if (i < 0 || i >= TMPNN_N_MPNN_TENSORS) return -1;
+    return i == 2 ? (int64_t)TMPNN_HID * 167 : tensor_table()[i].numel;
+}
+extern "C" int tmpnn_weights_is_ca(const tmpnn_weights_t *w) { return w ? w->ca : 0; }
+
 extern "C" int tmpnn_weights_create(tmpnn_weights_t **out, const float *const *tensors, int n_tensors, void *packed,
                                     size_t packed_bytes, tmpnn_stream_t stream) {
     return tmpnn_weights_create_p(out, tensors, n_tensors, packed, packed_bytes, nullptr, stream);
 }
 
+static int weights_create(bool ca, tmpnn_weights_t **out, const float *const *tensors, int n_tensors, void *packed, size_t packed_bytes,
+                          const char *precision, tmpnn_stream_t stream);
 extern "C" int tmpnn_weights_create_p(tmpnn_weights_t **out, const float *const *tensors, int n_tensors, void *packed,
                                       size_t packed_bytes, const char *precision, tmpnn_stream_t stream) {
+    return weights_create(false, out, tensors, n_tensors, packed, packed_bytes, precision, stream);
+}
+extern "C" int tmpnn_weights_create_ca(tmpnn_weights_t **out, const float *const *tensors, int n_tensors, void *packed,
+                                       size_t packed_bytes, const char *precision, tmpnn_stream_t stream) {
+    return weights_create(true, out, tensors, n_tensors, packed, packed_bytes, precision, stream);
+}
+
+// ca: the C-alpha-only flavour — the same 118 tensors with edge_embedding.weight [128,167]; ThermoMPNN has no CA flavour, so no head
+static int weights_create(bool ca, tmpnn_weights_t **out, const float *const *tensors, int n_tensors, void *packed, size_t packed_bytes,
+                          const char *precision, tmpnn_stream_t stream) {
     const int mode = precision ? parse_mode(precision) : default_mode();
     if (mode < 0)                  // first: a caller that sized `packed` with tmpnn_weights_packed_bytes_p() got 0 for this name
         return tm_set_error(TMPNN_E_INVALID, "weights_create: unknown precision '%s' (f16x2 | bf16x3 | fp32)",
                             precision ? precision : getenv("TMPNN_PRECISION"));
     if (!out || !tensors || !packed) return tm_set_error(TMPNN_E_INVALID, "weights_create: null argument");
     if (tensor_table().size() != TMPNN_N_TENSORS) return tm_set_error(TMPNN_E_INVALID, "internal tensor table size");
+    if (ca && n_tensors != TMPNN_N_MPNN_TENSORS)
+        return tm_set_error(TMPNN_E_INVALID, "weights_create_ca: n_tensors must be %d (a CA model has no ddG head), got %d",
+                            TMPNN_N_MPNN_TENSORS, n_tensors);
     if (n_tensors != TMPNN_N_MPNN_TENSORS && n_tensors != TMPNN_N_TENSORS)
         return tm_set_error(TMPNN_E_INVALID, "weights_create: n_tensors must be %d or %d, got %d", TMPNN_N_MPNN_TENSORS,
                             TMPNN_N_TENSORS, n_tensors);
-    if (packed_bytes < packed_bytes_for(mode))
+    if (packed_bytes < packed_bytes_for(mode, ca))
         return tm_set_error(TMPNN_E_WORKSPACE, "weights_create: packed buffer %zu < %zu bytes", packed_bytes,
-                            packed_bytes_for(mode));
+                            packed_bytes_for(mode, ca));
     if (((uintptr_t)packed & 15) != 0) return tm_set_error(TMPNN_E_INVALID, "weights_create: packed buffer must be 16-byte aligned");
     for (int i = 0; i < n_tensors; ++i)
         if (!tensors[i] || ((uintptr_t)tensors[i] & 15) != 0)
@@ -244,6 +274,7 @@ extern "C" int tmpnn_weights_create_p(tmpnn_weights_t **out, const float *const 
     memset(w, 0, sizeof(*w));
     w->n_tensors = n_tensors;
     w->mode = mode;
+    w->ca = ca ? 1 : 0;
     std::map<std::string, const float *> by_name;
     for (int i = 0; i < n_tensors; ++i) { w->t[i] = tensors[i]; by_name[tensor_table()[i].name] = tensors[i]; }
     auto get = [&](const std::string &n) -> const float * {
@@ -302,10 +333,12 @@ extern "C" int tmpnn_weights_create_p(tmpnn_weights_t **out, const float *const 
     float *p = (float *)packed;
     w->pos_table = p; p += POS_TABLE_FLOATS;
     for (int l = 0; l < 3; ++l) { w->seq_table[l] = p; p += SEQ_TABLE_FLOATS; }
-    w->conv_center = p; p += CONV_CENTER_FLOATS;
+    if (ca) { w->edge_ca = p; p += EDGE_CA_FLOATS; }
+    else { w->conv_center = p; p += CONV_CENTER_FLOATS; }
     int rc = launch_prep_tables(w, (hipStream_t)stream);
+    if (rc == TMPNN_OK && ca) rc = launch_prep_ca(w, (hipStream_t)stream);
     if (mode == TM_MM_F16X2) {   // fragment images of every 128 x 128 block the f16x2 kernels multiply by (the image rule, tmpnn_internal.h)
-        char *img = (char *)p, *const img_end = img + (size_t)TM_N_IMG * TM_WIMG_BYTES;       // (inside `packed`: checked above)
+        char *img = (char *)p, *const img_end = img + (size_t)(ca ? TM_N_IMG_CA : TM_N_IMG) * TM_WIMG_BYTES;       // (inside `packed`: checked above)
         auto image = [&](const float *base, int ld, int n_rows = 128, int k_valid = 128, int k_wrap = 0, bool perm = false) -> const char * {
             if (rc != TMPNN_OK || img == img_end) return nullptr;
             const char *at = img;
@@ -320,8 +353,12 @@ extern "C" int tmpnn_weights_create_p(tmpnn_weights_t **out, const float *const 
         auto proj_images = [&](NodeProj &np) { np.img = {image(np.spec.Wa, np.spec.lda), image(np.spec.Wc, np.spec.ldc)}; };
         auto msg_images = [&](MsgW &m) { m.img.w1 = image(m.W1e, m.ld1); m.img.w2 = image(m.W2, 128); };
         auto msg_images_kperm = [&](MsgW &m) { m.img.p1 = image(m.W1e, m.ld1, 128, 128, 0, true); m.img.p2 = image(m.W2, 128, 128, 128, 0, true); };
-        // RBF columns 16..415 (K padded to 416 + 96), then — K positions 400..415 — the 16 positional columns 0..15 of the same rows
-        for (int b = 0; b < 4; ++b) w->feat_img.edge[b] = image(w->edge_w + 16 + 128 * b, 416, 128, b < 3 ? 128 : 16, b < 3 ? 0 : 16);
+        if (ca) {   // the K blocks 0..127 and 128..159 of edge_ca (derived just above, on the same stream)
+            for (int b = 0; b < 2; ++b) w->feat_img.edge[b] = image(w->edge_ca + 128 * b, 160, 128, b == 0 ? 128 : 32);
+        } else {
+            // RBF columns 16..415 (K padded to 416 + 96), then — K positions 400..415 — the 16 positional columns 0..15 of the same rows
+            for (int b = 0; b < 4; ++b) w->feat_img.edge[b] = image(w->edge_w + 16 + 128 * b, 416, 128, b < 3 ? 128 : 16, b < 3 ? 0 : 16);
+        }
         w->feat_img.we = image(w->We_w, 128);
         if (n_tensors == TMPNN_N_TENSORS) {          // ddG head: centre tap (derived just above, on the same stream) + both_out.1
             for (int u = 0; u < 9; ++u) w->head_img.unit[u] = image(w->conv_center + (size_t)128 * (u / 3) * 384 + 128 * (u % 3), 384);
@@ -336,7 +373,7 @@ extern "C" int tmpnn_weights_create_p(tmpnn_weights_t **out, const float *const 
         }
         for (int l = 0; l < 3; ++l) { msg_images_kperm(w->enc[l].msg); msg_images_kperm(w->dec[l].msg); }   // (behind the others: the order of the packed buffer is kept)
         // every image member above is filled exactly once: the count the structs declare is the count built
-        const int n_built = (int)((img - (char *)p) / TM_WIMG_BYTES), n_want = TM_N_IMG - (n_tensors == TMPNN_N_TENSORS ? 0 : TM_N_HEAD_IMG);
+        const int n_built = (int)((img - (char *)p) / TM_WIMG_BYTES), n_want = ca ? TM_N_IMG_CA : TM_N_IMG - (n_tensors == TMPNN_N_TENSORS ? 0 : TM_N_HEAD_IMG);
         if (rc == TMPNN_OK && n_built != n_want) rc = tm_set_error(TMPNN_E_INVALID, "weights_create: built %d fragment images, expected %d", n_built, n_want);
     }
     if (rc != TMPNN_OK) { delete w; return rc; }
@@ -358,7 +395,13 @@ static const int64_t T_MAX = ((int64_t)1 << 31) / (TMPNN_KS * 4) - 1;   // int32
 // was split off).
 static LayerWs layer_ws(Carver &c, int64_t T) {             // (by reference: the forward's and the encoder's layouts go on behind it)
     const size_t n = (size_t)T;
-    return LayerWs{c.take<float>(n * 256), c.take<float>(n * 256), c.take<float>(n * TMPNN_HID), c.take<float>(n), c.used};
+    LayerWs ws{c.take<float>(n * 256), c.take<float>(n * 256), c.take<float>(n * TMPNN_HID), c.take<float>(n), c.used, nullptr};
+    // The frames of a CA forward, O [T,9], share P2's bytes (9 of its 256 floats per row): the edge-update projection is first written
+    // by node update 0, which every encoder runs behind the featurizer, the frames' only reader. Carved HERE so that the overlap is
+    // part of the layout: the sizers return what they return for a full-backbone handle.
+    static_assert(9 <= 256, "the frames must fit the projection they share bytes with");
+    ws.ca_frames = ws.P2;
+    return ws;
 }
 struct FwdWs { LayerWs l; int32_t *E_idx; float *D_nb, *hE, *hV[4]; size_t bytes; };       // tmpnn_ssm_forward
 static FwdWs fwd_ws(Carver c, int64_t T) {
@@ -445,7 +488,13 @@ static int run_encoder(const tmpnn_weights *w, const float *X, const float *mask
                        hipStream_t st) {
     static const bool fuse_small = TM_DBG_FLAG("TMPNN_FUSE_SMALL", true);     // (A/B switch in the debug library only)
     const KnnInit kinit{hV, ws.P, w->enc[0].msg_proj.spec.ba, status_opt};
-    if (fuse_small && max_len <= 256 && featurize_fusable(w->mode, T)) {             // one tile per workgroup: k-NN inside the featurizer launch
+    if (w->ca) {
+        // A CA handle: k-NN (the same kernel: _dist reads the C-alpha atoms in both flavours), the frame pre-pass, the CA edge kernel —
+        // at every launch size (the k-NN-inside-the-featurizer form is full-backbone only). The frames O [T,9]: ws.ca_frames (layer_ws).
+        TRY(launch_knn(X, mask, offsets, n_proteins, T, max_len, K, E_idx, D_nb, nullptr, st, kinit));
+        TRY(launch_ca_frames(X, offsets, n_proteins, T, ws.ca_frames, st));
+        TRY(launch_featurize_ca(w, X, ws.ca_frames, offsets, n_proteins, residue_idx, chain_enc, E_idx, D_nb, T, hE, nullptr, st));
+    } else if (fuse_small && max_len <= 256 && featurize_fusable(w->mode, T)) {             // one tile per workgroup: k-NN inside the featurizer launch
         const KnnFuse kf{mask, offsets, n_proteins, max_len, K, E_idx, D_nb, kinit};
         TRY(launch_featurize(w, X, residue_idx, chain_enc, E_idx, D_nb, T, hE, nullptr, st, &kf));
     } else {
@@ -491,8 +540,26 @@ extern "C" int tmpnn_edge_featurize(const tmpnn_weights_t *w, const float *X, co
                                     float *h_E, float *E_opt, tmpnn_stream_t stream) {
     REQUIRE(w && X && residue_idx && chain_enc && E_idx && D_nb && h_E, "edge_featurize: null pointer");
     REQUIRE(T >= 0 && T <= T_MAX, "edge_featurize: bad T");
+    REQUIRE(!w->ca, "edge_featurize: a CA handle needs the proteins' offsets and the frames: tmpnn_ca_frames + tmpnn_edge_featurize_ca");
     if (T == 0) return TMPNN_OK;
     return launch_featurize(w, X, residue_idx, chain_enc, E_idx, D_nb, T, h_E, E_opt, (hipStream_t)stream);
+}
+
+extern "C" int tmpnn_ca_frames(const float *X, const int32_t *offsets, int n_proteins, int64_t T, float *O, tmpnn_stream_t stream) {
+    REQUIRE(n_proteins >= 0 && T >= 0 && T <= T_MAX, "ca_frames: bad sizes (N=%d, T=%lld)", n_proteins, (long long)T);
+    if (T == 0 || n_proteins == 0) return TMPNN_OK;
+    REQUIRE(X && offsets && O, "ca_frames: null pointer");
+    return launch_ca_frames(X, offsets, n_proteins, T, O, (hipStream_t)stream);
+}
+
+extern "C" int tmpnn_edge_featurize_ca(const tmpnn_weights_t *w, const float *X, const int32_t *residue_idx, const int32_t *chain_enc,
+                                       const int32_t *offsets, int n_proteins, const int32_t *E_idx, const float *D_nb, const float *O,
+                                       int64_t T, float *h_E, float *E_opt, tmpnn_stream_t stream) {
+    REQUIRE(w && X && residue_idx && chain_enc && offsets && E_idx && D_nb && O && h_E, "edge_featurize_ca: null pointer");
+    REQUIRE(w->ca, "edge_featurize_ca: the handle is not a CA handle (tmpnn_weights_create_ca)");
+    REQUIRE(n_proteins >= 0 && T >= 0 && T <= T_MAX, "edge_featurize_ca: bad sizes");
+    if (T == 0 || n_proteins == 0) return TMPNN_OK;
+    return launch_featurize_ca(w, X, O, offsets, n_proteins, residue_idx, chain_enc, E_idx, D_nb, T, h_E, E_opt, (hipStream_t)stream);
 }
 
 extern "C" int tmpnn_gather_nodes(const float *nodes, const int64_t *neighbor_idx, int B, int N, int K, int C, float *out,
@@ -649,6 +716,7 @@ extern "C" int tmpnn_ssm_forward(const tmpnn_weights_t *w, const float *X, const
     REQUIRE(w, "ssm_forward: null weight handle");
     REQUIRE(n_proteins >= 0 && T >= 0 && T <= T_MAX, "ssm_forward: bad sizes");
     REQUIRE(K >= 1 && K <= TMPNN_KS, "ssm_forward: K=%d outside [1, %d]", K, TMPNN_KS);
+    REQUIRE(!ddg || !w->ca, "ssm_forward: ddg requested with a CA handle (ThermoMPNN has no CA flavour)");
     REQUIRE(!ddg || w->n_tensors == TMPNN_N_TENSORS, "ssm_forward: ddg requested but the handle has no head tensors");
     if (T == 0 || n_proteins == 0) return TMPNN_OK;   // an empty batch is a no-op (pointers may be null)
     REQUIRE(X && S && mask && residue_idx && chain_enc && offsets, "ssm_forward: null input pointer");

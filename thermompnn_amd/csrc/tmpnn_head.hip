@@ -192,7 +192,7 @@ __global__ void prep_conv_center_kernel(const float *__restrict__ conv_w, float 
 }
 
 int launch_prep_tables(tmpnn_weights *w, hipStream_t st) {
-    prep_pos_table_kernel<<<66, TM_H, 0, st>>>(w->pos_w, w->pos_b, w->edge_w, w->pos_table);
+    if (!w->ca) prep_pos_table_kernel<<<66, TM_H, 0, st>>>(w->pos_w, w->pos_b, w->edge_w, w->pos_table);   // (a CA handle: launch_prep_ca)
     for (int l = 0; l < 3; ++l)
         prep_seq_table_kernel<<<TMPNN_VOCAB, TM_H, 0, st>>>(w->Ws_w, w->dec[l].msg_proj.spec.Wa, w->seq_table[l]);
     if (w->n_tensors == TMPNN_N_TENSORS)

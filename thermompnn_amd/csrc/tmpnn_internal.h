@@ -40,11 +40,13 @@ struct EdgeW {   // encoder edge update: the edge block of W11, W12, W13, LayerN
 struct EncW { NodeW node; MsgW msg; EdgeW edge; NodeProj msg_proj, edge_proj; };   // projections: W1a | W1c and W11a | W11c
 struct DecW { NodeW node; MsgW msg; NodeProj msg_proj; };                          // W1a | W1d (spec.Wa is W1 itself)
 struct FeatImg { const char *edge[4], *we; };   // edge_embedding.weight[:, 16:416] (four 128-column blocks, the last zero-padded), W_e
+                                                // (a CA handle: edge[0:2] = the K blocks 0..127 and 128..159 of edge_ca, edge[2:4] null)
 struct HeadImg { const char *unit[12]; };        // 9 blocks of the conv centre tap + 3 of both_out.1: HeadArgs::img
 
 struct tmpnn_weights {
     int n_tensors;
     int mode;              // TM_MM_*: matrix-core path of this handle's per-edge GEMMs
+    int ca;                // 1: the C-alpha-only flavour (tmpnn_weights_create_ca): edge_w is [128,167], the featurizer is tmpnn_graph_ca.hip's
     const float *t[TMPNN_N_TENSORS];
     // features
     const float *pos_w, *pos_b, *edge_w, *norm_edges_w, *norm_edges_b, *We_w, *We_b, *Ws_w;
@@ -59,6 +61,7 @@ struct tmpnn_weights {
     float *pos_table;      // [66,128]   (W_pos^T + b_pos) . W_edge[:, :16]^T
     float *seq_table[3];   // [21,128]   W_s . W1_dec[l][:, 256:384]^T
     float *conv_center;    // [384,384]  feature_convolution.weight[:, :, 4]
+    float *edge_ca;        // [128,160]  CA handles: edge_w[:, 16:167] and 9 zero columns (GEMM 1 of the CA featurizer); null otherwise
 };
 // images of a full f16x2 handle, in the packed buffer behind the tables (a handle without the head tensors builds TM_N_HEAD_IMG fewer)
 enum {
@@ -76,6 +79,7 @@ struct LayerWs {
     float *Ssum;   // [T,128] sum_k mask_k * m2_k
     float *cnt;    // [T]     sum_k mask_k
     size_t bytes;  // of the workspace, up to the end of cnt
+    float *ca_frames;   // [T,9] frames of a CA forward: shares P2's bytes, dead before the first node update writes P2 (layer_ws)
 };
 
 // Caller-owned buffers are carved into arrays that each start on a 256-byte boundary. A buffer's layout is ONE function that takes
@@ -118,6 +122,11 @@ bool featurize_fusable(int mode, int64_t T);
 int launch_featurize(const tmpnn_weights *w, const float *X, const int32_t *ridx, const int32_t *cenc,
                      const int32_t *E_idx, const float *D_nb, int64_t T, float *h_E, float *E_opt, hipStream_t st,
                      const KnnFuse *knn = nullptr);
+// tmpnn_graph_ca.hip: the C-alpha-only flavour — frames O [T,9] once per residue, then the edge kernel that gathers them
+int launch_prep_ca(tmpnn_weights *w, hipStream_t st);       // pos_table (167-column weight) + edge_ca
+int launch_ca_frames(const float *X, const int32_t *offsets, int N, int64_t T, float *O, hipStream_t st);
+int launch_featurize_ca(const tmpnn_weights *w, const float *X, const float *O, const int32_t *offsets, int N, const int32_t *ridx,
+                        const int32_t *cenc, const int32_t *E_idx, const float *D_nb, int64_t T, float *h_E, float *E_opt, hipStream_t st);
 int launch_gather_rows(const float *nodes, const void *idx, int idx64, int64_t n_rows, int64_t rows_per_batch,
                        int64_t nodes_per_batch, int C, float *out, hipStream_t st);
 int launch_gather_edges(const float *edges, const int64_t *idx, int B, int N, int K, int C, float *out, hipStream_t st);

@@ -2,7 +2,7 @@
 (Engine.sample_each, csrc/tmpnn_sample.hip), scored by one order-masked decode over the same context.
 
     python -m thermompnn_amd.design_scan a.pdb b.pdb ... --num_seq 8 --temperature 0.1 --seed 0 [--chain A] [--fixed 1,5,10-20]
-                                         --out designs.fa [--synthetic_weights 0 | --model_path CKPT] [--precision f16x2]
+                                         --out designs.fa [--synthetic_weights 0 | --model_path CKPT] [--precision f16x2] [--ca_only]
 
 The files are parsed with the native reader and packed into batches of at most ``--max_residues`` residues. Per batch: one
 ``encode``, one ``sample_each`` (``num_seq`` chains per structure, each with its own random decoding order inside its structure)
@@ -13,6 +13,8 @@ driver's default omit_AAs). FASTA: per file the native sequence, then ``num_seq`
 ``>name, sample=k, T=temperature, seed=seed, score=..., seq_recovery=...``; residues without a full backbone are written as X.
 ``--seed`` fixes the decoding orders and the uniforms through one ``torch.Generator`` consumed file by file, so a file's
 designs do not depend on how the files were batched.
+``--ca_only`` designs on the C-alpha trace alone with a ProteinMPNN(ca_only=True) weight set (``--model_path`` then names a
+ca_model_weights checkpoint): only the CA atoms are read, and a residue counts as present when its CA atom is.
 Not here: tied positions and PSSM terms (Engine.sample_tied_each), per-file fixed positions, multi-GPU sharding of the files."""
 from __future__ import annotations
 
@@ -149,15 +151,23 @@ def main(argv=None):
     ap.add_argument("--synthetic_weights", type=int, default=None)
     ap.add_argument("--precision", default=None)
     ap.add_argument("--max_residues", type=int, default=4096, help="residue budget of one batch")
+    ap.add_argument("--ca_only", action="store_true", help="C-alpha-only model (ca_model_weights/v_48_*): reads the CA atoms alone")
     a = ap.parse_args(argv)
     if a.num_seq < 1 or not a.temperature > 0:
         ap.error("--num_seq must be >= 1 and --temperature positive")
     if a.synthetic_weights is None and not a.model_path:
         ap.error("give --model_path or --synthetic_weights")
-    sd = weights.synthetic_state_dict(a.synthetic_weights) if a.synthetic_weights is not None else weights.load_thermompnn_checkpoint(a.model_path)
-    eng = Engine(sd, "cuda", 48, precision=a.precision)
+    if a.ca_only:
+        sd = weights.synthetic_state_dict(a.synthetic_weights, "mpnn_ca") if a.synthetic_weights is not None else \
+            weights.load_vanilla_checkpoint(a.model_path)[1]
+    else:
+        sd = weights.synthetic_state_dict(a.synthetic_weights) if a.synthetic_weights is not None else weights.load_thermompnn_checkpoint(a.model_path)
+    eng = Engine(sd, "cuda", 48, precision=a.precision, ca_only=a.ca_only)
     fixed = parse_positions(a.fixed)
     entries = parse_pdbs(a.pdb, [a.chain] * len(a.pdb) if a.chain else None)
+    if a.ca_only:
+        for e in entries:
+            e["mask"] = e["ca_mask"]          # (tied_featurize(ca_only=True): present = the CA atom is)
     gen = torch.Generator().manual_seed(a.seed)
     chains = [draw_chains(e, a.num_seq, fixed, gen) for e in entries]
     names = [os.path.splitext(os.path.basename(p))[0] for p in a.pdb]

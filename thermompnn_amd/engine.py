@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import weights as _weights
 from ._lib import HID, KS, VOCAB, TmpnnError, TmpnnRangeError, check
 
 
@@ -62,8 +63,10 @@ class Weights:
     """Device-resident weight set + the native handle (tmpnn_weights_create)."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], device, with_head: Optional[bool] = None,
-                 precision: Optional[str] = None, tensors: Optional[List[torch.Tensor]] = None):
-        """``precision``: "f16x2" | "bf16x3" | "fp32" (matrix-core path of every call through this handle) or None for
+                 precision: Optional[str] = None, tensors: Optional[List[torch.Tensor]] = None, ca_only: Optional[bool] = None):
+        """``ca_only``: the C-alpha-only flavour (a ProteinMPNN(ca_only=True) state dict: tmpnn_weights_create_ca); None detects it by
+        the edge embedding's 167 inputs. The five parameters of such a state dict that its forward never reads are dropped.
+        ``precision``: "f16x2" | "bf16x3" | "fp32" (matrix-core path of every call through this handle) or None for
         the library default. ``tensors``: device tensors of another Weights of the same model to share (a second handle
         costs only its derived data: 0.8 MB of tables, plus 7.2 MB of f16 fragment images for an "f16x2" handle)."""
         lib = _lib.load()
@@ -74,30 +77,38 @@ class Weights:
             raise TmpnnError("weights must live on a CUDA (ROCm) device")
         names = _lib.tensor_names()
         sd = dict(state_dict)
+        if ca_only is None:
+            ca_only = _weights.is_ca_state_dict(sd)
+        if ca_only and with_head:
+            raise ValueError("a ca_only model has no ddG head (ThermoMPNN has no CA flavour)")
         if with_head is None:
-            with_head = all(n in sd for n in names[_lib.N_MPNN_TENSORS:])
+            with_head = not ca_only and all(n in sd for n in names[_lib.N_MPNN_TENSORS:])
         n = _lib.N_TENSORS if with_head else _lib.N_MPNN_TENSORS
+        numel = lib.tmpnn_tensor_numel_ca if ca_only else lib.tmpnn_tensor_numel
         self.tensors: List[torch.Tensor] = list(tensors) if tensors is not None else []
         for i, name in enumerate(names[:n] if tensors is None else []):
             key = name if i >= _lib.N_MPNN_TENSORS else ("prot_mpnn." + name if ("prot_mpnn." + name) in sd else name)
             if key not in sd:
                 raise KeyError(f"state dict lacks {key!r}")
             t = sd[key].detach().to(device=device, dtype=torch.float32).contiguous()
-            if t.numel() != lib.tmpnn_tensor_numel(i):
-                raise TmpnnError(f"{key}: {t.numel()} elements, engine expects {lib.tmpnn_tensor_numel(i)}")
+            if t.numel() != numel(i):
+                raise TmpnnError(f"{key}: {t.numel()} elements, engine expects {numel(i)}")
             if t.data_ptr() % 16:
                 t = t.clone()
             self.tensors.append(t)
         self.device = device
         self.with_head = with_head
+        self.ca_only = bool(ca_only)
         _selftest(lib, device)
-        nbytes = lib.tmpnn_weights_packed_bytes_p(precision.encode() if precision else None) or lib.tmpnn_weights_packed_bytes()
+        sizer, create = (lib.tmpnn_weights_ca_packed_bytes_p, lib.tmpnn_weights_create_ca) if ca_only else \
+            (lib.tmpnn_weights_packed_bytes_p, lib.tmpnn_weights_create_p)
+        nbytes = sizer(precision.encode() if precision else None) or lib.tmpnn_weights_packed_bytes()
         self.packed = torch.empty(nbytes, dtype=torch.uint8, device=device)      # (0 = unknown name: create_p reports it)
         arr = (C.c_void_p * n)(*[t.data_ptr() for t in self.tensors])
         self.handle = C.c_void_p()
         with torch.cuda.device(device):
-            check(lib.tmpnn_weights_create_p(C.byref(self.handle), arr, n, _ptr(self.packed), self.packed.numel(),
-                                             precision.encode() if precision else None, _stream()), "tmpnn_weights_create_p")
+            check(create(C.byref(self.handle), arr, n, _ptr(self.packed), self.packed.numel(),
+                         precision.encode() if precision else None, _stream()), "tmpnn_weights_create_ca" if ca_only else "tmpnn_weights_create_p")
         self.precision = lib.tmpnn_weights_precision(self.handle).decode()
 
     def __del__(self):
@@ -129,12 +140,15 @@ class Engine:
     """One weight set on one GPU. All tensors are packed along the residue axis (T = sum of lengths)."""
 
     def __init__(self, state_dict, device="cuda", k_neighbors: int = 48, precision: Optional[str] = None,
-                 retry_precision: Optional[str] = "bf16x3", with_head: Optional[bool] = None):
-        """``precision``: matrix-core path of the per-edge GEMMs ("f16x2" default | "bf16x3" | "fp32").
+                 retry_precision: Optional[str] = "bf16x3", with_head: Optional[bool] = None, ca_only: Optional[bool] = None):
+        """``ca_only``: a ProteinMPNN(ca_only=True) weight set (None: detected by the edge embedding's shape); ``X`` stays [T,4,3] in
+        every call, with only slot 1 (C-alpha) read, and ``want_ddg`` is refused.
+        ``precision``: matrix-core path of the per-edge GEMMs ("f16x2" default | "bf16x3" | "fp32").
         ``retry_precision``: when a forward in f16x2 leaves the finite range (an operand >= 65504 overflowed fp16), it is
         rerun once at this precision with a warning (None: raise TmpnnRangeError instead)."""
         self.lib = _lib.load()
-        self.w = Weights(state_dict, device, with_head=with_head, precision=precision)
+        self.w = Weights(state_dict, device, with_head=with_head, precision=precision, ca_only=ca_only)
+        self.ca_only = self.w.ca_only
         self.device = self.w.device
         self.precision = self.w.precision
         self.retry_precision = retry_precision
@@ -149,7 +163,7 @@ class Engine:
         """The handle for ``precision`` (created on first use; shares the raw tensors)."""
         if precision not in self._alt:
             self._alt[precision] = Weights({}, self.device, with_head=self.w.with_head, precision=precision,
-                                           tensors=self.w.tensors)
+                                           tensors=self.w.tensors, ca_only=self.ca_only)
         return self._alt[precision]
 
     def _raise_status(self, what: str, status: Optional[torch.Tensor] = None) -> int:
@@ -209,11 +223,27 @@ class Engine:
                                         _ptr(out), _stream()), "tmpnn_centrality")
         return out
 
-    def edge_featurize(self, X, residue_idx, chain_enc, E_idx, D_nb, want_E: bool = False):
+    def ca_frames(self, X, offsets):
+        """_orientations_coarse's frames O [T,9] of the packed batch (tmpnn_ca_frames): X [T,4,3] (slot 1 read), a segment per protein."""
+        X, offsets = self._f32(X), self._i32(offsets)
+        _need_cuda(X)
+        O = torch.empty((X.shape[0], 9), dtype=torch.float32, device=self.device)
+        check(self.lib.tmpnn_ca_frames(_ptr(X), _ptr(offsets), offsets.numel() - 1, X.shape[0], _ptr(O), _stream()), "tmpnn_ca_frames")
+        return O
+
+    def edge_featurize(self, X, residue_idx, chain_enc, E_idx, D_nb, want_E: bool = False, offsets=None):
+        """``offsets`` (a CA engine only): the proteins of the packed axis, default one protein [0, T)."""
         X, ridx, cenc = self._f32(X), self._i32(residue_idx), self._i32(chain_enc)
         T = X.shape[0]
         h_E = torch.empty((T, KS, HID), dtype=torch.float32, device=self.device)
         E = torch.empty_like(h_E) if want_E else None
+        if self.ca_only:
+            offsets = self._i32([0, T] if offsets is None else offsets)
+            O = self.ca_frames(X, offsets)
+            check(self.lib.tmpnn_edge_featurize_ca(self.w.handle, _ptr(X), _ptr(ridx), _ptr(cenc), _ptr(offsets), offsets.numel() - 1,
+                                                   _ptr(E_idx), _ptr(D_nb), _ptr(O), T, _ptr(h_E), _ptr(E), _stream()),
+                  "tmpnn_edge_featurize_ca")
+            return (h_E, E) if want_E else h_E
         check(self.lib.tmpnn_edge_featurize(self.w.handle, _ptr(X), _ptr(ridx), _ptr(cenc), _ptr(E_idx), _ptr(D_nb), T,
                                             _ptr(h_E), _ptr(E), _stream()), "tmpnn_edge_featurize")
         return (h_E, E) if want_E else h_E
@@ -312,6 +342,8 @@ class Engine:
         Throughput loops pass ``check_status=False`` (nothing syncs; call ``check_last_status()`` when convenient).
         ``precision`` overrides the engine's precision for this call. (``_private``: workspace / status word owned by a
         captured graph instead of the engine's shared ones, see ``capture_graph``.)"""
+        if want_ddg and self.ca_only:
+            raise ValueError("ssm_forward: want_ddg with a ca_only engine (ThermoMPNN has no CA flavour); pass want_ddg=False")
         max_len = self._max_len(offsets, max_len)
         X, mask = self._f32(X), self._f32(mask)
         S, ridx, cenc, offsets = self._i32(S), self._i32(residue_idx), self._i32(chain_enc), self._i32(offsets)

@@ -129,20 +129,20 @@ def tied_featurize(batch, device, chain_dict, fixed_position_dict=None, omit_AA_
     """Pack parsed proteins into padded tensors; returns the reference's 20-tuple
     (protein_mpnn_utils.py:353-605; tuple order at :605).
 
-    Only the arguments the inference path uses are implemented (``chain_dict`` and
-    ``fixed_position_dict``); the sequence-design extras raise ``NotImplementedError``."""
+    Only the arguments the inference path uses are implemented (``chain_dict``,
+    ``fixed_position_dict`` and ``ca_only``: ``X`` [B,L,3] from the ``CA_chain_*`` coordinates of ``alt_parse_PDB(ca_only=True)``);
+    the sequence-design extras raise ``NotImplementedError``."""
     for name, val in (("omit_AA_dict", omit_AA_dict), ("tied_positions_dict", tied_positions_dict),
                       ("pssm_dict", pssm_dict), ("bias_by_res_dict", bias_by_res_dict)):
         if val is not None:
             raise NotImplementedError(f"{name} is a sequence-design option outside the ThermoMPNN hot path")
-    if ca_only:
-        raise NotImplementedError("ca_only=True is never used by ThermoMPNN (transfer_model.py:26)")
+    atoms = ("CA",) if ca_only else BACKBONE      # ca_only (:360, :423-426, :601-602): X [B,L,3], mask = the C-alpha atom is finite
 
     B = len(batch)
     lengths = np.array([len(b["seq"]) for b in batch], dtype=np.int32)
     L = int(lengths.max())
     n_alpha = len(MPNN_ALPHABET)
-    X = np.full((B, L, 4, 3), np.nan, dtype=np.float64)
+    X = np.full((B, L, len(atoms), 3), np.nan, dtype=np.float64)
     residue_idx = np.full((B, L), -100, dtype=np.int32)
     chain_M = np.zeros((B, L), dtype=np.int32)
     chain_M_pos = np.zeros((B, L), dtype=np.int32)
@@ -170,7 +170,10 @@ def tied_featurize(batch, device, chain_dict, fixed_position_dict=None, omit_AA_
                 seq = "".join("X" if a == "-" else a for a in b[f"seq_chain_{letter}"])
                 n = len(seq)
                 coords = b[f"coords_chain_{letter}"]
-                xyz = np.stack([np.asarray(coords[f"{a}_chain_{letter}"], dtype=np.float64) for a in BACKBONE], 1)
+                if ca_only:
+                    xyz = np.asarray(coords[f"CA_chain_{letter}"], dtype=np.float64).reshape(n, 1, 3)    # [n,1,3] or [n,3]
+                else:
+                    xyz = np.stack([np.asarray(coords[f"{a}_chain_{letter}"], dtype=np.float64) for a in BACKBONE], 1)
                 sl = slice(pos, pos + n)
                 X[i, sl] = xyz
                 S[i, sl] = [_AA_TO_IDX[a] for a in seq]        # ValueError-equivalent: KeyError on unknown letter
@@ -200,6 +203,8 @@ def tied_featurize(batch, device, chain_dict, fixed_position_dict=None, omit_AA_
 
     mask = np.isfinite(X.sum(axis=(2, 3))).astype(np.float32)      # :576
     X = np.nan_to_num(X, nan=0.0)                                   # :577 (coords are finite or NaN)
+    if ca_only:
+        X = X[:, :, 0]                                              # :601-602
 
     jumps = ((residue_idx[:, 1:] - residue_idx[:, :-1]) == 1).astype(np.float32)
     phi = np.pad(jumps, [[0, 0], [1, 0]])

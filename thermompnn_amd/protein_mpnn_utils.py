@@ -2,7 +2,9 @@
 
 Same names, signatures and return conventions; the arithmetic runs in libtmpnn.so
 (hand-written HIP for gfx950) — this module only packs arguments. Out-of-scope symbols of the
-reference file (CA_ProteinFeatures, StructureDataset*, loss_*) are not provided.
+reference file (StructureDataset*, loss_*) are not provided.
+``ProteinMPNN(ca_only=True)`` is: CA_ProteinFeatures (:911-1081) runs in the engine's C-alpha featurizer (tmpnn_graph_ca.hip); every
+method then takes ``X`` [B,L,3] as the reference does.
 ``ProteinMPNN.conditional_probs`` / ``unconditional_probs`` (:1496-1587) are: the masked decoder runs in tmpnn_decode_ordered.
 ``ProteinMPNN.sample`` (:1279-1383) is: whole chains are sampled autoregressively inside one launch (tmpnn_sample).
 ``tied_sample`` (:1385-1494), the PSSM flags of ``sample`` and the design dictionaries of ``tied_featurize`` live in
@@ -102,8 +104,6 @@ class ProteinMPNN(_EngineOwner):
     def __init__(self, num_letters, node_features, edge_features, hidden_dim, num_encoder_layers=3,
                  num_decoder_layers=3, vocab=21, k_neighbors=64, augment_eps=0.05, dropout=0.1, ca_only=False):
         super().__init__()
-        if ca_only:
-            raise NotImplementedError("ca_only=True (CA_ProteinFeatures) is outside the ThermoMPNN hot path")
         if (num_letters, node_features, edge_features, hidden_dim, vocab) != (21, 128, 128, 128, 21) or \
                 (num_encoder_layers, num_decoder_layers) != (3, 3):
             raise NotImplementedError("the HIP engine is specialised for the ThermoMPNN configuration: "
@@ -114,7 +114,20 @@ class ProteinMPNN(_EngineOwner):
             raise NotImplementedError("augment_eps > 0 adds training noise; ThermoMPNN uses 0.0 (transfer_model.py:27)")
         self.node_features, self.edge_features, self.hidden_dim = node_features, edge_features, hidden_dim
         self.k_neighbors = int(k_neighbors)
-        _register_tree(self, _weights.mpnn_param_shapes())
+        self.ca_only = bool(ca_only)
+        # ca_only: the reference's parameter tree (CA_ProteinFeatures' own and W_v, :927-930, :1197), so that load_state_dict of a
+        # ca_model_weights checkpoint is strict-clean; the engine drops the five its forward never reads
+        _register_tree(self, _weights.mpnn_param_shapes(ca_only=self.ca_only))
+
+    def _backbone(self, X):
+        """X as the engine takes it, [B,L,4,3]: a ca_only model's [B,L,3] goes into slot 1 (C-alpha) of a zero tensor on the device."""
+        if not self.ca_only:
+            return X
+        if X.dim() != 3 or X.shape[-1] != 3:
+            raise ValueError(f"ca_only: X must be [B, L, 3] (C-alpha coordinates), got {tuple(X.shape)}")
+        X4 = torch.zeros((X.shape[0], X.shape[1], 4, 3), dtype=torch.float32, device=self.engine().device)
+        X4[:, :, 1] = X.to(X4.device, torch.float32)
+        return X4
 
     def forward(self, X, S, mask, chain_M, residue_idx, chain_encoding_all, randn, use_input_decoding_order=False,
                 decoding_order=None):
@@ -125,7 +138,7 @@ class ProteinMPNN(_EngineOwner):
         B, L = X.shape[0], X.shape[1]
         offsets = torch.arange(B + 1, dtype=torch.int32) * L
         with torch.cuda.device(eng.device):
-            res = eng.ssm_forward(X.reshape(B * L, 4, 3), S.reshape(-1), mask.reshape(-1), residue_idx.reshape(-1),
+            res = eng.ssm_forward(self._backbone(X).reshape(B * L, 4, 3), S.reshape(-1), mask.reshape(-1), residue_idx.reshape(-1),
                                   chain_encoding_all.reshape(-1), offsets, max_len=L, want_ddg=False,
                                   want_hidden=True, want_log_probs=True)
             h_S = eng.seq_embed(S.reshape(-1)).view(B, L, -1)
@@ -136,7 +149,7 @@ class ProteinMPNN(_EngineOwner):
         """The padded batch [B,L,...] as ``forward`` lays it out: B proteins of L rows each on the packed residue axis."""
         B, L = X.shape[0], X.shape[1]
         offsets = torch.arange(B + 1, dtype=torch.int32) * L
-        return eng.encode(X.reshape(B * L, 4, 3), mask.reshape(-1), residue_idx.reshape(-1), chain_encoding_all.reshape(-1),
+        return eng.encode(self._backbone(X).reshape(B * L, 4, 3), mask.reshape(-1), residue_idx.reshape(-1), chain_encoding_all.reshape(-1),
                           offsets, max_len=L)
 
     def conditional_probs(self, X, S, mask, chain_M, residue_idx, chain_encoding_all, randn, backbone_only=False):

@@ -24,18 +24,30 @@ VOCAB = 21       # protein_mpnn_utils.py:1186
 N_POS = 16       # num_positional_embeddings (protein_mpnn_utils.py:1085)
 N_RBF = 16
 EDGE_IN = N_POS + 25 * N_RBF   # 416 (protein_mpnn_utils.py:1097)
+EDGE_IN_CA = N_POS + 9 * N_RBF + 7   # 167: the C-alpha-only flavour (CA_ProteinFeatures, protein_mpnn_utils.py:926)
 HEAD_IN = 3 * H  # num_final_layers(2)*128 + 128 (transfer_model.py:57)
+# parameters the reference's ca_only model registers and its forward never reads (:927, :929, :1197): the engine's handle drops them
+CA_UNUSED = ("features.node_embedding.weight", "features.norm_nodes.weight", "features.norm_nodes.bias", "W_v.weight", "W_v.bias")
 
 
-def mpnn_param_shapes(num_enc: int = 3, num_dec: int = 3) -> "OrderedDict[str, tuple]":
+def mpnn_param_shapes(num_enc: int = 3, num_dec: int = 3, ca_only: bool = False) -> "OrderedDict[str, tuple]":
     """Names and shapes of ProteinMPNN's state dict, in module-registration order
-    (protein_mpnn_utils.py:1184-1215)."""
+    (protein_mpnn_utils.py:1184-1215). ``ca_only``: the tree of ProteinMPNN(ca_only=True) — CA_ProteinFeatures' parameters
+    (:923-930) and W_v (:1197), 123 entries."""
     s: "OrderedDict[str, tuple]" = OrderedDict()
     s["features.embeddings.linear.weight"] = (N_POS, 66)
     s["features.embeddings.linear.bias"] = (N_POS,)
-    s["features.edge_embedding.weight"] = (H, EDGE_IN)
+    if ca_only:
+        s["features.node_embedding.weight"] = (H, 3)
+    s["features.edge_embedding.weight"] = (H, EDGE_IN_CA if ca_only else EDGE_IN)
+    if ca_only:
+        s["features.norm_nodes.weight"] = (H,)
+        s["features.norm_nodes.bias"] = (H,)
     s["features.norm_edges.weight"] = (H,)
     s["features.norm_edges.bias"] = (H,)
+    if ca_only:
+        s["W_v.weight"] = (H, H)
+        s["W_v.bias"] = (H,)
     s["W_e.weight"] = (H, H)
     s["W_e.bias"] = (H,)
     s["W_s.weight"] = (VOCAB, H)
@@ -119,16 +131,33 @@ def _draw(rng: np.random.Generator, name: str, shape: tuple, style: str = "xavie
 
 
 def synthetic_state_dict(seed: int = 0, which: str = "transfer", style: str = "xavier", head=None) -> "OrderedDict[str, torch.Tensor]":
-    """Deterministic synthetic weights. ``which`` = 'transfer' (full TransferModel tree) or 'mpnn'; ``style`` see _draw;
+    """Deterministic synthetic weights. ``which`` = 'transfer' (full TransferModel tree), 'mpnn' or 'mpnn_ca' (the ca_only tree);
+    ``style`` see _draw;
     ``head`` = dict(hidden_dims=..., num_final_layers=..., lightattn=...) for a non-default TransferModel head (the ProteinMPNN
     tensors come first, so they are the same draws whatever the head)."""
     if style not in STYLES:
         raise ValueError(f"style={style!r}: expected one of {STYLES}")
     rng = np.random.default_rng(seed)
-    shapes = transfer_param_shapes(**(head or {})) if which == "transfer" else mpnn_param_shapes()
+    shapes = transfer_param_shapes(**(head or {})) if which == "transfer" else mpnn_param_shapes(ca_only=which == "mpnn_ca")
     out: "OrderedDict[str, torch.Tensor]" = OrderedDict()
     for name, shape in shapes.items():
         out[name] = torch.from_numpy(_draw(rng, name, shape, style))
+    return out
+
+
+def is_ca_state_dict(sd) -> bool:
+    """A ProteinMPNN(ca_only=True) state dict: its edge embedding takes 167 inputs."""
+    for k in ("features.edge_embedding.weight", "prot_mpnn.features.edge_embedding.weight"):
+        if k in sd:
+            return tuple(sd[k].shape) == (H, EDGE_IN_CA)
+    return False
+
+
+def ca_engine_tensors(sd) -> "OrderedDict[str, torch.Tensor]":
+    """The 118 tensors a CA weight handle takes (tmpnn_weights_create_ca), in the canonical order: the ca_only state dict without
+    the five parameters its forward never reads (CA_UNUSED)."""
+    out = OrderedDict((k, sd[k]) for k in mpnn_param_shapes(ca_only=True) if k not in CA_UNUSED)
+    assert list(out) == list(mpnn_param_shapes())
     return out
 
 
