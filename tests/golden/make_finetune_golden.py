@@ -1,6 +1,6 @@
 """Golden gradients of one fine-tuning step (ProteinMPNN unfrozen), by IMPORTING THE REFERENCE (runs only in the build container).
 
-    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_finetune_golden.py [2OCJ_A | 2OCJ_A_gap]
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_finetune_golden.py [2OCJ_A | 2OCJ_A_gap | 2OCJ_A_hot]
 
 The reference TransferModel (make_golden.build_reference_model: synthetic weights, seed 0, released head) runs in float64 and in
 train mode with every parameter trainable, over ~96 mutants of 2OCJ chain A (several sharing a position, a few with ddG None). Each
@@ -17,6 +17,9 @@ limits keep it under 1 MB. W_out has no gradient and is not stored. Only tensors
 its letter; residues 150-152 removed: positions 54-56 are '-', token 20, mask 0). Its mutant positions are drawn from the residues
 that have a letter, position 24 always among them. The E_idx of a masked row is arbitrary (every candidate sits at the same adjusted
 distance) and does not reach the loss.
+
+2OCJ_A_hot runs 2OCJ_A's mutants from the heavy weight draw "hot", seed 2 (matrices x 3, biases x 5, LayerNorm gamma in [-2, 2]), the
+drawn-mask run only, and stores beside every float64 result its distance "d32" from the same reference run in float32.
 """
 import os
 import sys
@@ -74,17 +77,21 @@ def sample_index(name, n):
 
 CASES = {"2OCJ_A": os.path.join(mg.REF, "examples", "2OCJ.pdb"), "2OCJ_A_gap": os.path.join(HERE, "2OCJ_gap_chainA.pdb")}
 GAP_MASKED = 24                                   # residue 120 without its N line
+# a case on another weight draw than make_golden's seed 0: (seed, style), and the tags it stores. 2OCJ_A_hot is 2OCJ_A (same mutants
+# and targets) from the heavy draw of the 2OCJ_A_hot inference fixture; it stores the drawn-mask run only (half the size of the
+# others) and, beside each float64 result, the distance "d32" of the SAME reference evaluated in float32 from it.
+WEIGHTS = {"2OCJ_A_hot": (2, "hot")}
+TAGS = {"2OCJ_A_hot": ("drawn",)}
+CASES["2OCJ_A_hot"] = CASES["2OCJ_A"]
 
 
 def main(case="2OCJ_A"):
     rng = np.random.default_rng(7)
-    with tempfile.TemporaryDirectory() as tmp:
-        model = mg.build_reference_model(tmp)
     pdb = mg.ref_utils.alt_parse_PDB(CASES[case], "A")
     seq = pdb[0]["seq"]
     L = len(seq)
     K = min(48, L)
-    if case == "2OCJ_A":
+    if case in ("2OCJ_A", "2OCJ_A_hot"):
         positions = np.sort(rng.choice([i for i in range(L) if seq[i] in AA20], 32, replace=False))
     else:
         assert seq[GAP_MASKED] in AA20 and seq[54:57] == "---"
@@ -96,23 +103,28 @@ def main(case="2OCJ_A"):
             muts.append(Mutation(int(p), seq[p], str(a), None, "2OCJ"))
     targets = rng.normal(0.0, 1.5, len(muts)).astype(np.float32)
     targets[rng.choice(len(muts), 6, replace=False)] = np.nan
-    for m, t in zip(muts, targets):
-        m.ddG = None if np.isnan(t) else torch.tensor([float(t)], dtype=torch.float64)
-    model = model.double()
-    # float64 end to end: the featurized inputs are cast, and the one-hot the reference builds with .float() is cast back
-    tf = mg.ref_tm.tied_featurize
-    mg.ref_tm.tied_featurize = lambda *a, **k: tuple(t.double() if torch.is_tensor(t) and t.is_floating_point() else t for t in tf(*a, **k))
-    model.prot_mpnn.features.embeddings.linear.register_forward_pre_hook(lambda mod, args: tuple(x.double() for x in args))
-    for prm in model.parameters():
-        prm.requires_grad_(True)
-    model.light_attention.dropout = nn.Identity()
+    weight_seed, style = WEIGHTS.get(case, (mg.WEIGHT_SEED, "xavier"))
     out = dict(positions=np.array([m.position for m in muts], np.int32), wildtype=np.array([AA20.index(m.wildtype) for m in muts], np.int32),
                mutation=np.array([AA20.index(m.mutation) for m in muts], np.int32), targets=targets, seed=np.int64(SEED),
-               step=np.int64(STEP), weight_seed=np.int64(mg.WEIGHT_SEED))
+               step=np.int64(STEP), weight_seed=np.int64(weight_seed))
+    if case in WEIGHTS:
+        out["weight_style"] = np.array(style)
     scale = 1.0 / (1.0 - round(0.1 * 2 ** 24) / 2 ** 24)
-    captured = {}
+    tf = mg.ref_tm.tied_featurize
 
-    for tag in ("ones", "drawn"):
+    def run(tag, dtype):
+        """The reference in ``dtype`` under the masks of ``tag`` -> (loss, {name: flat gradient or None}, E_idx)."""
+        with tempfile.TemporaryDirectory() as tmp:
+            model = mg.build_reference_model(tmp, weight_seed, style).to(dtype)
+        for m, t in zip(muts, targets):
+            m.ddG = None if np.isnan(t) else torch.tensor([float(t)], dtype=dtype)
+        # ``dtype`` end to end: the featurized inputs are cast, and the one-hot the reference builds with .float() is cast back
+        mg.ref_tm.tied_featurize = lambda *a, **k: tuple(t.to(dtype) if torch.is_tensor(t) and t.is_floating_point() else t for t in tf(*a, **k))
+        model.prot_mpnn.features.embeddings.linear.register_forward_pre_hook(lambda mod, args: tuple(x.to(dtype) for x in args))
+        for prm in model.parameters():
+            prm.requires_grad_(True)
+        model.light_attention.dropout = nn.Identity()
+        captured = {}
         mpnn = model.prot_mpnn
         for l, layer in enumerate(mpnn.encoder_layers):
             for j, name in enumerate(("dropout1", "dropout2", "dropout3")):
@@ -132,17 +144,27 @@ def main(case="2OCJ_A"):
         mpnn.features.forward = spy
         model.zero_grad()
         model.train()
-        pred, _ = model([pdb[0]], muts)
-        mpnn.features.forward = feat_fwd
+        try:
+            pred, _ = model([pdb[0]], muts)
+        finally:
+            mpnn.features.forward = feat_fwd
+            mg.ref_tm.tied_featurize = tf
         loss = torch.stack([F.mse_loss(o["ddG"], m.ddG) for m, o in zip(muts, pred) if m.ddG is not None]).mean()
         loss.backward()
-        out[f"{tag}_loss"] = np.float64(loss.item())
-        out["E_idx"] = captured["E_idx"][0].numpy().astype(np.int32)
+        assert loss.dtype == dtype
+        grads = {}
         for name, prm in model.named_parameters():
             if name.startswith("prot_mpnn.W_out"):
                 assert prm.grad is None
                 continue
-            g = (prm.grad if prm.grad is not None else torch.zeros_like(prm)).reshape(-1).numpy()
+            grads[name] = (prm.grad if prm.grad is not None else torch.zeros_like(prm)).reshape(-1).double().numpy()
+        return loss.item(), grads, captured["E_idx"][0].numpy().astype(np.int32)
+
+    for tag in TAGS.get(case, ("ones", "drawn")):
+        loss, grads, E_idx = run(tag, torch.float64)
+        out[f"{tag}_loss"] = np.float64(loss)
+        out["E_idx"] = E_idx
+        for name, g in grads.items():
             if g.size <= FULL_MAX:
                 out[f"{tag}|{name}|full"] = g.astype(np.float32)
             else:
@@ -151,7 +173,17 @@ def main(case="2OCJ_A"):
                 out[f"{tag}|{name}|sumsq"] = np.float64((g * g).sum())
                 out[f"{tag}|{name}|dot"] = np.float64((g * sign).sum())
                 out[f"{tag}|{name}|absmax"] = np.float64(np.abs(g).max())
-        print(f"{tag}: loss {loss.item():.8f}")
+        print(f"{tag}: loss {loss:.8f}")
+        if case in WEIGHTS:
+            loss32, g32, E32 = run(tag, torch.float32)
+            assert np.array_equal(E32, E_idx)
+            out[f"{tag}_loss_d32"] = np.float64(abs(loss32 - loss) / abs(loss))
+            worst = 0.0
+            for name, g in grads.items():
+                out[f"{tag}|{name}|d32"] = np.float64(np.abs(g32[name] - g).max())
+                if np.abs(g).max() > 1e-12:
+                    worst = max(worst, float(out[f"{tag}|{name}|d32"]) / float(np.abs(g).max()))
+            print(f"{case} {tag}: float32 reference: loss rel. d32 {out[f'{tag}_loss_d32']:.3g}, worst gradient d32 / max|g| {worst:.3g}")
     path = os.path.join(HERE, f"finetune_{case}.npz")
     np.savez_compressed(path, **out)
     print(f"finetune_{case}: {len(muts)} mutants -> {os.path.getsize(path) / 1024:.0f} KiB")

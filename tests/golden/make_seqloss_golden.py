@@ -1,7 +1,7 @@
 """Golden log-probabilities, loss and gradients of ProteinMPNN's own training objective, by IMPORTING THE REFERENCE's training
 flavour (model_utils.ProteinMPNN; runs only in the build container).
 
-    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_seqloss_golden.py [2OCJ_A | 2OCJ_A_gap | 2OCJ_A_fixed | losses]
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_seqloss_golden.py [2OCJ_A | 2OCJ_A_gap | 2OCJ_A_fixed | 2OCJ_A_hot | losses]
 
 The recipe of make_finetune_golden.py: float64, the synthetic ProteinMPNN weights of make_golden (seed 0), K = 48, augment_eps = 0,
 train mode, each of the 15 nn.Dropout modules replaced by a module that multiplies by an injected mask: all ones ("ones"), or the
@@ -11,7 +11,8 @@ the draw and the order are recorded. Loss = loss_smoothed(S, log_probs, mask * c
 
 Cases: 2OCJ_A (every residue designable), 2OCJ_A_gap (tests/golden/2OCJ_gap_chainA.pdb: position 24 has mask 0 and keeps its letter,
 positions 54-56 are '-', token 20, mask 0), 2OCJ_A_fixed (chain_M = 0 on every third residue: they decode first and are excluded from
-the loss).
+the loss), 2OCJ_A_hot (2OCJ_A from the heavy weight draw "hot", seed 2: matrices x 3, biases x 5, LayerNorm gamma in [-2, 2]; the
+drawn-mask run only, and beside every float64 result the distance "d32" of the same reference run in float32 from it).
 
 Stored per case: E_idx, randn, decoding_order, chain_M, and per tag log_probs, the loss and per tensor either the full gradient
 (<= 4096 entries) or the sample_index sample with the float64 sum of squares, the dot with the seeded +-1 vector and max|g|. Only
@@ -36,6 +37,15 @@ CASES = {"2OCJ_A": os.path.join(mg.REF, "examples", "2OCJ.pdb"), "2OCJ_A_gap": o
          "2OCJ_A_fixed": os.path.join(mg.REF, "examples", "2OCJ.pdb")}
 
 
+# cases on another weight draw than make_golden's seed 0: (seed, style), and the tags they store. 2OCJ_A_hot is the heavy draw of the
+# 2OCJ_A_hot inference fixture; it stores the drawn-mask run only (the file stays at half the size of the others) and, beside each
+# float64 result, the distance of the SAME reference evaluated in float32 from it ("d32"): the tests' lines on this draw are set
+# against that distance, never against a device's result.
+WEIGHTS = {"2OCJ_A_hot": (2, "hot")}
+TAGS = {"2OCJ_A_hot": ("drawn",)}
+CASES["2OCJ_A_hot"] = CASES["2OCJ_A"]
+
+
 def main(case="2OCJ_A"):
     entry = mg.ref_utils.alt_parse_PDB(CASES[case], "A")[0]
     # the reference's tied_featurize, as in make_finetune_golden.py (model_utils.featurize has no token for the '-' of a numbering gap)
@@ -49,15 +59,20 @@ def main(case="2OCJ_A"):
         chain_M[0, ::3] = 0.0
     if case == "2OCJ_A_gap":
         assert float(mask[0, 24]) == 0.0 and entry["seq"][54:57] == "---"
-    model = ref_mu.ProteinMPNN(k_neighbors=48, augment_eps=0.0, dropout=0.1)
-    missing = model.load_state_dict(synthetic_state_dict(mg.WEIGHT_SEED, "mpnn"), strict=True)
-    assert not missing.missing_keys and not missing.unexpected_keys
-    model = model.double().train()
-    model.features.embeddings.linear.register_forward_pre_hook(lambda mod, args: tuple(x.double() for x in args))
+    weight_seed, style = WEIGHTS.get(case, (mg.WEIGHT_SEED, "xavier"))
     scale = 1.0 / (1.0 - round(0.1 * 2 ** 24) / 2 ** 24)
-    out = dict(seed=np.int64(SEED), step=np.int64(STEP), weight_seed=np.int64(mg.WEIGHT_SEED), chain_M=chain_M[0].numpy())
-    captured = {}
-    for tag in ("ones", "drawn"):
+    out = dict(seed=np.int64(SEED), step=np.int64(STEP), weight_seed=np.int64(weight_seed), chain_M=chain_M[0].numpy())
+    if case in WEIGHTS:
+        out["weight_style"] = np.array(style)
+
+    def run(tag, dtype):
+        """The reference in ``dtype`` under the masks of ``tag`` -> (log_probs, loss, {name: flat gradient}, what the spies saw)."""
+        model = ref_mu.ProteinMPNN(k_neighbors=48, augment_eps=0.0, dropout=0.1)
+        missing = model.load_state_dict(synthetic_state_dict(weight_seed, "mpnn", style), strict=True)
+        assert not missing.missing_keys and not missing.unexpected_keys
+        model = model.to(dtype).train()
+        model.features.embeddings.linear.register_forward_pre_hook(lambda mod, args: tuple(x.to(dtype) for x in args))
+        captured = {}
         for l, layer in enumerate(model.encoder_layers):
             for j, name in enumerate(("dropout1", "dropout2", "dropout3")):
                 rows = L * K if j == 2 else L
@@ -85,19 +100,24 @@ def main(case="2OCJ_A"):
         try:
             model.zero_grad()
             torch.manual_seed(ORDER_SEED)
-            log_probs = model(X.double(), S, mask, chain_M, residue_idx, chain_enc)
+            log_probs = model(X.to(dtype), S, mask, chain_M, residue_idx, chain_enc)
         finally:
             model.features.forward, torch.randn, torch.argsort = feat_fwd, randn, argsort
-        _, loss = ref_mu.loss_smoothed(S, log_probs, mask * chain_M)
+        _, loss = ref_mu.loss_smoothed(S, log_probs.double(), mask * chain_M)
         loss.backward()
-        assert log_probs.dtype == torch.float64 and captured["randn"].shape == chain_M.shape
+        assert log_probs.dtype == dtype and captured["randn"].shape == chain_M.shape
+        grads = {name: (prm.grad if prm.grad is not None else torch.zeros_like(prm)).reshape(-1).double().numpy()
+                 for name, prm in model.named_parameters()}
+        return log_probs[0].detach().double().numpy(), loss.item(), grads, captured
+
+    for tag in TAGS.get(case, ("ones", "drawn")):
+        log_probs, loss, grads, captured = run(tag, torch.float64)
         out["E_idx"] = captured["E_idx"][0].numpy().astype(np.int32)
         out["randn"] = captured["randn"][0].numpy().astype(np.float32)
         out["decoding_order"] = captured["order"][0].numpy().astype(np.int32)
-        out[f"{tag}_log_probs"] = log_probs[0].detach().numpy().astype(np.float32)
-        out[f"{tag}_loss"] = np.float64(loss.item())
-        for name, prm in model.named_parameters():
-            g = (prm.grad if prm.grad is not None else torch.zeros_like(prm)).reshape(-1).numpy()
+        out[f"{tag}_log_probs"] = log_probs.astype(np.float32)
+        out[f"{tag}_loss"] = np.float64(loss)
+        for name, g in grads.items():
             if g.size <= FULL_MAX:
                 out[f"{tag}|{name}|full"] = g.astype(np.float32)
             else:
@@ -106,7 +126,20 @@ def main(case="2OCJ_A"):
                 out[f"{tag}|{name}|sumsq"] = np.float64((g * g).sum())
                 out[f"{tag}|{name}|dot"] = np.float64((g * sign).sum())
                 out[f"{tag}|{name}|absmax"] = np.float64(np.abs(g).max())
-        print(f"{case} {tag}: loss {loss.item():.8f}")
+        print(f"{case} {tag}: loss {loss:.8f}")
+        if case in WEIGHTS:
+            lp32, loss32, g32, cap32 = run(tag, torch.float32)
+            assert np.array_equal(cap32["order"][0].numpy(), captured["order"][0].numpy())
+            live = mask[0].numpy() > 0
+            assert np.array_equal(cap32["E_idx"][0].numpy()[live], captured["E_idx"][0].numpy()[live])
+            out[f"{tag}_log_probs_d32"] = np.float64(np.abs(lp32 - log_probs).max())
+            out[f"{tag}_loss_d32"] = np.float64(abs(loss32 - loss) / abs(loss))
+            worst = 0.0
+            for name, g in grads.items():
+                out[f"{tag}|{name}|d32"] = np.float64(np.abs(g32[name] - g).max())
+                worst = max(worst, float(out[f"{tag}|{name}|d32"]) / float(np.abs(g).max()))
+            print(f"{case} {tag}: max|log_probs| {np.abs(log_probs).max():.1f}, float32 reference: log_probs d32 {out[f'{tag}_log_probs_d32']:.3g}, "
+                  f"loss rel. d32 {out[f'{tag}_loss_d32']:.3g}, worst gradient d32 / max|g| {worst:.3g}")
     path = os.path.join(HERE, f"seqloss_{case}.npz")
     np.savez_compressed(path, **out)
     print(f"seqloss_{case}: L {L} -> {os.path.getsize(path) / 1024:.0f} KiB")

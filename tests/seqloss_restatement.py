@@ -27,18 +27,19 @@ def split_masks(flat, L, K):
     return out
 
 
-def log_probs_f64(sd, X, S, mask, ridx, cenc, E_idx, ranks, site_mult=None):
-    """-> (log_probs [L,21] float64 with a graph, W: {name: float64 leaf}) for ProteinMPNN's state dict ``sd`` (no prefix)."""
+def log_probs_f64(sd, X, S, mask, ridx, cenc, E_idx, ranks, site_mult=None, dtype=torch.float64):
+    """-> (log_probs [L,21] with a graph, W: {name: leaf}) for ProteinMPNN's state dict ``sd`` (no prefix), evaluated in ``dtype``:
+    float64 is the restatement; float32 is the same mathematics at the device's precision, for measuring what fp32 alone costs."""
     from oracle import thermompnn_oracle as O
-    W = {k: torch.as_tensor(v).detach().cpu().double().clone().requires_grad_(True) for k, v in sd.items()}
+    W = {k: torch.as_tensor(v).detach().cpu().to(dtype).clone().requires_grad_(True) for k, v in sd.items()}
     t = lambda a: torch.as_tensor(np.asarray(a))
     E_idx = np.asarray(E_idx)
     L, K = E_idx.shape
-    X, mask = t(X).double()[None], t(mask).double()[None]
+    X, mask = t(X).to(dtype)[None], t(mask).to(dtype)[None]
     ridx, cenc, S = t(ridx).long()[None], t(cenc).long()[None], t(S).long()[None]
     Ei = t(E_idx).long()[None]
     mult = site_mult if site_mult is not None else ones_mult(L, K)
-    m = [t(x).double().view(1, L, 128) if x.shape[0] == L else t(x).double().view(1, L, K, 128) for x in mult]
+    m = [t(x).to(dtype).view(1, L, 128) if x.shape[0] == L else t(x).to(dtype).view(1, L, K, 128) for x in mult]
     atoms = O.backbone_atoms(X)
     D_nb, _ = O.knn(atoms[O.CA], mask, K, Ei)
     blocks = [O.rbf(D_nb)]
@@ -46,10 +47,10 @@ def log_probs_f64(sd, X, S, mask, ridx, cenc, E_idx, ranks, site_mult=None):
         D_ab = torch.sqrt(((atoms[a][:, :, None, :] - atoms[b][:, None, :, :]) ** 2).sum(-1) + 1e-6)
         blocks.append(O.rbf(O.gather_edges(D_ab[..., None], Ei)[..., 0]))
     d = O.positional_index(ridx, cenc, Ei)
-    E_pos = F.linear(F.one_hot(d, 66).double(), W["features.embeddings.linear.weight"], W["features.embeddings.linear.bias"])
+    E_pos = F.linear(F.one_hot(d, 66).to(dtype), W["features.embeddings.linear.weight"], W["features.embeddings.linear.bias"])
     E = F.linear(torch.cat([E_pos] + blocks, -1), W["features.edge_embedding.weight"])
     hE = O.linear(O.layer_norm(E, W, "features.norm_edges"), W, "W_e")
-    hV = torch.zeros(1, L, 128, dtype=torch.float64)
+    hV = torch.zeros(1, L, 128, dtype=dtype)
     ma = mask.unsqueeze(-1) * O.gather_nodes(mask.unsqueeze(-1), Ei).squeeze(-1)
     for l in range(3):
         p = f"encoder_layers.{l}"
@@ -62,7 +63,7 @@ def log_probs_f64(sd, X, S, mask, ridx, cenc, E_idx, ranks, site_mult=None):
         hE = O.layer_norm(hE + m[3 * l + 2] * O.message(hEV, W, p, ("W11", "W12", "W13")), W, p + ".norm3")
     hS = F.embedding(S, W["W_s.weight"])
     r = t(ranks).long()
-    vis = (r[Ei[0]] < r[:, None]).double().view(1, L, K, 1)
+    vis = (r[Ei[0]] < r[:, None]).to(dtype).view(1, L, K, 1)
     hS_j = vis * O.gather_nodes(hS, Ei)
     hVenc_j = O.gather_nodes(hV, Ei)
     for l in range(3):
@@ -77,8 +78,8 @@ def log_probs_f64(sd, X, S, mask, ridx, cenc, E_idx, ranks, site_mult=None):
 
 
 def grads_f64(log_probs, W, dlp):
-    """dL/dW for L = sum(log_probs * dlp) -> {name: float64 grad (zeros where autograd reaches none)}."""
+    """dL/dW for L = sum(log_probs * dlp) -> {name: grad in log_probs' dtype (zeros where autograd reaches none)}."""
     for v in W.values():
         v.grad = None
-    (log_probs * torch.as_tensor(np.asarray(dlp)).double()).sum().backward()
+    (log_probs * torch.as_tensor(np.asarray(dlp)).to(log_probs.dtype)).sum().backward()
     return {k: (v.grad if v.grad is not None else torch.zeros_like(v)).detach() for k, v in W.items()}

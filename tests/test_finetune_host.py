@@ -160,3 +160,41 @@ def test_masked_backbones_parse_to_the_intended_mask_and_gaps(tmp_path, name):
     assert [i for i in range(L) if int(S[i]) == 20] == want_gaps
     assert {0, L - 1} <= set(missing_n) | set(gaps) and sum(want_mask) < L
     assert bool(np.isfinite(X.numpy()).all())                      # NaN coordinates are zeroed once the mask holds them
+
+
+@pytest.mark.parametrize("case", ["2OCJ_A", "2OCJ_A_hot"])
+def test_restatement_reproduces_the_reference_golden(case):
+    """restate() of tests/test_gpu_finetune.py in float64 against the imported reference's float64 loss and gradients under the drawn
+    dropout masks (tests/golden/make_finetune_golden.py), on the Xavier draw and on the heavy one (hot, seed 2; loss 8682): the GPU
+    tests' yardstick computes what the reference computes on both. The loss is stored in float64 and agrees to 1e-12; gradients are
+    stored in float32 (2^-24 relative) and agree to 1e-6 x max|g|. On the hot fixture the reference's own float32 distances, which
+    the GPU test's lines are set against, are checked to sit inside those lines / 2.5."""
+    import os
+    import torch
+    from conftest import GOLDEN, load_golden
+    from test_gpu_finetune import AA20, RELEASED, numpy_site_mask, restate
+    from thermompnn_amd.datasets import Mutation
+    from thermompnn_amd.finetune import slab_shapes
+    from thermompnn_amd.pdb_io import alt_parse_PDB
+    from train_weight_cases import SCALE, check_against_golden, cpu_protein, transfer_weights
+    g = load_golden("finetune_" + case)
+    pdb = alt_parse_PDB(os.path.join(GOLDEN, "2OCJ.pdb"), ["A"])
+    muts = [Mutation(int(p), AA20[w], AA20[m], None if np.isnan(t) else torch.tensor([float(t)]), "2OCJ")
+            for p, w, m, t in zip(g["positions"], g["wildtype"], g["mutation"], g["targets"])]
+    prot = cpu_protein(pdb, muts)
+    L, K = prot.L, 48
+    seed, step = int(g["seed"]), int(g["step"])
+    mult = [numpy_site_mask(seed, step, s, L * K if s < 9 and s % 3 == 2 else L).astype(np.float64) * SCALE for s in range(15)]
+    sd = transfer_weights(RELEASED, str(g["weight_style"]) if "weight_style" in g else "xavier", int(g["weight_seed"]))
+    names = list(slab_shapes(RELEASED["hidden_dims"], 2, True))
+    loss, grads, _ = restate(sd, names, prot, g["E_idx"].astype(np.int64), mult, None, 2, True, True)
+    print(case, "loss", loss, "reference", float(g["drawn_loss"]))
+    assert abs(loss - float(g["drawn_loss"])) <= 1e-12 * float(g["drawn_loss"])
+    worst = check_against_golden(g, "drawn", grads, 1e-6)
+    print(case, "worst gradient distance / max|g|:", worst)
+    if case.endswith("_hot"):
+        assert str(g["weight_style"]) == "hot" and float(g["drawn_loss"]) > 1e3
+        assert float(g["drawn_loss_d32"]) <= 1e-6 / 2.5
+        for k, v in grads.items():
+            gmax = float(v.abs().max())
+            assert float(g[f"drawn|{k}|d32"]) <= 1e-4 / 2.5 * gmax or gmax <= 1e-12, k

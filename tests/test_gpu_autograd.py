@@ -11,7 +11,8 @@ import torch
 import torch.nn.functional as F
 
 from conftest import GOLDEN, REPO, load_golden
-from test_gpu_finetune import AA20, CASES, RELEASED, _case_mutants, _golden_sample_index, _mutants, _pdb, restate
+from test_gpu_finetune import AA20, CASES, NF0, RELEASED, _case_mutants, _golden_sample_index, _mutants, _pdb, restate
+from train_weight_cases import UPSTREAM_CASE
 
 pytestmark = pytest.mark.gpu
 
@@ -27,11 +28,11 @@ def _cfg(tmp_path, head=None, subtract=True, freeze=False, training=None):
     return Config.wrap(d)
 
 
-def _model(tmp_path, head=None, subtract=True, freeze=False, seed=0):
+def _model(tmp_path, head=None, subtract=True, freeze=False, seed=0, style="xavier"):
     from thermompnn_amd import weights
     from thermompnn_amd.transfer_model import TransferModel
     head = head or RELEASED
-    sd = weights.synthetic_state_dict(seed, head=head)
+    sd = weights.synthetic_state_dict(seed, style=style, head=head)
     vdir = os.path.join(str(tmp_path), "vanilla_model_weights")
     os.makedirs(vdir, exist_ok=True)
     weights.save_vanilla_checkpoint(os.path.join(vdir, "v_48_020.pt"), weights.split_transfer_state_dict(sd)[0], 48)
@@ -166,8 +167,22 @@ SPLIT_CASES = CASES + [("2OCJ_A_gap", RELEASED, True, True), ("msk_L40", RELEASE
 @pytest.mark.parametrize("case,head,subtract,dropout", SPLIT_CASES,
                          ids=[f"{c[0]}-nf{c[1]['num_final_layers']}-la{int(c[1]['lightattn'])}" for c in SPLIT_CASES])
 def test_split_forward_backward_equals_the_fused_step_bit_for_bit(tmp_path, case, head, subtract, dropout):
+    _split_equals_fused(tmp_path, case, head, subtract)
+
+
+# the heavy draws ("hot": matrices x 3, biases x 5, LayerNorm gamma in [-2, 2]): (case, head, subtract, style, weight seed)
+HOT_SPLIT_CASES = [("msk_L40", RELEASED, True, "hot", 0), ("syn_L17", NF0, True, "hot", 2)]
+
+
+@pytest.mark.parametrize("case,head,subtract,style,seed", HOT_SPLIT_CASES, ids=[f"{c[0]}-nf{c[1]['num_final_layers']}-{c[3]}{c[4]}"
+                                                                                for c in HOT_SPLIT_CASES])
+def test_split_forward_backward_equals_the_fused_step_bit_for_bit_on_hot_weights(tmp_path, case, head, subtract, style, seed):
+    _split_equals_fused(tmp_path, case, head, subtract, style, seed)
+
+
+def _split_equals_fused(tmp_path, case, head, subtract, style="xavier", seed=0):
     from thermompnn_amd.finetune import MPNNTrainer
-    model = _model(tmp_path, head, subtract)
+    model = _model(tmp_path, head, subtract, seed=seed, style=style)
     tr = MPNNTrainer(model, seed=7)
     pdb = _pdb(case, tmp_path)
     prot = tr.prepare([(pdb, _case_mutants(case, pdb))])[0]
@@ -262,6 +277,45 @@ def test_arbitrary_upstream_gradient_and_finite_differences(tmp_path):
         fd = (vals[0] - vals[1]) / (2 * h)
         g = float(flat_grad[i])
         assert abs(fd - g) <= 1e-2 * abs(g), (name, fd, g)
+
+
+def test_arbitrary_upstream_gradient_matches_the_restatement_on_hot_weights(tmp_path):
+    """The objective of test_arbitrary_upstream_gradient_and_finite_differences, sum(pred * c) through loss.backward(), from the hot
+    draw (seed 0), against restate() with the same upstream gradient on the device's graph: the objective within 1e-5 relative and
+    every .grad within 1e-4 x max|g|, the fine-tune tests' lines. The restatement in float32 alone is at 1.4e-6 resp. 5.0e-6 on this
+    case (tests/test_train_weights_host.py, the "upstream" case). First passing run on the MI355X: objective 3.63e-6 relative,
+    worst gradient 4.15e-6 of max|g| (ddg_out.weight)."""
+    from thermompnn_amd.finetune import MPNNTrainer
+    case, head, subtract, style, seed = UPSTREAM_CASE
+    model = _model(tmp_path, head, subtract, seed=seed, style=style)
+    model.differentiable = True
+    model.eval()
+    pdb = _pdb(case, tmp_path)
+    muts = _mutants(pdb, 30, with_none=False)
+    c = torch.from_numpy(np.random.default_rng(4).normal(size=len(muts)).astype(np.float32))
+    pred, _ = model(pdb, muts)
+    objective = (torch.cat([p["ddG"] for p in pred]) * c.cuda()).sum()
+    objective.backward()
+    tr = MPNNTrainer(model)
+    prot = _all_mutants(tr, pdb, muts)
+    assert prot.M == len(muts)
+    L, K = prot.L, min(48, prot.L)
+    E_idx = torch.empty((L, K), dtype=torch.int32, device="cuda")
+    tr.forward_backward(prot, p_mpnn=0.0, p_head=0.0, E_idx_out=E_idx)
+    torch.cuda.synchronize()
+    ones = [np.ones((L * (K if s < 9 and s % 3 == 2 else 1), 128), np.float32) for s in range(15)]
+    ref_obj, ref, _ = restate(model.state_dict(), list(tr.shapes), prot, E_idx.cpu().numpy(), ones, None, 2, True, subtract, upstream=c)
+    params = dict(model.named_parameters())
+    ratio = {k: float((params[k].grad.cpu().double() - r).abs().max()) / float(r.abs().max()) for k, r in ref.items()
+             if float(r.abs().max()) > 1e-12}
+    print(f"hot upstream: objective {ref_obj:.5g} rel. error {abs(float(objective.detach()) - ref_obj) / abs(ref_obj):.3g}, worst gradient "
+          f"error / max|g| {max(ratio.values()):.3g}", max(ratio, key=ratio.get))
+    assert abs(float(objective.detach()) - ref_obj) <= 1e-5 * max(abs(ref_obj), 1e-3)
+    for k in tr.shapes:
+        g, r = params[k].grad.cpu().double(), ref[k]
+        gmax, err = float(r.abs().max()), float((g - r).abs().max())
+        assert err <= 1e-4 * gmax or err <= 1e-12, (k, err, gmax)
+    assert float(ref["prot_mpnn.W_e.weight"].abs().max()) > 0.0 and model.prot_mpnn.W_out.weight.grad is None
 
 
 def test_frozen_encoder_gets_no_grad_and_head_grads_equal_the_split_backward(tmp_path):

@@ -11,6 +11,7 @@ from conftest import GOLDEN, load_golden
 from masked_backbones import layout_arrays
 from seqloss_restatement import grads_f64, log_probs_f64, split_masks
 from test_gpu_finetune import _golden_sample_index, numpy_site_mask
+from train_weight_cases import HOT_F64_FACTOR, SEQLOSS_WEIGHT_CASES, mpnn_weights, seq_id
 
 pytestmark = pytest.mark.gpu
 
@@ -107,32 +108,42 @@ def _smoothed_and_dlp(S, lp, weight_mask):
 
 
 # ---- 1. the reference's goldens ------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", ["2OCJ_A", "2OCJ_A_gap", "2OCJ_A_fixed"])
+@pytest.mark.parametrize("case", ["2OCJ_A", "2OCJ_A_gap", "2OCJ_A_fixed", "2OCJ_A_hot"])
 def test_log_probs_loss_and_gradients_match_the_reference_golden(case):
     """The imported reference in float64 (tests/golden/make_seqloss_golden.py), all-ones and generator-drawn dropout masks, with the
-    criteria test_gpu_finetune.py applies to the same kernels."""
+    criteria test_gpu_finetune.py applies to the same kernels.
+
+    2OCJ_A_hot is 2OCJ_A from the heavy weight draw (hot, seed 2; the drawn masks only; max|log_probs| 29.3). The fixture records how
+    far the imported reference ITSELF is from its float64 result when run in float32: log_probs 1.81e-5, loss 4.7e-9 relative, worst
+    gradient 1.4e-6 of max|g|. log_probs and the loss are held to max(the Xavier line, 2.5 x that recorded distance) - 4.5e-5 for
+    log_probs, the unchanged 1e-6 for the loss - and the gradients to the unchanged 1e-4 x max|g|. First passing run (MI355X):
+    log_probs 2.10e-5, loss 1.6e-9 relative, worst gradient 2.05e-6 of max|g|."""
     from thermompnn_amd.protein_mpnn_utils import decoding_ranks
     g = load_golden("seqloss_" + case)
     _, (X, S, mask, ridx, cenc) = _features("2OCJ_gap_chainA.pdb" if case.endswith("gap") else "2OCJ.pdb")
     chain_M = torch.from_numpy(g["chain_M"])
     ranks = decoding_ranks(chain_M * mask, torch.from_numpy(g["randn"]))
-    call = Call(X, S, mask, ridx, cenc, ranks)
+    sd = mpnn_weights(str(g["weight_style"]), int(g["weight_seed"])) if "weight_style" in g else None
+    call = Call(X, S, mask, ridx, cenc, ranks, sd=sd)
     L, K = call.L, call.Keff
     seed, step = int(g["seed"]), int(g["step"])
     drawn = np.concatenate([numpy_site_mask(seed, step, s, L * K if s < 9 and s % 3 == 2 else L).reshape(-1) for s in range(15)])
     live = mask.numpy() > 0
-    for tag in ("ones", "drawn"):
+    for tag in [t for t in ("ones", "drawn") if f"{t}_loss" in g]:
         kw = dict(keep_in=torch.from_numpy(drawn).cuda(), p=0.1) if tag == "drawn" else dict(p=0.0)
+        # a fixture of a heavy draw carries the reference's own float32 distance from its float64 result: the line is 2.5 x that
+        lp_line = max(1e-5, HOT_F64_FACTOR * float(g.get(f"{tag}_log_probs_d32", 0.0)))
+        loss_line = max(1e-6, HOT_F64_FACTOR * float(g.get(f"{tag}_loss_d32", 0.0)))
         lp = call.forward(seed=seed, step=step, **kw)
         assert np.array_equal(call.E_idx.cpu().numpy()[live], g["E_idx"][live]), "the device's k-NN graph differs from the reference's"
         assert bool(torch.isfinite(lp).all())
         err = float(np.abs(lp.cpu().numpy() - g[f"{tag}_log_probs"]).max())
-        print(case, tag, "max |log_probs - reference|:", err)
-        assert err <= 1e-5
+        print(case, tag, "max |log_probs - reference|:", err, "line", lp_line)
+        assert err <= lp_line
         loss, dlp = _smoothed_and_dlp(S, lp, mask * chain_M)
         ref_loss = float(g[f"{tag}_loss"])
         print(case, tag, "loss", loss, "reference", ref_loss)
-        assert abs(loss - ref_loss) <= 1e-6 * abs(ref_loss)
+        assert abs(loss - ref_loss) <= loss_line * abs(ref_loss)
         grads = _split(call.backward(dlp, seed=seed, step=step, **kw))
         assert "W_out.weight" in grads and "W_out.bias" in grads
         worst = 0.0
@@ -184,6 +195,13 @@ def _restated(call, arrays, ranks, site_mult, dlp, sd=None):
     return lp.detach(), grads_f64(lp, W, dlp)
 
 
+def _restated_fp32_log_probs(call, arrays, ranks, site_mult, sd):
+    """The restatement's forward in float32 on the CPU, on the device's graph: what fp32 alone is away from float64 on this case."""
+    X, S, mask, ridx, cenc = arrays
+    with torch.no_grad():
+        return log_probs_f64(sd, X, S, mask, ridx, cenc, call.E_idx.cpu().numpy(), ranks, site_mult, dtype=torch.float32)[0].double()
+
+
 @pytest.mark.parametrize("name,K,kind,dropout", RESTATE_CASES, ids=[f"{c[0]}-K{c[1]}-{c[2]}-d{int(c[3])}" for c in RESTATE_CASES])
 def test_every_gradient_matches_the_float64_restatement(name, K, kind, dropout):
     """log_probs within 1e-5 and every gradient within GRAD_TOL x max|g| (or 1e-12 on a structural zero) of
@@ -232,6 +250,72 @@ def test_every_gradient_matches_the_float64_restatement(name, K, kind, dropout):
     if name.startswith("msk_"):                        # a masked row is finite and carries the bias-only distribution
         dead = np.nonzero(mask == 0)[0]
         assert len(dead) and bool(torch.equal(lp[dead[0]], lp[dead[-1]]))
+
+
+@pytest.mark.parametrize("name,K,kind,dropout,style,seed", SEQLOSS_WEIGHT_CASES, ids=[seq_id(c) for c in SEQLOSS_WEIGHT_CASES])
+def test_every_gradient_matches_the_float64_restatement_on_heavy_weight_draws(name, K, kind, dropout, style, seed):
+    """The body of test_every_gradient_matches_the_float64_restatement away from the Xavier draw of seed 0: "hot" weights (matrices
+    x 3, biases x 5, LayerNorm gamma in [-2, 2]; |log_probs| to 28), "wide" weights (matrices x 8; |log_probs| to 61) and a second
+    Xavier seed. gelu' sees saturated and strongly negative pre-activations, the LayerNorm backward negative and large gamma, the
+    log-softmax backward rows whose probabilities span e^-60 .. 1.
+
+    Every gradient within FINETUNE_TOL x max|g| (or 1e-12 on a structural zero): GRAD_TOL was measured on the Xavier cases and the
+    restatement in float32 alone is at 7.5e-6 at wide (tests/test_train_weights_host.py, which also asserts that float32 meets
+    FINETUNE_TOL / 2.5 on each of these cases). log_probs within max(1e-5, 2.5 x |restatement float32 - restatement float64|), the
+    float32 side computed here on the CPU on the device's graph: float32 alone is 1.1e-5 .. 1.5e-5 from float64 at hot and
+    3.1e-5 .. 3.6e-5 at wide.
+
+    First passing run (MI355X), in the order of SEQLOSS_WEIGHT_CASES - worst device gradient error / max|g| (the restatement's own
+    float32 figure from the host test), then the device's log_probs error (the float32 restatement's in the same run):
+    hot 0 2.21e-6 (1.62e-6), 1.61e-5 (1.01e-5); hot 2 with dropout 3.28e-6 (2.80e-6), 1.38e-5 (1.40e-5); wide 0 9.21e-6 (7.53e-6),
+    2.91e-5 (2.71e-5); xavier 1 1.29e-6 (1.20e-6), 2.71e-6 (1.82e-6); msk_L56 hot 2 2.15e-6 (2.24e-6), 1.91e-5 (9.83e-6); msk_L56 at
+    K = 30 wide 0 3.59e-6 (3.89e-6), 3.72e-5 (2.46e-5); msk_L17 hot 0 with dropout 7.33e-6 (4.84e-6), 1.50e-5 (8.99e-6); ties
+    1.88e-6 (1.93e-6), 1.13e-5 (9.22e-6); all ranks equal 2.88e-6 (2.04e-6), 1.51e-5 (1.01e-5). Every run prints its own figures."""
+    arrays = layout_arrays(name)
+    X, S, mask, ridx, cenc = arrays
+    L = len(S)
+    ranks = _ranks(kind, L)
+    sd = mpnn_weights(style, seed)
+    call = Call(X, S, mask, ridx, cenc, ranks, K, sd=sd)
+    Keff = call.Keff
+    assert Keff == min(K, L)
+    keep_out = torch.full((call.mask_numel(),), -1.0, device="cuda") if dropout else None
+    lp = call.forward(p=0.1 if dropout else 0.0, seed=7, step=3, keep_out=keep_out)
+    dlp = torch.from_numpy(np.random.default_rng(1).normal(size=(L, 21)).astype(np.float32))
+    grads = _split(call.backward(dlp, p=0.1 if dropout else 0.0, seed=7, step=3))
+    site_mult = None
+    if dropout:
+        keep = split_masks(keep_out.cpu().numpy(), L, Keff)
+        for s in range(15):                            # the in-kernel masks are the documented generator's
+            assert np.array_equal(keep[s], numpy_site_mask(7, 3, s, keep[s].shape[0])), s
+        site_mult = [k * SCALE for k in keep]
+    ref_lp, ref = _restated(call, arrays, ranks, site_mult, dlp, sd=sd)
+    fp32_dist = float((_restated_fp32_log_probs(call, arrays, ranks, site_mult, sd) - ref_lp).abs().max())
+    lp_line = max(1e-5, HOT_F64_FACTOR * fp32_dist)
+    assert bool(torch.isfinite(lp).all())
+    lp_err = float((lp.cpu().double() - ref_lp).abs().max())
+    worst = {}
+    for k, gt in grads.items():
+        d, r = gt.cpu().double(), ref[k]
+        gmax, err = float(r.abs().max()), float((d - r).abs().max())
+        worst[k] = err / gmax if gmax > 1e-12 else 0.0
+    print(f"{seq_id((name, K, kind, dropout, style, seed))}: max|log_probs| {float(ref_lp.abs().max()):.1f}, log_probs error {lp_err:.3g} "
+          f"(restatement float32 {fp32_dist:.3g}, line {lp_line:.3g}), worst gradient error / max|g|: {max(worst.values()):.3g}",
+          max(worst, key=worst.get))
+    assert lp_err <= lp_line, (lp_err, lp_line)
+    for k, gt in grads.items():
+        d, r = gt.cpu().double(), ref[k]
+        gmax, err = float(r.abs().max()), float((d - r).abs().max())
+        assert err <= FINETUNE_TOL * gmax or err <= 1e-12, (k, err, gmax)
+    if kind == "equal":                                # every edge invisible: no sequence information reaches the loss
+        assert float(grads["W_s.weight"].abs().max()) == 0.0
+        for l in range(3):
+            assert float(grads[f"decoder_layers.{l}.W1.weight"][:, 256:384].abs().max()) == 0.0
+            assert float(grads[f"decoder_layers.{l}.W1.weight"][:, 384:].abs().max()) > 0.0
+    else:
+        assert float(grads["W_s.weight"].abs().max()) > 0.0
+    dead = np.nonzero(mask == 0)[0]                    # a masked row is finite and carries the bias-only distribution
+    assert len(dead) and bool(torch.equal(lp[dead[0]], lp[dead[-1]]))
 
 
 # ---- 3. forward consistency with inference -------------------------------------------------------------------------------------------
@@ -313,10 +397,20 @@ def _batch(names):
 
 
 def test_module_backward_fills_every_grad_with_the_c_abi_gradients():
+    _module_backward_equals_the_c_abi("xavier", 0)
+
+
+def test_module_backward_fills_every_grad_with_the_c_abi_gradients_on_a_hot_draw():
+    """The same bit equality from the heavy draw (hot, seed 2): the module hands the kernels the weights it holds, whatever they are."""
+    _module_backward_equals_the_c_abi("hot", 2)
+
+
+def _module_backward_equals_the_c_abi(style, seed):
     from thermompnn_amd import model_utils as mu
     from thermompnn_amd.autograd import dropout_key
     from thermompnn_amd.protein_mpnn_utils import decoding_ranks
-    model = _module(dropout=0.1).train()
+    sd = mpnn_weights(style, seed)
+    model = _module(dropout=0.1, sd=sd).train()
     X, S, mask, chain_M, ridx, cenc = _batch(["msk_L40"])
     randn = torch.randn(chain_M.shape, generator=torch.Generator().manual_seed(4)).cuda()
     with dropout_key(5, 9):
@@ -325,7 +419,7 @@ def test_module_backward_fills_every_grad_with_the_c_abi_gradients():
     loss = mu.loss_smoothed(S, lp, mask * chain_M)[1]
     loss.backward()
     ranks = decoding_ranks(chain_M * mask, randn)[0].cpu().numpy()
-    call = Call(*layout_arrays("msk_L40"), ranks)
+    call = Call(*layout_arrays("msk_L40"), ranks, sd=sd)
     lp_c = call.forward(p=0.1, seed=5, step=9)
     assert torch.equal(lp_c, lp[0].detach())
     leaf = lp_c.clone().requires_grad_(True)
