@@ -358,6 +358,45 @@ int tmpnn_seqloss_backward(const float *X, const int32_t *S, const float *mask, 
                            const float *keep_in, uint64_t seed, uint64_t step, const float *dlog_probs, float *grads,
                            const void *saved, size_t saved_bytes, void *scratch, size_t scratch_bytes, tmpnn_stream_t stream);
 
+/* ---- the same objective over a packed batch: one forward, one backward for n_proteins proteins ---------------------------------
+ * X [T,4,3], S, mask, residue_idx, chain_enc, ranks [T] packed as tmpnn_encode takes them; protein b owns the rows
+ * [offsets[b], offsets[b+1]) (offsets: device int32 [n_proteins + 1], offsets[0] = 0, offsets[n_proteins] = T). The caller promises
+ * every segment length in [min_len, max_len], 2 <= min_len <= max_len <= 8192, so n_proteins min_len <= T <= n_proteins max_len.
+ * Neighbours come from the protein's own rows (the k-NN kernel of tmpnn_knn_topk with these offsets: a protein's graph does not depend
+ * on the batch it is packed into); E_idx_opt [T, K] holds global rows. ranks are compared inside a protein only (a neighbour is always
+ * in the same segment). ONE K serves the call: K = min(k_neighbors, min_len). A call with min_len < k_neighbors is accepted only when
+ * min_len == max_len (the padded [B, L] pack, B segments of L rows); otherwise TMPNN_E_INVALID, the message names both numbers.
+ * log_probs [T,21]: the rows of protein b are bit for bit what tmpnn_seqloss_forward gives for that protein alone at this K without
+ * dropout. grads receives the gradient of the whole batch, the sum over proteins, written as tmpnn_seqloss_backward writes it (the
+ * entries that can be non-zero, into a slab the caller has zeroed); the fixed row blocks of a weight gradient run over the packed
+ * rows, so it equals the sum of the proteins' own gradients to rounding, not bit for bit, except at n_proteins = 1, which is
+ * tmpnn_seqloss_* exactly. Deterministic as the one-protein entries: no float atomics, bit-identical reruns, a second backward over
+ * the same `saved` gives the same bits.
+ * Dropout: the same generator and the same 15 sites; `row` is the PACKED row (i for a node site, i K + k for an edge site), and the flat
+ * keep_in / keep_out buffer has the one-protein layout of a "protein" of T rows at this K: tmpnn_seqloss_batch_mask_numel(T, K) =
+ * (12 T + 3 T K) 128 floats, the sites in order, each [rows, 128] with no tail (the one-protein entries lay an edge site out for
+ * min(48, L) whatever K). With n_proteins = 1 the numbering coincides with the one-protein entry's. A protein's masks therefore DEPEND
+ * ON WHERE IT SITS in the batch: the same (seed, step) gives a protein other masks at another offset.
+ * status_opt (device int32, may be NULL) is zeroed on the stream and receives TMPNN_STATUS_MAXLEN when a segment's length lies outside
+ * [min_len, max_len], offsets[0] != 0 or offsets[n_proteins] != T (one workgroup checks this at the head of the forward). The kernels
+ * keep their clamps: a caller whose offsets break the promise gets wrong numbers and the status bit, never an access outside the
+ * buffers. T <= 65536 (tmpnn_seqbatch.hip derives it): the sizers return 0 above it, for T < 2, n_proteins < 1 or > T / 2, K outside
+ * [1, 48] or K > T (mask_numel: -1), and the entries return TMPNN_E_UNSUPPORTED above it. `saved` holds about 0.8 MB per residue at
+ * K = 48. Error codes before any launch as tmpnn_seqloss_*. */
+size_t tmpnn_seqloss_batch_saved_bytes(int64_t T, int n_proteins, int K);
+size_t tmpnn_seqloss_batch_scratch_bytes(int64_t T, int n_proteins, int K);
+int64_t tmpnn_seqloss_batch_mask_numel(int64_t T, int K);
+int tmpnn_seqloss_batch_forward(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
+                                const int32_t *offsets, int n_proteins, int64_t T, int min_len, int max_len, int k_neighbors,
+                                const int32_t *ranks, const float *params, int64_t slab_numel, float p_mpnn, const float *keep_in,
+                                float *keep_out, uint64_t seed, uint64_t step, float *log_probs, int32_t *E_idx_opt, int32_t *status_opt,
+                                void *saved, size_t saved_bytes, tmpnn_stream_t stream);
+int tmpnn_seqloss_batch_backward(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
+                                 const int32_t *offsets, int n_proteins, int64_t T, int min_len, int max_len, int k_neighbors,
+                                 const int32_t *ranks, const float *params, int64_t slab_numel, float p_mpnn, const float *keep_in,
+                                 uint64_t seed, uint64_t step, const float *dlog_probs, float *grads, const void *saved,
+                                 size_t saved_bytes, void *scratch, size_t scratch_bytes, tmpnn_stream_t stream);
+
 /* ---- the fused path ------------------------------------------------------------------------------
  * Everything TransferModel.forward does on the device for a ragged batch of N proteins
  * (transfer_model.py:75-121 + protein_mpnn_utils.py:1222-1277), one call, 18 launches on `stream` (14 when every workgroup has at most one residue tile).

@@ -37,25 +37,16 @@
 // (FtSeg::vis, ft_row), the inverse-neighbour gathers of the backward take it too (FtCollect::vis), the output layer W_out with its
 // log-softmax closes the forward and seeds the backward from any dL / dlog_probs, and the slab is the whole state dict (sq_layout).
 // Every operand of the ddG path has vis = 0 and keeps its arithmetic.
+//
+// Segments: ft_forward / ft_backward run over L rows in n_prot segments (FtCtx, tmpnn_ft.h). Every entry of this file has one segment
+// [0, L]; the packed sequence loss (tmpnn_seqbatch.hip, tmpnn_seqloss_batch_*) runs the same two functions over a batch's T rows.
 #include <math.h>
 #include <stdint.h>
 
 #include <algorithm>
 #include <utility>
 
-#include "tmpnn_common.h"
-#include "tmpnn_internal.h"
-
-#define FT_REQUIRE(cond, ...) do { if (!(cond)) return tm_set_error(TMPNN_E_INVALID, __VA_ARGS__); } while (0)
-#define FT_TRY(expr) do { int rc_ = (expr); if (rc_ != TMPNN_OK) return rc_; } while (0)
-
-static const int FT_H = 128;
-static const int FT_SITES = 15;
-static const int FT_MAX_PARTS = 256;     // row blocks of a weight gradient over [L K] rows
-static const int FT_CLS_PARTS = 64;      // row blocks of a class-indexed / column sum
-static const int FT_MAX_LAYERS = 8;
-static const int64_t FT_L_MAX = 8192;    // the k-NN kernel's LDS bound (tmpnn_graph.hip) holds well past this
-static const int64_t FT_M_MAX = 1 << 22;
+#include "tmpnn_ft.h"
 
 __device__ __forceinline__ uint64_t ft_mix(uint64_t x) {   // = tr_mix (tmpnn_train.hip)
     x ^= x >> 30;
@@ -71,9 +62,7 @@ __device__ __forceinline__ float ft_gelu_d(float x) {
     return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * 0.39894228040143268f * expf(-0.5f * x * x);
 }
 
-// ---- dropout --------------------------------------------------------------------------------------------------------------------
-struct FtDrop { int mode; const float *keep_in; float *keep_out; uint64_t k2; uint32_t thr; float scale; int64_t off[FT_SITES]; };
-
+// ---- dropout (FtDrop: tmpnn_ft.h) -------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float ft_keep(const FtDrop &d, int site, int row, int col) {
     if (d.mode == 0) return 1.f;
     const int64_t idx = d.off[site] + (int64_t)row * FT_H + col;
@@ -289,15 +278,23 @@ __device__ __forceinline__ void ft_atom(const float *x, int a, float *o) {   // 
     for (int k = 0; k < 3; ++k) o[k] = -0.58273431f * av[k] + 0.56802827f * b[k] - 0.54067466f * cc[k] + x[3 + k];
 }
 
-// per edge e = (i, k): compact E_idx, positional class, Ein[e] = [W_pos[:, cls] + b_pos | 400 RBF]
-struct FtGraph { const float *X; const int32_t *ridx, *cenc, *E48; const float *D48, *pos_w, *pos_b; int32_t *eidx, *cls; float *Ein; int L, K; };
+// per edge e = (i, k): compact E_idx, positional class, Ein[e] = [W_pos[:, cls] + b_pos | 400 RBF]. L rows in N segments (offs [N + 1],
+// already made safe: ft_offsets_kernel / sq_segments_kernel); a neighbour is clamped into its residue's own segment.
+struct FtGraph { const float *X; const int32_t *ridx, *cenc, *E48; const float *D48, *pos_w, *pos_b; int32_t *eidx, *cls; float *Ein; int L, K;
+                 const int32_t *offs; int N; };
 
 __global__ __launch_bounds__(TM_THREADS) void ft_graph_kernel(FtGraph a) {
     const int64_t E = (int64_t)a.L * a.K, stride = (int64_t)tm_nblk() * TM_THREADS;
     for (int64_t e = (int64_t)tm_bid() * TM_THREADS + tm_tid(); e < E; e += stride) {
         const int i = (int)(e / a.K), k = (int)(e - (int64_t)i * a.K);
+        int lo = 0, hi = a.N;                                 // segment p with offs[p] <= i < offs[p + 1] (as the k-NN kernel finds it)
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (a.offs[mid] <= i) lo = mid; else hi = mid;
+        }
+        const int s0 = min(max(a.offs[lo], 0), a.L - 1), s1 = min(max(a.offs[lo + 1], s0 + 1), a.L);
         int j = a.E48[(size_t)i * TM_KS + k];
-        j = min(max(j, 0), a.L - 1);
+        j = min(max(j, s0), s1 - 1);
         a.eidx[e] = j;
         const int cl = a.cenc[i] == a.cenc[j] ? min(max(a.ridx[i] - a.ridx[j] + 32, 0), 64) : 65;
         a.cls[e] = cl;
@@ -529,13 +526,7 @@ static int ft_dims_ok(int n_final, int n_layers, const int32_t *dims) {
     return 1;
 }
 
-// Slab offsets: ProteinMPNN's tensors in state-dict order (weights.mpnn_param_shapes) without W_out.weight / W_out.bias (log_probs is
-// not in the loss: no gradient, never touched), then the head slab of tmpnn_head_slab_numel. With num_final_layers = 0 the head reads
-// W_s[S] only: W_s is then the one ProteinMPNN tensor in the slab.
-struct FtEncP { int64_t n1w, n1b, n2w, n2b, n3w, n3b, W1, b1, W2, b2, W3, b3, W11, b11, W12, b12, W13, b13, Win, bin, Wout, bout; };
-struct FtDecP { int64_t n1w, n1b, n2w, n2b, W1, b1, W2, b2, W3, b3, Win, bin, Wout, bout; };
-struct FtLayout { int64_t posw, posb, edgew, new_, neb, Wew, Web, Ws; FtEncP enc[3]; FtDecP dec[3]; int64_t head, total, Wo, bo; };
-
+// Slab offsets (FtLayout: tmpnn_ft.h)
 static FtLayout ft_layout(int n_final) {
     FtLayout S{};
     int64_t o = 0;
@@ -567,7 +558,7 @@ static FtLayout ft_layout(int n_final) {
 
 // The sequence loss's slab, a layout of its own: ProteinMPNN's tensors in state-dict order with W_out.weight [21,128] and W_out.bias
 // [21] at the end, and no head.
-static FtLayout sq_layout() {
+FtLayout sq_layout() {
     FtLayout S = ft_layout(3);
     S.Wo = S.head;
     S.bo = S.Wo + TMPNN_VOCAB * FT_H;
@@ -584,38 +575,19 @@ static int ft_cparts(int64_t R) {
     return (int)(p < 1 ? 1 : p > FT_CLS_PARTS ? FT_CLS_PARTS : p);
 }
 
-// Workspace, in two parts carved in a fixed order. SAVED: what the backward reads from the forward (the graph, the features, every
-// saved activation, W_s[S], the head rows) and the head's workspace of the forward. SCRATCH: what only the backward writes (the CSR
-// lists, the gradients of activations, the weight-gradient partials) and the head's workspace of the backward. The fused entries take
-// one workspace, saved part first; there the forward's temporaries (ftm, fdh, fdF) are the backward's tm, dh1, dF, and both head
-// passes share one head workspace. The split entries (tmpnn_finetune_forward / _backward) give the forward its own temporaries in the
-// saved part and the backward its own head workspace in the scratch part, so that the backward never writes the saved part.
-struct FtEncS { float *a1, *a2, *b1, *b2, *x3, *mu3, *rs3, *x1, *mu1, *rs1, *hV1, *fa, *x2, *mu2, *rs2, *out; };
-struct FtDecS { float *a1, *a2, *x1, *mu1, *rs1, *hV1, *fa, *x2, *mu2, *rs2, *out; };
-struct FtWs {
-    int32_t *offs, *E48, *eidx, *cls, *cnt, *cur, *coff, *clist, *mcnt, *mcur, *moff, *mlist, *rows_id, *status;
-    float *D48, *Ein, *E0, *nemu, *ners, *En, *hE[4], *hV0, *hS, *headX, *dheadX;
-    FtEncS enc[3];
-    FtDecS dec[3];
-    float *tm, *t1, *t2, *dA, *dE, *dE2, *dEd, *gx, *gb, *dEp, *dV, *dV2, *dh1, *dF, *dhS, *dH[3], *dG, *P, *CP;
-    float *ftm, *fdh, *fdF;                       // the forward's temporaries: message / LayerNorm input, message sum, FFN output
-    float *lp, *dlg, *dVe;                        // the sequence loss: saved log_probs [L,21]; d logits; the encoder output's gradient
-    void *head_ws, *head_ws_b;                    // the head's workspace of the forward / of the backward
-    size_t head_bytes, saved_bytes, scratch_bytes, bytes;
-};
-
+// The workspace in two parts (FtWs, tmpnn_ft.h), carved in a fixed order.
 // seq: the sequence loss's buffers (tmpnn_seqloss_*): no mutants and no head (M = 0, dims unused), log_probs and two gradients more.
-static FtWs ft_carve2(void *saved, void *scratch, bool split, int64_t L, int64_t M, int lightattn, int n_layers, const int32_t *dims,
-                      bool seq = false) {
+FtWs ft_carve2(void *saved, void *scratch, bool split, int64_t L, int64_t M, int lightattn, int n_layers, const int32_t *dims, bool seq,
+               int64_t Kc, int64_t n_prot) {
     FtWs w{};
     Carver sv(saved, false), sc(scratch, false);       // (a null base measures; the entries compare with the byte counts first)
     auto f = [&](int64_t n) { return sv.take<float>((size_t)n); };
     auto i32 = [&](int64_t n) { return sv.take<int32_t>((size_t)n); };
     auto fc = [&](int64_t n) { return sc.take<float>((size_t)n); };
     auto ic = [&](int64_t n) { return sc.take<int32_t>((size_t)n); };
-    const int64_t K = L < TM_KS ? L : TM_KS, E = L * K, H = FT_H, D0 = seq ? 0 : dims[0];
+    const int64_t K = Kc > 0 ? Kc : L < TM_KS ? L : TM_KS, E = L * K, H = FT_H, D0 = seq ? 0 : dims[0];
     // saved
-    w.offs = i32(2); w.E48 = i32(L * TM_KS); w.eidx = i32(E); w.cls = i32(E); w.rows_id = i32(M); w.status = i32(1);
+    w.offs = i32(n_prot + 1); w.E48 = i32(L * TM_KS); w.eidx = i32(E); w.cls = i32(E); w.rows_id = i32(M); w.status = i32(1);
     w.D48 = f(L * TM_KS); w.Ein = f(E * 416); w.E0 = f(E * H); w.nemu = f(E); w.ners = f(E); w.En = f(E * H);
     for (int l = 0; l < 4; ++l) w.hE[l] = f(E * H);
     w.hV0 = f(L * H); w.hS = f(L * H); w.headX = f(M * D0);
@@ -674,23 +646,7 @@ static int ft_grid_threads(int64_t n) {
     return (int)(b < 1 ? 1 : b < cap ? b : cap);
 }
 
-// One call's context: sizes, pointers, the dropout description.
-struct FtCtx {
-    int L, K, M, nf, lightattn, n_layers, subtract, seq;
-    int64_t E;
-    const int32_t *dims;
-    const float *X, *mask;
-    const int32_t *S, *ridx, *cenc, *pos, *mut, *wt;
-    const float *dlp;                             // the sequence loss: upstream dL / dlog_probs [L,21] (backward)
-    const int32_t *ranks;                         // the sequence loss: decoding ranks [L] (null: every neighbour visible, the ddG path)
-    const float *params;
-    float *grads;
-    FtLayout lay;
-    FtWs w;
-    FtDrop drop;
-    hipStream_t st;
-};
-
+// (One call's context, FtCtx: tmpnn_ft.h)
 static FtSeg ft_seg(const float *p, int ld, int width, int mode, int masked, int rows) { return FtSeg{p, ld, width, mode, masked, rows, 0, nullptr}; }
 static FtA ft_plain(const float *p, int ld, int width, int rows, int act = 0) {
     FtA a{};
@@ -828,16 +784,17 @@ static void ft_node_bwd(const FtCtx &c, const float *dout, int site1, int site2,
     ft_ln_bwd(c, dhV1, nullptr, x1, mu1, rs1, on1w, on1b, dhV1, 0, c.w.dh1, site1, L);
 }
 
-static int ft_forward(const FtCtx &c) {
+int ft_forward(const FtCtx &c) {
     const FtWs &w = c.w;
     const FtLayout &S = c.lay;
     const float *P = c.params;
     const int L = c.L, E = (int)c.E;
     ft_embed_kernel<<<ft_grid_threads((int64_t)L * FT_H), TM_THREADS, 0, c.st>>>(P + S.Ws, c.S, L, w.hS);
     if (c.nf > 0) {
-        ft_offsets_kernel<<<1, TM_THREADS, 0, c.st>>>(w.offs, L);
-        FT_TRY(launch_knn(c.X, c.mask, w.offs, 1, L, L, c.K, w.E48, w.D48, w.status, c.st));
-        FtGraph g{c.X, c.ridx, c.cenc, w.E48, w.D48, P + S.posw, P + S.posb, w.eidx, w.cls, w.Ein, L, c.K};
+        // the segments of the row space: one protein [0, L], or what the packed entry has written into w.offs from its caller's offsets
+        if (!c.seg_offsets) ft_offsets_kernel<<<1, TM_THREADS, 0, c.st>>>(w.offs, L);
+        FT_TRY(launch_knn(c.X, c.mask, w.offs, c.n_prot, L, c.max_len, c.K, w.E48, w.D48, c.status ? c.status : w.status, c.st));
+        FtGraph g{c.X, c.ridx, c.cenc, w.E48, w.D48, P + S.posw, P + S.posb, w.eidx, w.cls, w.Ein, L, c.K, w.offs, c.n_prot};
         ft_graph_kernel<<<ft_grid_threads(E), TM_THREADS, 0, c.st>>>(g);
         ft_linear(c, ft_plain(w.Ein, 416, 416, E), P + S.edgew, nullptr, w.E0, FT_H, E, FT_H);
         FtLnF ln{w.E0, nullptr, 0, P + S.new_, P + S.neb, nullptr, w.ftm, w.En, w.nemu, w.ners, E, c.drop};   // xs = E0 again (temporary)
@@ -878,7 +835,7 @@ static int ft_forward(const FtCtx &c) {
     return TMPNN_OK;
 }
 
-static void ft_backward(const FtCtx &c) {
+void ft_backward(const FtCtx &c) {
     const FtWs &w = c.w;
     const FtLayout &S = c.lay;
     const int L = c.L, E = (int)c.E;
@@ -956,13 +913,13 @@ static void ft_backward(const FtCtx &c) {
     ft_class_sum(c, c.S, w.dhS, FT_H, 0, L, FT_H, TMPNN_VOCAB, c.grads + S.Ws, FT_H, 1);        // d W_s[a] = sum over S_i = a
 }
 
-static int64_t ft_mask_numel(int64_t L) {
-    const int64_t K = L < TM_KS ? L : TM_KS;
-    return (12 * L + 3 * L * K) * FT_H;
-}
+// keep_in / keep_out of L rows at K neighbours: the 15 sites in order, each [rows, 128] (one protein: K = min(48, L), whatever k_neighbors)
+int64_t ft_mask_numel(int64_t L, int64_t K) { return (12 * L + 3 * L * K) * FT_H; }
+static int64_t ft_k48(int64_t L) { return L < TM_KS ? L : TM_KS; }
+static int64_t ft_mask_numel(int64_t L) { return ft_mask_numel(L, ft_k48(L)); }
 
-static void ft_mask_offsets(int64_t L, int64_t *off) {
-    const int64_t K = L < TM_KS ? L : TM_KS, node = L * FT_H, edge = L * K * FT_H;
+static void ft_mask_offsets(int64_t L, int64_t K, int64_t *off) {
+    const int64_t node = L * FT_H, edge = L * K * FT_H;
     int64_t o = 0;
     for (int s = 0; s < FT_SITES; ++s) {
         off[s] = o;
@@ -1009,7 +966,9 @@ static FtCtx ft_ctx(const float *X, const int32_t *S, const float *mask, const i
                     int subtract, const float *params, float *grads, void *ws, hipStream_t st) {
     FtCtx c{};
     c.L = (int)L;
-    c.K = (int)(L < TM_KS ? L : TM_KS);
+    c.K = (int)ft_k48(L);
+    c.n_prot = 1;
+    c.min_len = c.max_len = c.L;
     c.E = (int64_t)c.L * c.K;
     c.M = (int)M;
     c.nf = n_final;
@@ -1027,14 +986,14 @@ static FtCtx ft_ctx(const float *X, const int32_t *S, const float *mask, const i
 }
 
 // ProteinMPNN's dropout of one call: the injected masks (keep_in), the stated generator keyed on (seed, step) when p > 0, else none
-static void ft_set_drop(FtCtx &c, int64_t L, float p_mpnn, const float *keep_in, float *keep_out, uint64_t seed, uint64_t step) {
+void ft_set_drop(FtCtx &c, int64_t L, int64_t K, float p_mpnn, const float *keep_in, float *keep_out, uint64_t seed, uint64_t step) {
     const uint32_t thr = (uint32_t)llround((double)p_mpnn * 16777216.0);
     c.drop.mode = keep_in ? 1 : thr > 0 ? 2 : 0;
     c.drop.keep_in = keep_in;
     c.drop.keep_out = c.drop.mode == 2 ? keep_out : nullptr;
     c.drop.thr = thr;
     c.drop.scale = (float)(1.0 / (1.0 - (double)thr / 16777216.0));
-    ft_mask_offsets(L, c.drop.off);
+    ft_mask_offsets(L, K, c.drop.off);
     {   // k2 of the stated generator, formed on the host in the same 64-bit arithmetic
         auto mix = [](uint64_t x) { x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31; return x; };
         c.drop.k2 = mix(mix(seed ^ 0x9E3779B97F4A7C15ull) + step);
@@ -1057,7 +1016,7 @@ extern "C" int tmpnn_finetune_step(const float *X, const int32_t *S, const float
     FT_TRY(ft_check_ws("finetune_step", L, M, n_final, lightattn, n_layers, dims, workspace, workspace_bytes));
     FtCtx c = ft_ctx(X, S, mask, residue_idx, chain_enc, L, pos, mut, wt, M, n_final, lightattn, n_layers, dims, subtract_mut, params, grads,
                      workspace, (hipStream_t)stream);
-    ft_set_drop(c, L, p_mpnn, keep_in, keep_out, seed, step);
+    ft_set_drop(c, L, ft_k48(L), p_mpnn, keep_in, keep_out, seed, step);
     if (keep_out && c.drop.mode != 2) (void)hipMemsetAsync(keep_out, 0, (size_t)ft_mask_numel(L) * 4, c.st);
     FT_TRY(ft_forward(c));
     const int64_t D0 = dims[0];
@@ -1082,7 +1041,7 @@ extern "C" int tmpnn_finetune_eval(const float *X, const int32_t *S, const float
     FT_TRY(ft_check_ws("finetune_eval", L, M, n_final, lightattn, n_layers, dims, workspace, workspace_bytes));
     FtCtx c = ft_ctx(X, S, mask, residue_idx, chain_enc, L, pos, mut, wt, M, n_final, lightattn, n_layers, dims, subtract_mut, params, nullptr,
                      workspace, (hipStream_t)stream);
-    ft_mask_offsets(L, c.drop.off);
+    ft_mask_offsets(L, ft_k48(L), c.drop.off);
     FT_TRY(ft_forward(c));
     FT_TRY(tmpnn_head_eval(c.w.headX, M, c.w.rows_id, mut, wt, M, n_final, lightattn, n_layers, dims, subtract_mut, params + c.lay.head,
                            slab_numel - c.lay.head, pred, c.w.head_ws, c.w.head_bytes, stream));
@@ -1110,7 +1069,7 @@ static int ft_check_split(const char *what, int n_final, int lightattn, float p_
     return TMPNN_OK;
 }
 
-static int ft_check_buf(const char *what, const char *which, void *buf, size_t bytes, size_t need) {
+int ft_check_buf(const char *what, const char *which, void *buf, size_t bytes, size_t need) {
     if (!buf || bytes < need) return tm_set_error(TMPNN_E_WORKSPACE, "%s: %s buffer %zu < %zu bytes", what, which, bytes, need);
     return TMPNN_OK;
 }
@@ -1131,7 +1090,7 @@ extern "C" int tmpnn_finetune_forward(const float *X, const int32_t *S, const fl
     FtCtx c = ft_ctx(X, S, mask, residue_idx, chain_enc, L, pos, mut, wt, M, n_final, lightattn, n_layers, dims, subtract_mut, params, nullptr,
                      nullptr, (hipStream_t)stream);
     c.w = ft_carve2(saved, nullptr, true, L, M, lightattn, n_layers, dims);
-    ft_set_drop(c, L, p_mpnn, keep_in, keep_out, seed, step);
+    ft_set_drop(c, L, ft_k48(L), p_mpnn, keep_in, keep_out, seed, step);
     if (keep_out && c.drop.mode != 2) (void)hipMemsetAsync(keep_out, 0, (size_t)ft_mask_numel(L) * 4, c.st);
     FT_TRY(ft_forward(c));
     FT_TRY(tm_head_forward(c.w.headX, M, c.w.rows_id, mut, wt, M, lightattn, n_layers, dims, subtract_mut, params + c.lay.head, p_head,
@@ -1159,7 +1118,7 @@ extern "C" int tmpnn_finetune_backward(const float *X, const int32_t *S, const f
                      nullptr, (hipStream_t)stream);
     // the saved part is only read: its one writer is the forward
     c.w = ft_carve2(const_cast<void *>(saved), scratch, true, L, M, lightattn, n_layers, dims);
-    ft_set_drop(c, L, p_mpnn, keep_in, nullptr, seed, step);
+    ft_set_drop(c, L, ft_k48(L), p_mpnn, keep_in, nullptr, seed, step);
     FT_TRY(tm_head_train_core(c.w.headX, M, c.w.rows_id, mut, wt, nullptr, M, lightattn, n_layers, dims, subtract_mut, params + c.lay.head,
                               grads + c.lay.head, p_head, head_keep_in, nullptr, seed, step, nullptr, nullptr, c.w.head_ws_b, c.st,
                               mpnn_grads ? c.w.dheadX : nullptr, dpred));
@@ -1194,6 +1153,8 @@ static FtCtx sq_ctx(const float *X, const int32_t *S, const float *mask, const i
     FtCtx c{};
     c.L = (int)L;
     c.K = (int)(L < k_neighbors ? L : k_neighbors);
+    c.n_prot = 1;
+    c.min_len = c.max_len = c.L;
     c.E = (int64_t)c.L * c.K;
     c.nf = 3;
     c.seq = 1;
@@ -1214,7 +1175,7 @@ extern "C" int tmpnn_seqloss_forward(const float *X, const int32_t *S, const flo
     FT_REQUIRE(log_probs, "seqloss_forward: null pointer");
     FT_REQUIRE(!(keep_in && keep_out), "seqloss_forward: keep_in (injected masks) and keep_out (drawn masks) exclude each other");
     FtCtx c = sq_ctx(X, S, mask, residue_idx, chain_enc, L, k_neighbors, ranks, params, nullptr, saved, nullptr, (hipStream_t)stream);
-    ft_set_drop(c, L, p_mpnn, keep_in, keep_out, seed, step);
+    ft_set_drop(c, L, ft_k48(L), p_mpnn, keep_in, keep_out, seed, step);
     if (keep_out) (void)hipMemsetAsync(keep_out, 0, (size_t)ft_mask_numel(L) * 4, c.st);   // (K < 48 leaves the edge sites' tails unwritten)
     FT_TRY(ft_forward(c));
     (void)hipMemcpyAsync(log_probs, c.w.lp, (size_t)L * TMPNN_VOCAB * 4, hipMemcpyDeviceToDevice, c.st);
@@ -1233,7 +1194,7 @@ extern "C" int tmpnn_seqloss_backward(const float *X, const int32_t *S, const fl
     FtCtx c = sq_ctx(X, S, mask, residue_idx, chain_enc, L, k_neighbors, ranks, params, grads, const_cast<void *>(saved), scratch,
                      (hipStream_t)stream);
     c.dlp = dlog_probs;
-    ft_set_drop(c, L, p_mpnn, keep_in, nullptr, seed, step);
+    ft_set_drop(c, L, ft_k48(L), p_mpnn, keep_in, nullptr, seed, step);
     ft_backward(c);
     return tm_check_launch("seqloss_backward");
 }

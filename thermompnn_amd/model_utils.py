@@ -10,7 +10,8 @@ log p(sequence | structure) under a random decoding order with a graph over the 
 
 The arithmetic runs in csrc/tmpnn_finetune.hip (tmpnn_seqloss_forward / _backward): the exact-fp32 training forward and the
 deterministic backward of the ddG fine-tuning path with the order-masked decoder and the output layer. One
-``torch.autograd.Function`` call per batch member; the Function's inputs are the module's parameters in state-dict order (W_out
+``torch.autograd.Function`` call per batch member, or with ``model.packed = True`` one for the whole batch
+(csrc/tmpnn_seqbatch.hip, tmpnn_seqloss_batch_*: the same kernels over the packed rows); the Function's inputs are the module's parameters in state-dict order (W_out
 included), packed once per weight version into one flat slab. Gradients with respect to coordinates are not provided: the
 ``augment_eps`` noise is added on the host. The dropout masks come from the library's counter-based generator, keyed per forward from
 torch's default CPU generator or pinned with ``thermompnn_amd.autograd.dropout_key``; the decoding order is drawn with
@@ -68,6 +69,14 @@ class SeqPlan:
 
     def scratch(self, L: int, device) -> torch.Tensor:
         need = int(self.lib.tmpnn_seqloss_scratch_bytes(L))
+        if self._scratch is None or self._scratch.numel() < need or self._scratch.device != device:
+            self._scratch = None
+            self._scratch = torch.empty(need, dtype=torch.uint8, device=device)
+        return self._scratch
+
+    def batch_scratch(self, inp, device) -> torch.Tensor:
+        """The same shared buffer, grown to what a packed batch's backward needs."""
+        need = int(self.lib.tmpnn_seqloss_batch_scratch_bytes(inp.T, inp.n, inp.K))
         if self._scratch is None or self._scratch.numel() < need or self._scratch.device != device:
             self._scratch = None
             self._scratch = torch.empty(need, dtype=torch.uint8, device=device)
@@ -137,9 +146,110 @@ def sequence_log_probs(plan: SeqPlan, params, X, S, mask, residue_idx, chain_enc
     return SeqLossFunction.apply(plan, inp, float(p_mpnn), seed, step, *params)
 
 
+class SeqBatchInputs:
+    """A packed batch's device inputs: X [T,4,3] fp32, S / residue_idx / chain_enc / ranks [T] int32, mask [T] fp32, offsets
+    [n + 1] int32 (protein b in the rows offsets[b]:offsets[b+1]), and the bounds the lengths are promised to keep."""
+
+    def __init__(self, X, S, mask, ridx, cenc, ranks, offsets, k_neighbors, min_len=None, max_len=None):
+        f = lambda t: t.detach().to(torch.float32).contiguous()
+        i = lambda t: t.detach().to(torch.int32).contiguous()
+        self.X, self.S, self.mask, self.ridx, self.cenc, self.ranks = f(X), i(S), f(mask), i(ridx), i(cenc), i(ranks)
+        host = [int(v) for v in (offsets.tolist() if torch.is_tensor(offsets) else offsets)]
+        self.n, self.T, self.k_neighbors = len(host) - 1, int(self.S.numel()), int(k_neighbors)
+        if self.n < 1:
+            raise ValueError("offsets must hold n_proteins + 1 entries, n_proteins >= 1")
+        lens = [b - a for a, b in zip(host, host[1:])]
+        self.min_len = int(min(lens) if min_len is None else min_len)
+        self.max_len = int(max(lens) if max_len is None else max_len)
+        if not L_MIN <= self.min_len <= self.max_len <= L_MAX:
+            raise ValueError(f"protein lengths {self.min_len}..{self.max_len} outside [{L_MIN}, {L_MAX}]")
+        self.K = min(self.k_neighbors, self.min_len)
+        self.offsets = torch.tensor(host, dtype=torch.int32, device=self.S.device)
+
+    def args(self):
+        return (_ptr(self.X), _ptr(self.S), _ptr(self.mask), _ptr(self.ridx), _ptr(self.cenc), _ptr(self.offsets), self.n, self.T,
+                self.min_len, self.max_len, self.k_neighbors, _ptr(self.ranks))
+
+
+class SeqBatchFunction(torch.autograd.Function):
+    """log_probs [T,21] of a packed batch under ``inp.ranks``: ONE autograd node, one saved buffer, one gradient slab and one backward
+    for all its proteins (tmpnn_seqloss_batch_forward / _backward). ``status`` [1] int32 receives the device status word."""
+
+    @staticmethod
+    def forward(ctx, plan, inp, status, p_mpnn, seed, step, *params):
+        slab = plan.pack(params)
+        dev = slab.device
+        need = int(plan.lib.tmpnn_seqloss_batch_saved_bytes(inp.T, inp.n, inp.K))
+        if need == 0:
+            raise ValueError(f"packed batch of {inp.T} rows, {inp.n} proteins, K = {inp.K}: outside what tmpnn_seqloss_batch_* takes")
+        saved = torch.empty(need, dtype=torch.uint8, device=dev)
+        log_probs = torch.empty((inp.T, 21), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            check(plan.lib.tmpnn_seqloss_batch_forward(*inp.args(), _ptr(slab), plan.numel, p_mpnn, None, None, seed, step, _ptr(log_probs),
+                                                       None, _ptr(status), _ptr(saved), saved.numel(), _stream()),
+                  "tmpnn_seqloss_batch_forward")
+        ctx.plan, ctx.inp, ctx.cfg = plan, inp, (p_mpnn, seed, step)
+        ctx.save_for_backward(saved, slab)
+        return log_probs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dlp):
+        plan, inp = ctx.plan, ctx.inp
+        p_mpnn, seed, step = ctx.cfg
+        saved, slab = ctx.saved_tensors
+        dev = slab.device
+        dlp = dlp.to(device=dev, dtype=torch.float32).contiguous()
+        grads = torch.zeros(plan.numel, dtype=torch.float32, device=dev)
+        scratch = plan.batch_scratch(inp, dev)
+        with torch.cuda.device(dev):
+            check(plan.lib.tmpnn_seqloss_batch_backward(*inp.args(), _ptr(slab), plan.numel, p_mpnn, None, seed, step, _ptr(dlp), _ptr(grads),
+                                                        _ptr(saved), saved.numel(), _ptr(scratch), scratch.numel(), _stream()),
+                  "tmpnn_seqloss_batch_backward")
+        out, off = [], 0
+        for i, (shape, n) in enumerate(zip(plan.shapes.values(), plan.sizes)):
+            out.append(grads[off:off + n].view(shape) if ctx.needs_input_grad[6 + i] else None)
+            off += n
+        return (None,) * 6 + tuple(out)
+
+
+def sequence_log_probs_batch(plan: SeqPlan, params, X, S, mask, residue_idx, chain_enc, ranks, offsets, k_neighbors: int, p_mpnn: float,
+                             min_len=None, max_len=None):
+    """log_probs [T,21] of a packed batch with a graph over ``params``: one forward and one backward for all its proteins. The six
+    inputs are packed tensors ([T,4,3] and [T]) with ``offsets`` [n + 1], or lists of per-protein tensors, which are packed here
+    (``offsets`` may then be None). One K = min(k_neighbors, shortest protein) serves the batch; proteins shorter than ``k_neighbors``
+    need a batch of one length. ``min_len`` / ``max_len`` default to the lengths ``offsets`` gives. Reads the device status word (a
+    stream sync) and raises through tmpnn_status_error. Dropout rows are numbered over the packed rows, so a protein's masks depend
+    on its place in the batch."""
+    from .autograd import _draw_key
+    if params[0].device.type != "cuda":
+        raise RuntimeError(_CPU_ERROR)
+    dev = params[0].device
+    if isinstance(S, (list, tuple)):
+        lens = [int(s.numel()) for s in S]
+        offsets = [0]
+        for n in lens:
+            offsets.append(offsets[-1] + n)
+        X, S, mask, residue_idx, chain_enc, ranks = (torch.cat([t.to(dev) for t in ts]) for ts in (X, S, mask, residue_idx, chain_enc, ranks))
+    inp = SeqBatchInputs(*(t.to(dev) for t in (X, S, mask, residue_idx, chain_enc, ranks)), offsets, k_neighbors, min_len, max_len)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    seed, step = _draw_key() if p_mpnn > 0 else (0, 0)
+    log_probs = SeqBatchFunction.apply(plan, inp, status, float(p_mpnn), seed, step, *params)
+    st = int(status.item())
+    if st:
+        check(plan.lib.tmpnn_status_error(st), "tmpnn_seqloss_batch_forward")
+    return log_probs
+
+
 class ProteinMPNN(nn.Module):
     """Constructor / forward signature and state-dict names of the reference's training class (model_utils.py:396-470); a checkpoint
     of ``protein_mpnn_utils.ProteinMPNN`` loads into it and the other way round."""
+
+    # Opt-in packed training: with packed = True, forward runs the [B, L] batch as ONE device call over B segments of L rows (padding
+    # rows included, exactly what the loop feeds each member) and one autograd node, and draws one dropout key per forward where the
+    # loop draws B. log_probs are the loop's bit for bit without dropout; gradients agree to rounding (the weight gradients' fixed row
+    # blocks run over the packed rows). A batch of one takes the per-protein call either way.
+    packed = False
 
     def __init__(self, num_letters=21, node_features=128, edge_features=128, hidden_dim=128, num_encoder_layers=3,
                  num_decoder_layers=3, vocab=21, k_neighbors=32, augment_eps=0.1, dropout=0.1):
@@ -170,6 +280,12 @@ class ProteinMPNN(nn.Module):
             randn = torch.randn(chain_M.shape, device=chain_M.device)
         ranks = decoding_ranks(chain_M, randn.to(chain_M.device))
         p = self.dropout if self.training else 0.0
+        B, L = int(S.shape[0]), int(S.shape[1])
+        if self.packed and B > 1:
+            flat = lambda t: t.reshape((B * L,) + tuple(t.shape[2:]))
+            out = sequence_log_probs_batch(self._plan, params, flat(X), flat(S), flat(mask), flat(residue_idx), flat(chain_encoding_all),
+                                           flat(ranks), list(range(0, B * L + 1, L)), self.k_neighbors, p)
+            return out.view(B, L, 21)
         out = [sequence_log_probs(self._plan, params, X[b], S[b], mask[b], residue_idx[b], chain_encoding_all[b], ranks[b],
                                   self.k_neighbors, p) for b in range(X.shape[0])]
         return torch.stack(out)

@@ -144,11 +144,12 @@ class TransferModel(_EngineOwner):
             out = ddg if self.subtract_mut else z * self.ddg_out.weight.view(()) + self.ddg_out.bias.view(())
             return out.view(V, L, VOCAB_DIM)
 
-    def sequence_log_probs(self, pdb, chain_M=None, randn=None) -> torch.Tensor:
+    def sequence_log_probs(self, pdb, chain_M=None, randn=None, packed=False) -> torch.Tensor:
         """log p(sequence | structure) of one parsed structure, [L, 21], under the decoding order
         ``decoding_ranks(chain_M * mask, randn)`` (chain_M None: every residue designable; randn None: drawn), with a graph over
         ``prot_mpnn``'s parameters, W_out included (thermompnn_amd/autograd.py). Needs ``differentiable = True``. Together with
-        the ddG loss it is two backward passes into the same ``.grad``s."""
+        the ddG loss it is two backward passes into the same ``.grad``s. ``packed`` is the switch of
+        ``model_utils.ProteinMPNN.packed``; one structure is a batch of one, which takes the per-protein call either way."""
         from . import autograd as _autograd
         return _autograd.transfer_sequence_log_probs(self, pdb, chain_M, randn)
 
