@@ -293,4 +293,5 @@ def test_range_overflow_raises_or_retries(synthetic_weights):
         warnings.simplefilter("always")
         got = run(eng, enc, c)
     assert any("bf16x3" in str(w.message) for w in rec)
+    assert all(w.category is RuntimeWarning and w.filename == __file__ for w in rec if "bf16x3" in str(w.message))     # attributed to the caller
     assert torch.equal(got["S"], want["S"]) and torch.equal(got["probs"], want["probs"])

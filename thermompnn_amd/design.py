@@ -67,51 +67,25 @@ def pack_tied_args(randn, chain_mask, mask, temperature, omit_AAs_np, bias_AAs_n
     pk["decoding_order"] = order.to(dev)[None].repeat(B, 1)
     pk["close"] = close.to(dev)[None].repeat(B, 1)
     pk["weight"] = (f(tied_beta).reshape(L) / size.to(dev))[None].repeat(B, 1)
-    pk["pssm_mix"] = pk["pssm_bias"] = pk["pssm_keep"] = None
-    if pssm_bias_flag:
-        pk["pssm_mix"] = (float(pssm_multi) * f(pssm_coef)).expand(B, L).contiguous()
-        pk["pssm_bias"] = f(pssm_bias).expand(B, L, 21).contiguous()
-    if pssm_log_odds_flag:
-        pk["pssm_keep"] = f(pssm_log_odds_mask).expand(B, L, 21).contiguous()
+    pk.update(pssm_tables(B, L, dev, pssm_coef, pssm_bias, pssm_multi, pssm_log_odds_flag, pssm_log_odds_mask, pssm_bias_flag))
     return pk
+
+
+def pssm_tables(B, L, dev, pssm_coef, pssm_bias, pssm_multi, pssm_log_odds_flag, pssm_log_odds_mask, pssm_bias_flag):
+    """The PSSM terms of both reference samplers as the sampler's tables -> dict(pssm_mix [B,L] = pssm_multi * pssm_coef and pssm_bias
+    [B,L,21] (with pssm_bias_flag, else None; :1475), pssm_keep [B,L,21] = pssm_log_odds_mask (with pssm_log_odds_flag, else None; :1478))."""
+    f = lambda x: torch.as_tensor(x).to(dtype=torch.float32, device=dev)
+    tabs = {"pssm_mix": None, "pssm_bias": None, "pssm_keep": None}
+    if pssm_bias_flag:
+        tabs["pssm_mix"] = (float(pssm_multi) * f(pssm_coef)).expand(B, L).contiguous()
+        tabs["pssm_bias"] = f(pssm_bias).expand(B, L, 21).contiguous()
+    if pssm_log_odds_flag:
+        tabs["pssm_keep"] = f(pssm_log_odds_mask).expand(B, L, 21).contiguous()
+    return tabs
 
 
 class ProteinMPNNDesign(ProteinMPNN):
     """``ProteinMPNN`` with the reference's ``tied_sample`` and the PSSM flags of ``sample``."""
-
-    def _run_tied(self, what, X, S_true, chain_encoding_all, residue_idx, mask, temperature, pk, generator, uniforms):
-        """The members as chains of ``Engine.sample_tied``: one encode when they share the structure and the per-residue tables;
-        otherwise one padded encode and ``Engine.sample_tied_each``, member b as one chain over protein b's own steps. -> (S [B,L] int64, probs [B,L,21])."""
-        if not float(temperature) > 0.0:
-            raise ValueError(f"{what}: temperature must be positive, got {temperature!r}")
-        eng = self.engine()
-        dev = eng.device
-        B, L = X.shape[0], X.shape[1]
-        S_true = S_true.to(dev)
-        if S_true.numel() and (int(S_true.min()) < 0 or int(S_true.max()) >= 21):
-            raise ValueError(f"{what}: S_true must lie in [0, 21)")
-        tables = ("bias", "allowed", "pssm_mix", "pssm_bias", "pssm_keep")
-        with torch.cuda.device(dev):
-            if uniforms is None:
-                uniforms = torch.rand((B, L), device=dev, dtype=torch.float32, generator=generator)
-            u = torch.as_tensor(uniforms).to(device=dev, dtype=torch.float32).reshape(B, L)
-            same = lambda t: t is None or bool((t[1:] == t[:1]).all())
-            shared = B > 1 and all(same(t) for t in (X.to(dev), mask.to(dev), residue_idx.to(dev), chain_encoding_all.to(dev),
-                                                     *(pk[k] for k in tables)))
-            if shared or B == 1:
-                enc = self._encode_padded(eng, X[:1], mask[:1], residue_idx[:1], chain_encoding_all[:1])
-                r = eng.sample_tied(enc, pk["decoding_order"], pk["close"], S_true, pk["free"], u, temperature=float(temperature),
-                                    weight=pk["weight"], **{k: None if pk[k] is None else pk[k][0] for k in tables})
-                return r["S"].to(torch.int64), r["probs"]
-            # ONE padded encode and ONE launch: member b is protein b of the packed axis, one chain over its own steps
-            enc = self._encode_padded(eng, X, mask, residue_idx, chain_encoding_all)
-            flat = lambda t: None if t is None else t.reshape(B * L, *t.shape[2:])
-            order = pk["decoding_order"]
-            shift = (torch.arange(B, device=dev, dtype=order.dtype) * L)[:, None]
-            row = lambda t: None if t is None else flat(t)[None]
-            r = eng.sample_tied_each(enc, row(order + shift), row(pk["close"]), row(S_true), row(pk["free"]), row(u),
-                                     temperature=float(temperature), weight=row(pk["weight"]), **{k: flat(pk[k]) for k in tables})
-        return r["S"].view(B, L).to(torch.int64), r["probs"].view(B, L, 21)
 
     def tied_sample(self, X, randn, S_true, chain_mask, chain_encoding_all, residue_idx, mask=None, temperature=1.0,
                     omit_AAs_np=None, bias_AAs_np=None, chain_M_pos=None, omit_AA_mask=None, pssm_coef=None,
@@ -123,19 +97,11 @@ class ProteinMPNNDesign(ProteinMPNN):
         chain_M_pos, S_true at a fixed position) are the ones of a group's LAST listed member, and probs is written to every
         member of a group, fixed ones included — both as the reference does. One uniform per (member, closing residue) from
         ``torch.rand(..., generator=generator)`` or ``uniforms`` [B,L] picks the letter by inverse CDF, as ``sample``."""
-        if mask is None:
-            raise ValueError("tied_sample: mask is required")
-        dev = self.engine().device
-        B, L = X.shape[0], X.shape[1]
-        if chain_M_pos is None:
-            chain_M_pos = torch.ones_like(chain_mask)
-        zeros21 = torch.zeros(21)
-        pk = pack_tied_args(randn.to(dev), chain_mask.to(dev), mask.to(dev), temperature,
-                            zeros21 if omit_AAs_np is None else omit_AAs_np, zeros21 if bias_AAs_np is None else bias_AAs_np,
-                            chain_M_pos.to(dev), omit_AA_mask, bias_by_res, [] if tied_pos is None else tied_pos,
-                            torch.ones(L) if tied_beta is None else tied_beta, pssm_coef, pssm_bias, pssm_multi, pssm_log_odds_flag,
-                            pssm_log_odds_mask, pssm_bias_flag)
-        S, probs = self._run_tied("tied_sample", X, S_true, chain_encoding_all, residue_idx, mask, temperature, pk, generator, uniforms)
+        pk = self._packed("tied_sample", pack_tied_args, randn, chain_mask, mask, temperature, omit_AAs_np, bias_AAs_np, chain_M_pos,
+                          omit_AA_mask, bias_by_res, [] if tied_pos is None else tied_pos,
+                          torch.ones(X.shape[1]) if tied_beta is None else tied_beta, pssm_coef, pssm_bias, pssm_multi, pssm_log_odds_flag,
+                          pssm_log_odds_mask, pssm_bias_flag)
+        S, probs = self._sample_members("tied_sample", X, S_true, chain_encoding_all, residue_idx, mask, temperature, pk, generator, uniforms)
         return {"S": S, "probs": probs, "decoding_order": pk["decoding_order"]}
 
     def sample(self, X, randn, S_true, chain_mask, chain_encoding_all, residue_idx, mask=None, temperature=1.0,
@@ -149,25 +115,13 @@ class ProteinMPNNDesign(ProteinMPNN):
             return super().sample(X, randn, S_true, chain_mask, chain_encoding_all, residue_idx, mask=mask, temperature=temperature,
                                   omit_AAs_np=omit_AAs_np, bias_AAs_np=bias_AAs_np, chain_M_pos=chain_M_pos, omit_AA_mask=omit_AA_mask,
                                   bias_by_res=bias_by_res, generator=generator, uniforms=uniforms)
-        if mask is None:
-            raise ValueError("sample: mask is required")
-        dev = self.engine().device
-        B, L = X.shape[0], X.shape[1]
-        if chain_M_pos is None:
-            chain_M_pos = torch.ones_like(chain_mask)
-        zeros21 = torch.zeros(21)
-        pk = pack_sample_args(randn.to(dev), chain_mask.to(dev), mask.to(dev), temperature,
-                              zeros21 if omit_AAs_np is None else omit_AAs_np, zeros21 if bias_AAs_np is None else bias_AAs_np,
-                              chain_M_pos.to(dev), omit_AA_mask, bias_by_res)
-        f = lambda x: torch.as_tensor(x).to(dtype=torch.float32, device=dev)
-        pk["close"] = torch.ones((B, L), dtype=torch.int32, device=dev)
-        pk["weight"] = pk["pssm_mix"] = pk["pssm_bias"] = pk["pssm_keep"] = None
-        if pssm_bias_flag:
-            pk["pssm_mix"] = (float(pssm_multi) * f(pssm_coef)).expand(B, L).contiguous()
-            pk["pssm_bias"] = f(pssm_bias).expand(B, L, 21).contiguous()
-        if pssm_log_odds_flag:
-            pk["pssm_keep"] = f(pssm_log_odds_mask).expand(B, L, 21).contiguous()
-        S, probs = self._run_tied("sample", X, S_true, chain_encoding_all, residue_idx, mask, temperature, pk, generator, uniforms)
+        pk = self._packed("sample", pack_sample_args, randn, chain_mask, mask, temperature, omit_AAs_np, bias_AAs_np, chain_M_pos,
+                          omit_AA_mask, bias_by_res)
+        dev = pk["free"].device
+        B, L = pk["free"].shape
+        pk["close"], pk["weight"] = torch.ones((B, L), dtype=torch.int32, device=dev), None
+        pk.update(pssm_tables(B, L, dev, pssm_coef, pssm_bias, pssm_multi, pssm_log_odds_flag, pssm_log_odds_mask, pssm_bias_flag))
+        S, probs = self._sample_members("sample", X, S_true, chain_encoding_all, residue_idx, mask, temperature, pk, generator, uniforms)
         probs = probs * (pk["free"] * mask.to(dev))[:, :, None]
         return {"S": S, "probs": probs, "decoding_order": pk["decoding_order"]}
 

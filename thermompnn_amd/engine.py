@@ -476,7 +476,7 @@ class Engine:
         self._chunks(what, enc, [(i0, min(n, i0 + per)) for i0 in range(0, n, per)], need, launch, check_status, stacklevel + 1)
 
     def _chunks(self, what: str, enc: "EncodedBackbone", chunks, need: int, launch, check_status: bool, stacklevel: int):
-        """``launch(e, w, ws, *chunk)`` for every chunk (the body of ``_chunked``; ``sample_each`` plans its own chunks)."""
+        """``launch(e, w, ws, *chunk)`` for every chunk (the body of ``_chunked``; the sample entries plan their own chunks)."""
         def run(precision: str) -> int:
             e = enc
             if precision != enc.precision:
@@ -502,48 +502,8 @@ class Engine:
         N is sampled in chunks of at most ``max_rows`` rows (N * T; default 2**18) — a chain's result does not depend on the chunking.
         Range contract as ``decode_variants``: a non-finite result of an f16x2 context re-encodes the backbone and reruns the whole
         call at ``retry_precision`` with a warning, or raises TmpnnRangeError."""
-        T, dev = enc.T, self.device
-        O, S0 = self._i32(order), self._i32(S_fixed)
-        Fr, U = self._f32(free), self._f32(u)
-        for name, t in (("order", O), ("S_fixed", S0), ("free", Fr), ("u", U)):
-            if t.dim() != 2 or t.shape[1] != T or t.shape[0] != O.shape[0]:
-                raise TmpnnError(f"sample: {name} must be [N, {T}] like order, got {tuple(t.shape)}")
-        if not float(temperature) > 0.0 or not np.isfinite(float(temperature)):
-            raise TmpnnError(f"sample: temperature must be positive and finite, got {temperature!r}")
-        B = A = None
-        if bias is not None:
-            B = self._f32(bias)
-            if tuple(B.shape) != (T, VOCAB):
-                raise TmpnnError(f"sample: bias must be [{T}, {VOCAB}], got {tuple(B.shape)}")
-        if allowed is not None:
-            A = self._f32(allowed)
-            if tuple(A.shape) != (T, VOCAB):
-                raise TmpnnError(f"sample: allowed must be [{T}, {VOCAB}], got {tuple(A.shape)}")
-        N = O.shape[0]
-        res = {"S": torch.empty((N, T), dtype=torch.int32, device=dev), "probs": torch.empty((N, T, VOCAB), dtype=torch.float32, device=dev)}
-        if N == 0 or T == 0:
-            return res
-        _need_cuda(enc.ctx)
-        # every row of `order` a permutation (one device sort), every letter in range: ONE read-back of both verdicts
-        steps = torch.arange(T, dtype=torch.int32, device=dev)
-        ok = torch.stack([(torch.sort(O, dim=1).values == steps).all(), ((S0 >= 0) & (S0 < VOCAB)).all()]).tolist()
-        if not ok[0]:
-            raise TmpnnError(f"sample: every row of order must be a permutation of 0..{T - 1}")
-        if not ok[1]:
-            raise TmpnnError(f"sample: residue indices must lie in [0, {VOCAB})")
-        per = self._per_chunk(max_rows, T)
-        need = self.lib.tmpnn_sample_workspace_bytes(T, min(per, N))
-        if need == 0:
-            raise TmpnnError(f"sample: {min(per, N)} chains of {T} residues exceed one launch's table; lower max_rows")
-
-        def launch(e: "EncodedBackbone", w: Weights, ws: torch.Tensor, n0: int, n1: int):
-            check(self.lib.tmpnn_sample(w.handle, _ptr(e.ctx), e.ctx.numel(), _ptr(e.mask), T, n1 - n0, _ptr(O[n0:n1]), _ptr(S0[n0:n1]),
-                                        _ptr(Fr[n0:n1]), _ptr(U[n0:n1]), 1.0 / float(temperature), _ptr(B), _ptr(A),
-                                        _ptr(res["S"][n0:n1]), _ptr(res["probs"][n0:n1]), _ptr(self._status), _ptr(ws), ws.numel(),
-                                        _stream()), "tmpnn_sample")
-
-        self._chunked("sample", enc, N, per, need, launch, check_status, stacklevel=2)
-        return res
+        return self._sample_front("sample", enc, order, None, S_fixed, free, u, temperature, None, bias, allowed, None, None, None,
+                                  max_rows, check_status)
 
     def sample_tied(self, enc: "EncodedBackbone", order, close, S_fixed, free, u, temperature: float = 1.0, weight=None, bias=None,
                     allowed=None, pssm_mix=None, pssm_bias=None, pssm_keep=None, max_rows: Optional[int] = None,
@@ -557,55 +517,8 @@ class Engine:
         with ``pssm_bias`` [T,21]: probs = (1 - mix) probs + mix pssm_bias; ``pssm_keep`` [T,21]: probs = (probs keep + 0.001 probs),
         renormalised; then ``allowed``. -> dict(S int32 [N,T], probs [N,T,21]); probs is written to every member of a live group,
         fixed ones included. Chunking and the range contract as ``sample``."""
-        T, dev = enc.T, self.device
-        O, Cl, S0 = self._i32(order), self._i32(close), self._i32(S_fixed)
-        Fr, U = self._f32(free), self._f32(u)
-        Wt = None if weight is None else self._f32(weight)
-        for name, t in (("order", O), ("close", Cl), ("S_fixed", S0), ("free", Fr), ("u", U), ("weight", Wt)):
-            if t is not None and (t.dim() != 2 or t.shape[1] != T or t.shape[0] != O.shape[0]):
-                raise TmpnnError(f"sample_tied: {name} must be [N, {T}] like order, got {tuple(t.shape)}")
-        if not float(temperature) > 0.0 or not np.isfinite(float(temperature)):
-            raise TmpnnError(f"sample_tied: temperature must be positive and finite, got {temperature!r}")
-        if (pssm_mix is None) != (pssm_bias is None):
-            raise TmpnnError("sample_tied: pssm_bias goes with pssm_mix (give both or neither)")
-        tabs = {}
-        for name, t, shape in (("bias", bias, (T, VOCAB)), ("allowed", allowed, (T, VOCAB)), ("pssm_mix", pssm_mix, (T,)),
-                               ("pssm_bias", pssm_bias, (T, VOCAB)), ("pssm_keep", pssm_keep, (T, VOCAB))):
-            tabs[name] = None if t is None else self._f32(t)
-            if t is not None and tuple(tabs[name].shape) != shape:
-                raise TmpnnError(f"sample_tied: {name} must be {list(shape)}, got {tuple(tabs[name].shape)}")
-        N = O.shape[0]
-        res = {"S": torch.empty((N, T), dtype=torch.int32, device=dev), "probs": torch.empty((N, T, VOCAB), dtype=torch.float32, device=dev)}
-        if N == 0 or T == 0:
-            return res
-        _need_cuda(enc.ctx)
-        # a permutation per row (one device sort), letters in range, close 0 / 1 and ending every row: ONE read-back of the verdicts
-        steps = torch.arange(T, dtype=torch.int32, device=dev)
-        ok = torch.stack([(torch.sort(O, dim=1).values == steps).all(), ((S0 >= 0) & (S0 < VOCAB)).all(),
-                          ((Cl == 0) | (Cl == 1)).all(), (Cl[:, -1] == 1).all()]).tolist()
-        if not ok[0]:
-            raise TmpnnError(f"sample_tied: every row of order must be a permutation of 0..{T - 1}")
-        if not ok[1]:
-            raise TmpnnError(f"sample_tied: residue indices must lie in [0, {VOCAB})")
-        if not ok[2]:
-            raise TmpnnError("sample_tied: close must hold 0 or 1")
-        if not ok[3]:
-            raise TmpnnError("sample_tied: close[:, -1] must be 1 (the last step ends its group)")
-        per = self._per_chunk(max_rows, T)
-        need = self.lib.tmpnn_sample_tied_workspace_bytes(T, min(per, N))
-        if need == 0:
-            raise TmpnnError(f"sample_tied: {min(per, N)} chains of {T} residues exceed one launch's table; lower max_rows")
-
-        def launch(e: "EncodedBackbone", w: Weights, ws: torch.Tensor, n0: int, n1: int):
-            check(self.lib.tmpnn_sample_tied(w.handle, _ptr(e.ctx), e.ctx.numel(), _ptr(e.mask), T, n1 - n0, _ptr(O[n0:n1]), _ptr(Cl[n0:n1]),
-                                             _ptr(S0[n0:n1]), _ptr(Fr[n0:n1]), _ptr(U[n0:n1]), 1.0 / float(temperature),
-                                             _ptr(None if Wt is None else Wt[n0:n1]), _ptr(tabs["bias"]), _ptr(tabs["allowed"]),
-                                             _ptr(tabs["pssm_mix"]), _ptr(tabs["pssm_bias"]), _ptr(tabs["pssm_keep"]),
-                                             _ptr(res["S"][n0:n1]), _ptr(res["probs"][n0:n1]), _ptr(self._status), _ptr(ws), ws.numel(),
-                                             _stream()), "tmpnn_sample_tied")
-
-        self._chunked("sample_tied", enc, N, per, need, launch, check_status, stacklevel=2)
-        return res
+        return self._sample_front("sample_tied", enc, order, close, S_fixed, free, u, temperature, weight, bias, allowed, pssm_mix,
+                                  pssm_bias, pssm_keep, max_rows, check_status)
 
     # -- the samplers for every protein of a packed batch over its own steps -------------------------------------------
     def sample_each(self, enc: "EncodedBackbone", order, S_fixed, free, u, temperature: float = 1.0, bias=None, allowed=None,
@@ -618,8 +531,8 @@ class Engine:
         ``sample`` gives for that protein encoded alone with the segment's order shifted to local indices. A chunk is a protein
         range times a chain range of at most ``max_rows`` rows (chains * residues of the range; default 2**18; one protein and
         one chain at least), long proteins launched first; results do not depend on the chunking. Range contract as ``sample``."""
-        return self._sample_each("sample_each", None, enc, order, S_fixed, free, u, temperature, None, bias, allowed, None, None, None,
-                                 max_rows, check_status)
+        return self._sample_front("sample_each", enc, order, None, S_fixed, free, u, temperature, None, bias, allowed, None, None, None,
+                                  max_rows, check_status)
 
     def sample_tied_each(self, enc: "EncodedBackbone", order, close, S_fixed, free, u, temperature: float = 1.0, weight=None, bias=None,
                          allowed=None, pssm_mix=None, pssm_bias=None, pssm_keep=None, max_rows: Optional[int] = None,
@@ -627,85 +540,57 @@ class Engine:
         """``sample_tied`` for every protein of a packed batch over its own steps (tmpnn_sample_tied_each): arguments as
         ``sample_tied``, schedule, chunking and bits as ``sample_each``. Groups live inside one protein: every protein's last step
         must close (close[n, offsets[b + 1] - 1] == 1)."""
-        return self._sample_each("sample_tied_each", close, enc, order, S_fixed, free, u, temperature, weight, bias, allowed, pssm_mix,
-                                 pssm_bias, pssm_keep, max_rows, check_status)
+        return self._sample_front("sample_tied_each", enc, order, close, S_fixed, free, u, temperature, weight, bias, allowed, pssm_mix,
+                                  pssm_bias, pssm_keep, max_rows, check_status)
 
-    def _sample_each(self, what: str, close, enc: "EncodedBackbone", order, S_fixed, free, u, temperature, weight, bias, allowed,
-                     pssm_mix, pssm_bias, pssm_keep, max_rows: Optional[int], check_status: bool):
-        """The body of sample_each (close is None) and sample_tied_each."""
-        tied = close is not None
-        T, dev = enc.T, self.device
-        O, S0 = self._i32(order), self._i32(S_fixed)
-        Cl = self._i32(close) if tied else None
-        Fr, U = self._f32(free), self._f32(u)
-        Wt = None if weight is None else self._f32(weight)
-        for name, t in (("order", O), ("close", Cl), ("S_fixed", S0), ("free", Fr), ("u", U), ("weight", Wt)):
-            if t is not None and (t.dim() != 2 or t.shape[1] != T or t.shape[0] != O.shape[0]):
-                raise TmpnnError(f"{what}: {name} must be [N, {T}] like order, got {tuple(t.shape)}")
-        if not float(temperature) > 0.0 or not np.isfinite(float(temperature)):
-            raise TmpnnError(f"{what}: temperature must be positive and finite, got {temperature!r}")
-        if (pssm_mix is None) != (pssm_bias is None):
-            raise TmpnnError(f"{what}: pssm_bias goes with pssm_mix (give both or neither)")
-        tabs = {}
-        for name, t, shape in (("bias", bias, (T, VOCAB)), ("allowed", allowed, (T, VOCAB)), ("pssm_mix", pssm_mix, (T,)),
-                               ("pssm_bias", pssm_bias, (T, VOCAB)), ("pssm_keep", pssm_keep, (T, VOCAB))):
-            tabs[name] = None if t is None else self._f32(t)
-            if t is not None and tuple(tabs[name].shape) != shape:
-                raise TmpnnError(f"{what}: {name} must be {list(shape)}, got {tuple(tabs[name].shape)}")
-        N, P = O.shape[0], enc.offsets.numel() - 1
-        res = {"S": torch.empty((N, T), dtype=torch.int32, device=dev), "probs": torch.empty((N, T, VOCAB), dtype=torch.float32, device=dev)}
-        if N == 0 or T == 0 or P <= 0:
+    def _sample_front(self, what: str, enc: "EncodedBackbone", order, close, S_fixed, free, u, temperature, weight, bias, allowed,
+                      pssm_mix, pssm_bias, pssm_keep, max_rows: Optional[int], check_status: bool):
+        """The body of the four sample entries (``what`` names one): ``sample_args`` and ``sample_verdicts`` refuse before any launch,
+        then the chunk plan, the workspace and one launch per chunk of the entry's own C function."""
+        tied, each = "tied" in what, what.endswith("_each")
+        T, P = enc.T, enc.offsets.numel() - 1
+        rows, tabs, res = sample_args(what, T, self.device, order, close, S_fixed, free, u, temperature, weight, bias, allowed, pssm_mix,
+                                      pssm_bias, pssm_keep)
+        N = rows["order"].shape[0]
+        if N == 0 or T == 0 or (each and P <= 0):
             return res
         _need_cuda(enc.ctx)
         # one device pass, ONE read-back: the verdicts and the offsets the chunk plan needs on the host
-        verdicts = each_verdicts(O, S0, Cl, enc.offsets)
-        back = torch.cat([verdicts.to(torch.int64), enc.offsets.to(torch.int64)]).tolist()
-        ok, offs = back[: verdicts.numel()], back[verdicts.numel():]
-        if offs[0] != 0 or offs[-1] != T or any(b < a for a, b in zip(offs, offs[1:])):
-            raise TmpnnError(f"{what}: offsets must rise from 0 to T = {T}")
-        if not ok[0]:
-            raise TmpnnError(f"{what}: every row of order must be a permutation of 0..{T - 1}")
-        if not ok[1]:
-            raise TmpnnError(f"{what}: every entry of order must stay inside the protein of its position (order[n, t0:t1] is a "
-                             f"permutation of t0..t1-1)")
-        if not ok[2]:
-            raise TmpnnError(f"{what}: residue indices must lie in [0, {VOCAB})")
-        if tied and not ok[3]:
-            raise TmpnnError(f"{what}: close must hold 0 or 1")
-        if tied and not ok[4]:
-            raise TmpnnError(f"{what}: every protein's last step must close (close[n, offsets[b + 1] - 1] == 1): a group lives inside "
-                             f"one protein")
-        chunks = plan_each_chunks(offs, N, max_rows)
-        sizer = self.lib.tmpnn_sample_tied_each_workspace_bytes if tied else self.lib.tmpnn_sample_each_workspace_bytes
+        offs = sample_verdicts(what, rows["order"], rows["S_fixed"], rows["close"], enc.offsets if each else None)
+        chunks = plan_each_chunks(offs, N, max_rows) if each else plan_axis_chunks(T, N, max_rows)
+        entry, sizer = {"sample": (self.lib.tmpnn_sample, self.lib.tmpnn_sample_workspace_bytes),
+                        "sample_tied": (self.lib.tmpnn_sample_tied, self.lib.tmpnn_sample_tied_workspace_bytes),
+                        "sample_each": (self.lib.tmpnn_sample_each, self.lib.tmpnn_sample_each_workspace_bytes),
+                        "sample_tied_each": (self.lib.tmpnn_sample_tied_each, self.lib.tmpnn_sample_tied_each_workspace_bytes)}[what]
         need = 0
         for p0, p1, n0, n1 in chunks:
             b = sizer(offs[p1] - offs[p0], n1 - n0)
             if b == 0:
                 raise TmpnnError(f"{what}: {n1 - n0} chain(s) of the {offs[p1] - offs[p0]} residues of proteins [{p0}, {p1}) exceed one "
-                                 f"launch's table")
+                                 f"launch's table" if each else
+                                 f"{what}: {n1 - n0} chains of {T} residues exceed one launch's table; lower max_rows")
             need = max(need, b)
-        # the launch order of every chunk's proteins, longest first: one upload
-        sched = torch.as_tensor(np.concatenate([each_schedule(offs, p0, p1) for p0, p1, _, _ in chunks]), dtype=torch.int32).to(dev)
-        at, pos = {}, 0
-        for p0, p1, n0, n1 in chunks:
-            at[(p0, p1, n0, n1)] = pos
-            pos += p1 - p0
+        at = {}
+        if each:    # the launch order of every chunk's proteins, longest first: one upload
+            sched = torch.as_tensor(np.concatenate([each_schedule(offs, p0, p1) for p0, p1, _, _ in chunks]), dtype=torch.int32).to(self.device)
+            pos = 0
+            for p0, p1, n0, n1 in chunks:
+                at[(p0, p1, n0, n1)] = pos
+                pos += p1 - p0
 
         def launch(e: "EncodedBackbone", w: Weights, ws: torch.Tensor, p0: int, p1: int, n0: int, n1: int):
-            k = at[(p0, p1, n0, n1)]
-            head = (w.handle, _ptr(e.ctx), e.ctx.numel(), _ptr(e.mask), T, _ptr(e.offsets), P, p0, p1, offs[p0], offs[p1] - offs[p0],
-                    _ptr(sched[k:k + p1 - p0]), n1 - n0, _ptr(O[n0:n1]))
-            tail = (_ptr(res["S"][n0:n1]), _ptr(res["probs"][n0:n1]), _ptr(self._status), _ptr(ws), ws.numel(), _stream())
-            if tied:
-                check(self.lib.tmpnn_sample_tied_each(*head, _ptr(Cl[n0:n1]), _ptr(S0[n0:n1]), _ptr(Fr[n0:n1]), _ptr(U[n0:n1]),
-                                                      1.0 / float(temperature), _ptr(None if Wt is None else Wt[n0:n1]), _ptr(tabs["bias"]),
-                                                      _ptr(tabs["allowed"]), _ptr(tabs["pssm_mix"]), _ptr(tabs["pssm_bias"]),
-                                                      _ptr(tabs["pssm_keep"]), *tail), "tmpnn_sample_tied_each")
-            else:
-                check(self.lib.tmpnn_sample_each(*head, _ptr(S0[n0:n1]), _ptr(Fr[n0:n1]), _ptr(U[n0:n1]), 1.0 / float(temperature),
-                                                 _ptr(tabs["bias"]), _ptr(tabs["allowed"]), *tail), "tmpnn_sample_each")
+            part = {k: _ptr(None if t is None else t[n0:n1]) for k, t in rows.items()}
+            args = [w.handle, _ptr(e.ctx), e.ctx.numel(), _ptr(e.mask), T]
+            if each:
+                s = at[(p0, p1, n0, n1)]
+                args += [_ptr(e.offsets), P, p0, p1, offs[p0], offs[p1] - offs[p0], _ptr(sched[s:s + p1 - p0])]
+            args += [n1 - n0, part["order"]] + ([part["close"]] if tied else [])
+            args += [part["S_fixed"], part["free"], part["u"], 1.0 / float(temperature)] + ([part["weight"]] if tied else [])
+            args += [_ptr(tabs[k]) for k in (SAMPLE_TABLES if tied else SAMPLE_TABLES[:2])]
+            check(entry(*args, _ptr(res["S"][n0:n1]), _ptr(res["probs"][n0:n1]), _ptr(self._status), _ptr(ws), ws.numel(), _stream()),
+                  f"tmpnn_{what}")
 
-        self._chunks(what, enc, chunks, need, launch, check_status, stacklevel=3)
+        self._chunks(what, enc, chunks, need, launch, check_status, stacklevel=3)       # a retry warning names the public entry's caller
         return res
 
     def capture_graph(self, X, S, mask, residue_idx, chain_enc, offsets, max_len: int, out: Optional[dict] = None, **want):
@@ -754,26 +639,92 @@ class Engine:
 
 
 # module-level gathers with the reference's signatures (protein_mpnn_utils.py:763-791)
-# -- host side of sample_each: the checks, the chunk plan and the launch order (plain torch / numpy: they run without a GPU) -------
+# -- host side of the four sample entries: the checks, the chunk plans and the launch order (plain torch / numpy: they run without a GPU) --
 EACH_ROWS_MAX = ((1 << 24) - 1) // 3          # chains * rows of one launch (3 * N * rows < 2**24, the chain kernel's row arithmetic)
+SAMPLE_TABLES = ("bias", "allowed", "pssm_mix", "pssm_bias", "pssm_keep")     # per residue: [T,21], pssm_mix [T]
 
 
-def each_verdicts(order: torch.Tensor, S_fixed: torch.Tensor, close: Optional[torch.Tensor], offsets: torch.Tensor) -> torch.Tensor:
-    """The checks of sample_each / sample_tied_each in one pass on the arrays' device -> bool [3] (or [5] with ``close``): every row
-    of ``order`` [N,T] a permutation of 0..T-1; every entry inside the protein of its position (seg[order] == seg[position] — with
-    the first, order[n, t0:t1] is a permutation of t0..t1-1); letters in [0, 21); close 0 / 1; every non-empty protein's last step
-    closing (so no group spans two proteins)."""
+def sample_args(what: str, T: int, dev, order, close, S_fixed, free, u, temperature, weight, bias, allowed, pssm_mix, pssm_bias, pssm_keep):
+    """The arguments of the sample entry ``what`` on ``dev``, refused with the entry's name where their shapes or values cannot be
+    launched -> (rows, tabs, res): the per-chain arrays [N,T] (order / close / S_fixed int32, free / u / weight float32; close only for
+    the tied entries, weight may be None), the per-residue tables (SAMPLE_TABLES, float32 or None) and the allocated dict(S, probs)."""
+    i32 = lambda t: torch.as_tensor(t).to(device=dev, dtype=torch.int32).contiguous()
+    f32 = lambda t: torch.as_tensor(t).to(device=dev, dtype=torch.float32).contiguous()
+    rows = {"order": i32(order), "close": i32(close) if "tied" in what else None, "S_fixed": i32(S_fixed), "free": f32(free), "u": f32(u),
+            "weight": None if weight is None else f32(weight)}
+    N = rows["order"].shape[0]
+    for name, t in rows.items():
+        if t is not None and (t.dim() != 2 or t.shape[1] != T or t.shape[0] != N):
+            raise TmpnnError(f"{what}: {name} must be [N, {T}] like order, got {tuple(t.shape)}")
+    if not float(temperature) > 0.0 or not np.isfinite(float(temperature)):
+        raise TmpnnError(f"{what}: temperature must be positive and finite, got {temperature!r}")
+    if (pssm_mix is None) != (pssm_bias is None):
+        raise TmpnnError(f"{what}: pssm_bias goes with pssm_mix (give both or neither)")
+    tabs = {}
+    for name, t in zip(SAMPLE_TABLES, (bias, allowed, pssm_mix, pssm_bias, pssm_keep)):
+        shape = (T,) if name == "pssm_mix" else (T, VOCAB)
+        tabs[name] = None if t is None else f32(t)
+        if t is not None and tuple(tabs[name].shape) != shape:
+            raise TmpnnError(f"{what}: {name} must be {list(shape)}, got {tuple(tabs[name].shape)}")
+    res = {"S": torch.empty((N, T), dtype=torch.int32, device=dev), "probs": torch.empty((N, T, VOCAB), dtype=torch.float32, device=dev)}
+    return rows, tabs, res
+
+
+def sample_verdicts(what: str, order: torch.Tensor, S_fixed: torch.Tensor, close: Optional[torch.Tensor],
+                    offsets: Optional[torch.Tensor]) -> List[int]:
+    """``each_verdicts`` for the sample entry ``what``, read back ONCE together with the offsets and refused with the entry's name ->
+    the offsets on the host. ``offsets`` None: the whole axis is one segment [0, T) (sample / sample_tied, whatever the context packs)."""
+    T = order.shape[1]
+    verdicts = each_verdicts(order, S_fixed, close, offsets)
+    if offsets is None:
+        ok, offs = verdicts.tolist(), [0, T]
+    else:
+        back = torch.cat([verdicts.to(torch.int64), offsets.to(device=verdicts.device, dtype=torch.int64)]).tolist()
+        ok, offs = back[: verdicts.numel()], back[verdicts.numel():]
+    if offs[0] != 0 or offs[-1] != T or any(b < a for a, b in zip(offs, offs[1:])):
+        raise TmpnnError(f"{what}: offsets must rise from 0 to T = {T}")
+    if not ok[0]:
+        raise TmpnnError(f"{what}: every row of order must be a permutation of 0..{T - 1}")
+    if not ok[1]:
+        raise TmpnnError(f"{what}: every entry of order must stay inside the protein of its position (order[n, t0:t1] is a "
+                         f"permutation of t0..t1-1)")
+    if not ok[2]:
+        raise TmpnnError(f"{what}: residue indices must lie in [0, {VOCAB})")
+    if close is not None and not ok[3]:
+        raise TmpnnError(f"{what}: close must hold 0 or 1")
+    if close is not None and not ok[4]:
+        raise TmpnnError(f"{what}: every protein's last step must close (close[n, offsets[b + 1] - 1] == 1): a group lives inside "
+                         f"one protein" if what.endswith("_each") else
+                         f"{what}: close[:, -1] must be 1 (the last step ends its group)")
+    return offs
+
+
+def plan_axis_chunks(T: int, N: int, max_rows: Optional[int] = None) -> List[tuple]:
+    """The chunks of sample / sample_tied in ``plan_each_chunks``'s form: the one segment (0, 1) times chain ranges of at most
+    ``max_rows`` rows (default 2**18), one chain at least, rising over [0, N)."""
+    per = Engine._per_chunk(max_rows, T)
+    return [(0, 1, n0, min(N, n0 + per)) for n0 in range(0, N, per)]
+
+
+def each_verdicts(order: torch.Tensor, S_fixed: torch.Tensor, close: Optional[torch.Tensor], offsets: Optional[torch.Tensor]) -> torch.Tensor:
+    """The checks of the sample entries in one pass on the arrays' device -> bool [3] (or [5] with ``close``): every row of ``order``
+    [N,T] a permutation of 0..T-1; every entry inside the protein of its position (seg[order] == seg[position] — with the first,
+    order[n, t0:t1] is a permutation of t0..t1-1); letters in [0, 21); close 0 / 1; every non-empty protein's last step closing (so
+    no group spans two proteins). ``offsets`` None: the axis is one segment [0, T) — nothing lies outside it, its last step is T - 1."""
     N, T = order.shape
     dev = order.device
-    offsets = offsets.to(device=dev, dtype=torch.int64)
     steps = torch.arange(T, dtype=torch.int64, device=dev)
-    seg = torch.bucketize(steps, offsets[1:].contiguous(), right=True)                      # position -> protein
-    O = order.to(torch.int64)
-    perm = (torch.sort(O, dim=1).values == steps).all()
-    inside = (seg[O.clamp(0, max(T - 1, 0))] == seg).all()
+    perm = (torch.sort(order, dim=1).values == steps).all()
+    if offsets is None:
+        inside = torch.ones_like(perm)
+    else:
+        offsets = offsets.to(device=dev, dtype=torch.int64)
+        seg = torch.bucketize(steps, offsets[1:].contiguous(), right=True)                      # position -> protein
+        inside = (seg[order.to(torch.int64).clamp(0, max(T - 1, 0))] == seg).all()
     out = [perm, inside, ((S_fixed >= 0) & (S_fixed < VOCAB)).all()]
     if close is not None:
-        last = (offsets[1:] - 1)[offsets[1:] > offsets[:-1]].clamp(0, max(T - 1, 0))        # the last position of every non-empty protein
+        last = slice(-1, None) if offsets is None else \
+            (offsets[1:] - 1)[offsets[1:] > offsets[:-1]].clamp(0, max(T - 1, 0))               # the last position of every non-empty protein
         out += [((close == 0) | (close == 1)).all(), (close[:, last] == 1).all()]
     return torch.stack(out)
 

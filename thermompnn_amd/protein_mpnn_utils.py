@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import weights as _weights
-from .engine import Engine, cat_neighbors_nodes, gather_edges, gather_nodes  # noqa: F401  (API surface)
+from .engine import SAMPLE_TABLES, Engine, cat_neighbors_nodes, gather_edges, gather_nodes  # noqa: F401  (API surface)
 from .pdb_io import alt_parse_PDB, featurize, tied_featurize  # noqa: F401  (API surface)
 
 
@@ -208,39 +208,61 @@ class ProteinMPNN(_EngineOwner):
         ``thermompnn_amd.design.ProteinMPNNDesign`` has both."""
         if pssm_bias_flag or pssm_log_odds_flag:
             raise NotImplementedError("sample: pssm_bias_flag / pssm_log_odds_flag are served by thermompnn_amd.design.ProteinMPNNDesign")
+        pk = self._packed("sample", pack_sample_args, randn, chain_mask, mask, temperature, omit_AAs_np, bias_AAs_np, chain_M_pos,
+                          omit_AA_mask, bias_by_res)
+        S, probs = self._sample_members("sample", X, S_true, chain_encoding_all, residue_idx, mask, temperature, pk, generator, uniforms)
+        return {"S": S, "probs": probs, "decoding_order": pk["decoding_order"]}
+
+    def _packed(self, what, pack, randn, chain_mask, mask, temperature, omit_AAs_np, bias_AAs_np, chain_M_pos, *rest):
+        """``pack`` (``pack_sample_args`` or one with its leading arguments) on the engine's device, with the reference's defaults for
+        chain_M_pos / omit_AAs_np / bias_AAs_np; ``rest`` goes to ``pack`` as given."""
         if not float(temperature) > 0.0:
-            raise ValueError(f"sample: temperature must be positive, got {temperature!r}")
-        eng = self.engine()
-        dev = eng.device
-        B, L = X.shape[0], X.shape[1]
+            raise ValueError(f"{what}: temperature must be positive, got {temperature!r}")
+        dev = self.engine().device
         if mask is None:
-            raise ValueError("sample: mask is required")
+            raise ValueError(f"{what}: mask is required")
         if chain_M_pos is None:
             chain_M_pos = torch.ones_like(chain_mask)
         zeros21 = torch.zeros(21)
-        pk = pack_sample_args(randn.to(dev), chain_mask.to(dev), mask.to(dev), temperature,
-                              zeros21 if omit_AAs_np is None else omit_AAs_np, zeros21 if bias_AAs_np is None else bias_AAs_np,
-                              chain_M_pos.to(dev), omit_AA_mask, bias_by_res)
-        order, free, bias, allowed = pk["decoding_order"], pk["free"], pk["bias"], pk["allowed"]
+        return pack(randn.to(dev), chain_mask.to(dev), mask.to(dev), temperature, zeros21 if omit_AAs_np is None else omit_AAs_np,
+                    zeros21 if bias_AAs_np is None else bias_AAs_np, chain_M_pos.to(dev), *rest)
+
+    def _sample_members(self, what, X, S_true, chain_encoding_all, residue_idx, mask, temperature, pk, generator, uniforms):
+        """The members as chains of the sampler, ``pk`` from ``pack_sample_args`` (``Engine.sample`` / ``sample_each``) or with a
+        "close" key from ``design.pack_tied_args`` (``Engine.sample_tied`` / ``sample_tied_each``): one encode and B chains when the
+        members share the structure and the per-residue tables of ``pk``; otherwise one padded encode and the per-protein entry,
+        member b as one chain over protein b's own steps. -> (S [B,L] int64, probs [B,L,21])."""
+        eng = self.engine()
+        dev = eng.device
+        B, L = X.shape[0], X.shape[1]
         S_true = S_true.to(dev)
         if S_true.numel() and (int(S_true.min()) < 0 or int(S_true.max()) >= 21):
-            raise ValueError("sample: S_true must lie in [0, 21)")
+            raise ValueError(f"{what}: S_true must lie in [0, 21)")
+        tied, order = "close" in pk, pk["decoding_order"]
+        tables = {k: pk[k] for k in SAMPLE_TABLES if k in pk}
         with torch.cuda.device(dev):
             if uniforms is None:
                 uniforms = torch.rand((B, L), device=dev, dtype=torch.float32, generator=generator)
             u = torch.as_tensor(uniforms).to(device=dev, dtype=torch.float32).reshape(B, L)
             same = lambda t: t is None or bool((t[1:] == t[:1]).all())
-            shared = B > 1 and all(same(t) for t in (X.to(dev), mask.to(dev), residue_idx.to(dev), chain_encoding_all.to(dev), bias, allowed))
+            shared = B > 1 and all(same(t) for t in (X.to(dev), mask.to(dev), residue_idx.to(dev), chain_encoding_all.to(dev), *tables.values()))
             if shared or B == 1:
                 enc = self._encode_padded(eng, X[:1], mask[:1], residue_idx[:1], chain_encoding_all[:1])
-                r = eng.sample(enc, order, S_true, free, u, temperature=float(temperature), bias=bias[0],
-                               allowed=None if allowed is None else allowed[0])
-                S, probs = r["S"].to(torch.int64), r["probs"]
-            else:       # ONE padded encode and ONE launch: member b is protein b of the packed axis, sampled as one chain over its own steps
-                enc = self._encode_padded(eng, X, mask, residue_idx, chain_encoding_all)
-                flat = lambda t: None if t is None else t.reshape(B * L, *t.shape[2:])
-                shift = (torch.arange(B, device=dev, dtype=order.dtype) * L)[:, None]
-                r = eng.sample_each(enc, flat(order + shift)[None], flat(S_true)[None], flat(free)[None], flat(u)[None],
-                                    temperature=float(temperature), bias=flat(bias), allowed=flat(allowed))
-                S, probs = r["S"].view(B, L).to(torch.int64), r["probs"].view(B, L, 21)
-        return {"S": S, "probs": probs, "decoding_order": order}
+                kw = dict(temperature=float(temperature), **{k: None if t is None else t[0] for k, t in tables.items()})
+                if tied:
+                    r = eng.sample_tied(enc, order, pk["close"], S_true, pk["free"], u, weight=pk["weight"], **kw)
+                else:
+                    r = eng.sample(enc, order, S_true, pk["free"], u, **kw)
+                return r["S"].to(torch.int64), r["probs"]
+            # ONE padded encode and ONE launch: member b is protein b of the packed axis, sampled as one chain over its own steps
+            enc = self._encode_padded(eng, X, mask, residue_idx, chain_encoding_all)
+            flat = lambda t: None if t is None else t.reshape(B * L, *t.shape[2:])
+            row = lambda t: None if t is None else flat(t)[None]
+            shift = (torch.arange(B, device=dev, dtype=order.dtype) * L)[:, None]
+            kw = dict(temperature=float(temperature), **{k: flat(t) for k, t in tables.items()})
+            if tied:
+                r = eng.sample_tied_each(enc, row(order + shift), row(pk["close"]), row(S_true), row(pk["free"]), row(u),
+                                         weight=row(pk["weight"]), **kw)
+            else:
+                r = eng.sample_each(enc, row(order + shift), row(S_true), row(pk["free"]), row(u), **kw)
+        return r["S"].view(B, L).to(torch.int64), r["probs"].view(B, L, 21)
