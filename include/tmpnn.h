@@ -397,6 +397,43 @@ int tmpnn_seqloss_batch_backward(const float *X, const int32_t *S, const float *
                                  uint64_t seed, uint64_t step, const float *dlog_probs, float *grads, const void *saved,
                                  size_t saved_bytes, void *scratch, size_t scratch_bytes, tmpnn_stream_t stream);
 
+/* ---- gradients with respect to the backbone coordinates ------------------------------------------------------------------------
+ * The three split backwards with one output more: dX = dL / dX, [L,4,3] ([T,4,3] packed), fp32, directly after grads. Each entry takes
+ * its parent's arguments, buffers, sizes and error order, writes grads exactly as its parent does, bit for bit, and writes ALL of dX
+ * (the caller does not zero it). dX == NULL is TMPNN_E_INVALID: the parent is the entry for that case. tmpnn_finetune_backward_x needs
+ * the ProteinMPNN backward: mpnn_grads = 0 is TMPNN_E_INVALID; with num_final_layers = 0 the head never reads the structure and dX is
+ * all zeros. `saved` is never written: a second _x backward over it gives the same bits. No float atomics, fixed summation orders,
+ * bit-identical reruns. In the packed entry a row's neighbours lie in its own segment, so dX of protein b is a function of that
+ * protein's rows only. No workspace grows: the stage lives in scratch buffers that are dead after the encoder loop.
+ * What is differentiated: the featurizer (model_utils.py:314-381 = protein_mpnn_utils.py:1101-1168 of the reference): the virtual Cb
+ * from N, Ca, C (cross product included), the 25 atom-pair distances sqrt(|A - B|^2 + 1e-6) of every edge, their 16 RBFs, then
+ * edge_embedding; one stage at the tail of the backward, after d edge_embedding is formed:
+ *     dRBF [E,400] = dE0 W_edge[:, 16:416];   dD_p = sum_r dRBF[e, 16 p + r] RBF[e, 16 p + r] (-1.28 (D_p - mu_r));
+ *     edge (i, k), j = E_idx[i, k], pair p = (a, b): + dD_p (A - B) / D_p to atom a of row i, - the same to atom b of row j;
+ *     per residue: its own K edges in slot order, then the incoming edges in ascending edge order, then the Cb chain rule.
+ * Contract: the graph E_idx is a constant (no gradient through the choice of neighbours), and D_max of _dist (model_utils.py:318-319)
+ * is a constant. Pair 0 (Ca-Ca, the masked distance of _dist) therefore contributes (Ca_i - Ca_j) / D where mask_i mask_j = 1 and
+ * nothing elsewhere. (The reference's autograd leaks a gradient from every masked neighbour slot of a row into that row's farthest
+ * valid residue through D + (1 - mask_2D) D_max: a by-product of how masked entries are pushed behind the sort, undefined at distance
+ * ties, and absent whenever a protein has more than K valid residues: there the two definitions coincide exactly.) Everything else is
+ * the chain rule as written: a masked residue that IS selected as a neighbour gets the gradient of its (zero) coordinates through the
+ * 24 unmasked pairs, as in the reference. Rows whose coordinates reach the loss through no edge get exactly 0. */
+int tmpnn_finetune_backward_x(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
+                              int64_t L, const int32_t *pos, const int32_t *mut, const int32_t *wt, int64_t M, int n_final, int lightattn,
+                              int n_layers, const int32_t *dims, int subtract_mut, const float *params, int64_t slab_numel, float p_mpnn,
+                              float p_head, const float *keep_in, const float *head_keep_in, uint64_t seed, uint64_t step,
+                              const float *dpred, float *grads, float *dX, int mpnn_grads, const void *saved, size_t saved_bytes,
+                              void *scratch, size_t scratch_bytes, tmpnn_stream_t stream);
+int tmpnn_seqloss_backward_x(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
+                             int64_t L, int k_neighbors, const int32_t *ranks, const float *params, int64_t slab_numel, float p_mpnn,
+                             const float *keep_in, uint64_t seed, uint64_t step, const float *dlog_probs, float *grads, float *dX,
+                             const void *saved, size_t saved_bytes, void *scratch, size_t scratch_bytes, tmpnn_stream_t stream);
+int tmpnn_seqloss_batch_backward_x(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx,
+                                   const int32_t *chain_enc, const int32_t *offsets, int n_proteins, int64_t T, int min_len, int max_len,
+                                   int k_neighbors, const int32_t *ranks, const float *params, int64_t slab_numel, float p_mpnn,
+                                   const float *keep_in, uint64_t seed, uint64_t step, const float *dlog_probs, float *grads, float *dX,
+                                   const void *saved, size_t saved_bytes, void *scratch, size_t scratch_bytes, tmpnn_stream_t stream);
+
 /* ---- the fused path ------------------------------------------------------------------------------
  * Everything TransferModel.forward does on the device for a ragged batch of N proteins
  * (transfer_model.py:75-121 + protein_mpnn_utils.py:1222-1277), one call, 18 launches on `stream` (14 when every workgroup has at most one residue tile).

@@ -76,6 +76,8 @@ SIGNATURES = {
                                     _p, C.c_uint64, C.c_uint64, _p, _p, _p, _p, _sz, _p]),
     "tmpnn_finetune_backward": (_i, [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _i64, _i, _i, _i, _p, _i, _p, _i64, C.c_float, C.c_float, _p, _p,
                                      C.c_uint64, C.c_uint64, _p, _p, _i, _p, _sz, _p, _sz, _p]),
+    "tmpnn_finetune_backward_x": (_i, [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _i64, _i, _i, _i, _p, _i, _p, _i64, C.c_float, C.c_float, _p, _p,
+                                       C.c_uint64, C.c_uint64, _p, _p, _p, _i, _p, _sz, _p, _sz, _p]),
     "tmpnn_seqloss_slab_numel": (_i64, []),
     "tmpnn_seqloss_saved_bytes": (_sz, [_i64]),
     "tmpnn_seqloss_scratch_bytes": (_sz, [_i64]),
@@ -83,6 +85,8 @@ SIGNATURES = {
                                    _p]),
     "tmpnn_seqloss_backward": (_i, [_p, _p, _p, _p, _p, _i64, _i, _p, _p, _i64, C.c_float, _p, C.c_uint64, C.c_uint64, _p, _p, _p, _sz, _p,
                                     _sz, _p]),
+    "tmpnn_seqloss_backward_x": (_i, [_p, _p, _p, _p, _p, _i64, _i, _p, _p, _i64, C.c_float, _p, C.c_uint64, C.c_uint64, _p, _p, _p, _p, _sz,
+                                      _p, _sz, _p]),
     "tmpnn_seqloss_batch_saved_bytes": (_sz, [_i64, _i, _i]),
     "tmpnn_seqloss_batch_scratch_bytes": (_sz, [_i64, _i, _i]),
     "tmpnn_seqloss_batch_mask_numel": (_i64, [_i64, _i]),
@@ -90,6 +94,8 @@ SIGNATURES = {
                                          C.c_uint64, _p, _p, _p, _p, _sz, _p]),
     "tmpnn_seqloss_batch_backward": (_i, [_p, _p, _p, _p, _p, _p, _i, _i64, _i, _i, _i, _p, _p, _i64, C.c_float, _p, C.c_uint64,
                                           C.c_uint64, _p, _p, _p, _sz, _p, _sz, _p]),
+    "tmpnn_seqloss_batch_backward_x": (_i, [_p, _p, _p, _p, _p, _p, _i, _i64, _i, _i, _i, _p, _p, _i64, C.c_float, _p, C.c_uint64,
+                                            C.c_uint64, _p, _p, _p, _p, _sz, _p, _sz, _p]),
     "tmpnn_pdb_parse": (_i, [C.c_char_p, C.c_char_p, C.POINTER(_p)]),
     "tmpnn_pdb_parse_batch": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, _i, C.POINTER(_p)]),
     "tmpnn_pdb_parse_batch_status": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, _i, C.POINTER(_p), _p]),

@@ -132,6 +132,9 @@ class FinetuneFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plan, inp, subtract, p_mpnn, p_head, seed, step, mpnn_grads, *params):
+        ctx.x_in = None
+        if len(params) == len(plan.sizes) + 1:           # the coordinates follow the parameters (forward_coords): inp.X holds their values
+            params, ctx.x_in = params[:-1], (tuple(params[-1].shape), params[-1].dtype)
         slab = plan.pack(params)
         dev = slab.device
         saved = torch.empty(plan.saved_bytes(inp.L, inp.M), dtype=torch.uint8, device=dev)
@@ -155,16 +158,24 @@ class FinetuneFunction(torch.autograd.Function):
         dpred = dpred.to(device=dev, dtype=torch.float32).contiguous()
         grads = torch.zeros(plan.numel, dtype=torch.float32, device=dev)
         scratch = plan.scratch(inp.L, inp.M, dev)
+        dX = torch.empty_like(inp.X) if ctx.x_in is not None and ctx.needs_input_grad[-1] else None
         with torch.cuda.device(dev):
-            check(plan.lib.tmpnn_finetune_backward(
-                *inp.args(), plan.n_final, int(plan.lightattn), plan.n_layers, plan.cdims, subtract, _ptr(slab), plan.numel, p_mpnn,
-                p_head, None, None, seed, step, _ptr(dpred), _ptr(grads), mpnn_grads, _ptr(saved), saved.numel(), _ptr(scratch),
-                scratch.numel(), _stream()), "tmpnn_finetune_backward")
+            if dX is None:
+                check(plan.lib.tmpnn_finetune_backward(
+                    *inp.args(), plan.n_final, int(plan.lightattn), plan.n_layers, plan.cdims, subtract, _ptr(slab), plan.numel, p_mpnn,
+                    p_head, None, None, seed, step, _ptr(dpred), _ptr(grads), mpnn_grads, _ptr(saved), saved.numel(), _ptr(scratch),
+                    scratch.numel(), _stream()), "tmpnn_finetune_backward")
+            else:
+                check(plan.lib.tmpnn_finetune_backward_x(
+                    *inp.args(), plan.n_final, int(plan.lightattn), plan.n_layers, plan.cdims, subtract, _ptr(slab), plan.numel, p_mpnn,
+                    p_head, None, None, seed, step, _ptr(dpred), _ptr(grads), _ptr(dX), mpnn_grads, _ptr(saved), saved.numel(),
+                    _ptr(scratch), scratch.numel(), _stream()), "tmpnn_finetune_backward_x")
         out, off = [], 0
         for i, (shape, n) in enumerate(zip(plan.shapes.values(), plan.sizes)):
             out.append(grads[off:off + n].view(shape) if ctx.needs_input_grad[8 + i] else None)
             off += n
-        return (None,) * 8 + tuple(out)
+        out = (None,) * 8 + tuple(out)
+        return out if ctx.x_in is None else out + (None if dX is None else dX.view(ctx.x_in[0]).to(ctx.x_in[1]),)
 
 
 def wants_grad(model) -> bool:
@@ -173,20 +184,47 @@ def wants_grad(model) -> bool:
         any(p.requires_grad for p in model.parameters())
 
 
-def transfer_forward(model, pdb, mutations):
+_NOT_DIFFERENTIABLE = "{} is part of the gradient path: set model.differentiable = True"
+_FROZEN = "{} needs ProteinMPNN's parameters unfrozen (requires_grad): the coordinates' gradient comes out of the ProteinMPNN backward"
+
+
+def _given_coords(X, parsed, device, what):
+    """The caller's coordinates [L,4,3] in place of the parsed ones -> (their float32 values for the device call, the tensor that
+    enters the graph or None when nothing asks for its gradient)."""
+    if not torch.is_tensor(X) or not X.is_floating_point() or tuple(X.shape) != tuple(parsed.shape):
+        raise ValueError(f"{what}: X must be a float tensor of shape {tuple(parsed.shape)} (the parsed structure's residues x N, CA, C, O)")
+    if X.device != device:
+        raise ValueError(f"{what}: X is on {X.device}, the model on {device}")
+    return X.detach().float().contiguous(), (X if X.requires_grad and torch.is_grad_enabled() else None)
+
+
+def transfer_forward(model, pdb, mutations, X=None):
     """TransferModel.forward on the gradient path -> (list of {"ddG": Tensor[1]} | None, None); the Tensor[1]s are views of one
-    pred tensor that carries the graph."""
+    pred tensor that carries the graph. ``X`` (TransferModel.forward_coords) replaces the parsed coordinates and, when it requires
+    grad, is one more input of the Function (tmpnn_finetune_backward_x)."""
     from .pdb_io import tied_featurize
     params = dict(model.named_parameters())
     device = next(iter(params.values())).device
     if device.type != "cuda":
         raise RuntimeError("thermompnn_amd runs on MI355X only: move the model to a CUDA (ROCm) device with .cuda(); there is no "
                            "CPU execution path")
+    plan = plan_for(model)
+    slab_params = [params[k] for k in plan.names]
+    mpnn_grads = any(p.requires_grad for p in slab_params[:plan.n_mpnn])
     live = [m for m in mutations if m is not None]
-    if not live:
+    if X is None and not live:
         return [None for _ in mutations], None
     feats = tied_featurize([pdb[0]], device, None, None, None, None, None, None, ca_only=False)
-    X, S, mask, chain_enc, residue_idx = feats[0][0], feats[1][0], feats[2][0], feats[5][0], feats[12][0]
+    x_graph = None
+    if X is not None:                                    # checked whatever the mutation list holds
+        if not mpnn_grads:
+            raise RuntimeError(_FROZEN.format("forward_coords"))
+        X_val, x_graph = _given_coords(X, feats[0][0], device, "forward_coords")
+        if not live:
+            return [None for _ in mutations], None
+    else:
+        X_val = feats[0][0].float().contiguous()
+    S, mask, chain_enc, residue_idx = feats[1][0], feats[2][0], feats[5][0], feats[12][0]
     L = int(S.numel())
     if not L_MIN <= L <= L_MAX:
         raise ValueError(f"protein length {L} outside [{L_MIN}, {L_MAX}]: the differentiable path runs one protein per call")
@@ -196,33 +234,39 @@ def transfer_forward(model, pdb, mutations):
     code = lambda a: _AA[a] if a in _AA else ALPHABET.index(a)
     sel = torch.tensor([[int(m.position) for m in live], [code(m.mutation) for m in live], [code(m.wildtype) for m in live]],
                        dtype=torch.int32).to(device)
-    inp = _Inputs(X.float().contiguous(), S.to(torch.int32).contiguous(), mask.float().contiguous(),
+    inp = _Inputs(X_val, S.to(torch.int32).contiguous(), mask.float().contiguous(),
                   residue_idx.to(torch.int32).contiguous(), chain_enc.to(torch.int32).contiguous(), sel[0], sel[1], sel[2])
-    plan = plan_for(model)
-    slab_params = [params[k] for k in plan.names]
-    mpnn_grads = any(p.requires_grad for p in slab_params[:plan.n_mpnn])
     p_mpnn = MPNN_DROPOUT if model.prot_mpnn.training and plan.n_final > 0 else 0.0
     p_head = CONV_DROPOUT if plan.lightattn and model.light_attention.training else 0.0
     seed, step = _draw_key()
-    pred = FinetuneFunction.apply(plan, inp, bool(model.subtract_mut), p_mpnn, p_head, seed, step, mpnn_grads, *slab_params)
+    extra = () if x_graph is None else (x_graph,)
+    pred = FinetuneFunction.apply(plan, inp, bool(model.subtract_mut), p_mpnn, p_head, seed, step, mpnn_grads, *slab_params, *extra)
     pieces = iter(pred.split(1))
     return [None if m is None else {"ddG": next(pieces)} for m in mutations], None
 
 
-def transfer_sequence_log_probs(model, pdb, chain_M=None, randn=None):
-    """TransferModel.sequence_log_probs: log_probs [L,21] of one parsed structure with a graph over prot_mpnn's parameters."""
+def transfer_sequence_log_probs(model, pdb, chain_M=None, randn=None, X=None):
+    """TransferModel.sequence_log_probs: log_probs [L,21] of one parsed structure with a graph over prot_mpnn's parameters, and over
+    ``X`` [L,4,3] when it is given in place of the parsed coordinates and requires grad."""
     from . import model_utils as mu
     from .pdb_io import tied_featurize
     from .protein_mpnn_utils import decoding_ranks
     if not getattr(model, "differentiable", False):
-        raise RuntimeError("sequence_log_probs is part of the gradient path: set model.differentiable = True")
+        raise RuntimeError(_NOT_DIFFERENTIABLE.format("sequence_log_probs"))
     params = [p for _, p in model.prot_mpnn.named_parameters()]
     device = params[0].device
     if device.type != "cuda":
         raise RuntimeError("thermompnn_amd runs on MI355X only: move the model to a CUDA (ROCm) device with .cuda(); there is no "
                            "CPU execution path")
     feats = tied_featurize([pdb[0] if isinstance(pdb, (list, tuple)) else pdb], device, None, None, None, None, None, None, ca_only=False)
-    X, S, mask, chain_enc, residue_idx = feats[0][0], feats[1][0], feats[2][0], feats[5][0], feats[12][0]
+    X_parsed, S, mask, chain_enc, residue_idx = feats[0][0], feats[1][0], feats[2][0], feats[5][0], feats[12][0]
+    if X is None:
+        X = X_parsed
+    else:
+        if not any(p.requires_grad for p in params):
+            raise RuntimeError(_FROZEN.format("sequence_log_probs(X=)"))
+        X_val, x_graph = _given_coords(X, X_parsed, device, "sequence_log_probs")
+        X = X_val if x_graph is None else x_graph
     cm = mask if chain_M is None else torch.as_tensor(chain_M, dtype=torch.float32, device=device) * mask
     if randn is None:
         randn = torch.randn(cm.shape, device=device)

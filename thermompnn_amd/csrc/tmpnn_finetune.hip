@@ -266,18 +266,7 @@ __global__ __launch_bounds__(TM_THREADS) void ft_ln_bwd_kernel(FtLnB a) {
 }
 
 // ---- graph, features, embeddings ---------------------------------------------------------------------------------------------------
-__constant__ int c_ft_pa[25] = {1, 0, 2, 3, 4, 1, 1, 1, 1, 0, 0, 0, 4, 4, 3, 0, 2, 3, 4, 2, 3, 4, 2, 3, 2};   // PAIR_ORDER (:1143-1167)
-__constant__ int c_ft_pb[25] = {1, 0, 2, 3, 4, 0, 2, 3, 4, 2, 3, 4, 2, 3, 2, 1, 1, 1, 1, 0, 0, 0, 4, 4, 3};
-
-__device__ __forceinline__ void ft_atom(const float *x, int a, float *o) {   // N, Ca, C, O, virtual Cb (:1131-1138)
-    if (a < 4) { o[0] = x[3 * a]; o[1] = x[3 * a + 1]; o[2] = x[3 * a + 2]; return; }
-    float b[3], cc[3];
-    for (int k = 0; k < 3; ++k) { b[k] = x[3 + k] - x[k]; cc[k] = x[6 + k] - x[3 + k]; }
-    const float ax = b[1] * cc[2] - b[2] * cc[1], ay = b[2] * cc[0] - b[0] * cc[2], az = b[0] * cc[1] - b[1] * cc[0];
-    const float av[3] = {ax, ay, az};
-    for (int k = 0; k < 3; ++k) o[k] = -0.58273431f * av[k] + 0.56802827f * b[k] - 0.54067466f * cc[k] + x[3 + k];
-}
-
+// (the pair order c_ft_pa / c_ft_pb and ft_atom: tmpnn_ft.h)
 // per edge e = (i, k): compact E_idx, positional class, Ein[e] = [W_pos[:, cls] + b_pos | 400 RBF]. L rows in N segments (offs [N + 1],
 // already made safe: ft_offsets_kernel / sq_segments_kernel); a neighbour is clamped into its residue's own segment.
 struct FtGraph { const float *X; const int32_t *ridx, *cenc, *E48; const float *D48, *pos_w, *pos_b; int32_t *eidx, *cls; float *Ein; int L, K;
@@ -909,6 +898,13 @@ void ft_backward(const FtCtx &c) {
         ft_linear_t(c, w.t1, FT_H, c.params + S.edgew, 416, w.dEp, 16, E, FT_H, 16);             // d E_pos = dE0 W_edge[:, :16]
         ft_class_sum(c, w.cls, w.dEp, 16, 0, E, 16, 66, c.grads + S.posw, 1, 66);                  // d W_pos[d, class]
         ft_class_sum(c, nullptr, w.dEp, 16, 0, E, 16, 1, c.grads + S.posb, 0, 1);
+        if (c.dX) {
+            // d RBF = dE0 W_edge[:, 16:416] into dA (dead after the encoder loop); tmpnn_coordgrad.hip takes it to dX through tm (dead too)
+            ft_linear_t(c, w.t1, FT_H, c.params + S.edgew + 16, 416, w.dA, 400, E, FT_H, 400);
+            ft_coord_grad(c, w.dA);
+        }
+    } else if (c.dX) {
+        (void)hipMemsetAsync(c.dX, 0, (size_t)L * 12 * 4, c.st);     // no ProteinMPNN layer: the head never reads the structure
     }
     ft_class_sum(c, c.S, w.dhS, FT_H, 0, L, FT_H, TMPNN_VOCAB, c.grads + S.Ws, FT_H, 1);        // d W_s[a] = sum over S_i = a
 }
@@ -1100,30 +1096,55 @@ extern "C" int tmpnn_finetune_forward(const float *X, const int32_t *S, const fl
     return tm_check_launch("finetune_forward");
 }
 
+// both backwards of the split step: what = "finetune_backward" (dX null) or "finetune_backward_x" (dX [L,4,3], written whole)
+static int ft_backward_entry(const char *what, bool want_dx, const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx,
+                             const int32_t *chain_enc, int64_t L, const int32_t *pos, const int32_t *mut, const int32_t *wt, int64_t M,
+                             int n_final, int lightattn, int n_layers, const int32_t *dims, int subtract_mut, const float *params,
+                             int64_t slab_numel, float p_mpnn, float p_head, const float *keep_in, const float *head_keep_in, uint64_t seed,
+                             uint64_t step, const float *dpred, float *grads, float *dX, int mpnn_grads, const void *saved, size_t saved_bytes,
+                             void *scratch, size_t scratch_bytes, tmpnn_stream_t stream) {
+    FT_TRY(ft_check(what, X, S, mask, residue_idx, chain_enc, L, pos, mut, wt, M, n_final, lightattn, n_layers, dims, params, slab_numel));
+    FT_REQUIRE(dpred && grads, "%s: null pointer", what);
+    if (want_dx) {
+        FT_REQUIRE(dX, "%s: dX is null (tmpnn_finetune_backward is the entry without it)", what);
+        FT_REQUIRE(mpnn_grads, "%s: dX needs the ProteinMPNN backward (mpnn_grads = 1)", what);
+    }
+    FT_TRY(ft_check_split(what, n_final, lightattn, p_mpnn, p_head, keep_in, head_keep_in));
+    FT_TRY(ft_check_buf(what, "saved", (void *)saved, saved_bytes, tmpnn_finetune_saved_bytes(L, M, n_final, lightattn, n_layers, dims)));
+    FT_TRY(ft_check_buf(what, "scratch", scratch, scratch_bytes, tmpnn_finetune_scratch_bytes(L, M, n_final, lightattn, n_layers, dims)));
+    FtCtx c = ft_ctx(X, S, mask, residue_idx, chain_enc, L, pos, mut, wt, M, n_final, lightattn, n_layers, dims, subtract_mut, params, grads,
+                     nullptr, (hipStream_t)stream);
+    // the saved part is only read: its one writer is the forward
+    c.w = ft_carve2(const_cast<void *>(saved), scratch, true, L, M, lightattn, n_layers, dims);
+    c.dX = dX;
+    ft_set_drop(c, L, ft_k48(L), p_mpnn, keep_in, nullptr, seed, step);
+    FT_TRY(tm_head_train_core(c.w.headX, M, c.w.rows_id, mut, wt, nullptr, M, lightattn, n_layers, dims, subtract_mut, params + c.lay.head,
+                              grads + c.lay.head, p_head, head_keep_in, nullptr, seed, step, nullptr, nullptr, c.w.head_ws_b, c.st,
+                              mpnn_grads ? c.w.dheadX : nullptr, dpred));
+    if (mpnn_grads) ft_backward(c);
+    return tm_check_launch(what);
+}
+
 extern "C" int tmpnn_finetune_backward(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
                                        int64_t L, const int32_t *pos, const int32_t *mut, const int32_t *wt, int64_t M, int n_final, int lightattn,
                                        int n_layers, const int32_t *dims, int subtract_mut, const float *params, int64_t slab_numel, float p_mpnn,
                                        float p_head, const float *keep_in, const float *head_keep_in, uint64_t seed, uint64_t step,
                                        const float *dpred, float *grads, int mpnn_grads, const void *saved, size_t saved_bytes, void *scratch,
                                        size_t scratch_bytes, tmpnn_stream_t stream) {
-    FT_TRY(ft_check("finetune_backward", X, S, mask, residue_idx, chain_enc, L, pos, mut, wt, M, n_final, lightattn, n_layers, dims, params,
-                    slab_numel));
-    FT_REQUIRE(dpred && grads, "finetune_backward: null pointer");
-    FT_TRY(ft_check_split("finetune_backward", n_final, lightattn, p_mpnn, p_head, keep_in, head_keep_in));
-    FT_TRY(ft_check_buf("finetune_backward", "saved", (void *)saved, saved_bytes,
-                        tmpnn_finetune_saved_bytes(L, M, n_final, lightattn, n_layers, dims)));
-    FT_TRY(ft_check_buf("finetune_backward", "scratch", scratch, scratch_bytes,
-                        tmpnn_finetune_scratch_bytes(L, M, n_final, lightattn, n_layers, dims)));
-    FtCtx c = ft_ctx(X, S, mask, residue_idx, chain_enc, L, pos, mut, wt, M, n_final, lightattn, n_layers, dims, subtract_mut, params, grads,
-                     nullptr, (hipStream_t)stream);
-    // the saved part is only read: its one writer is the forward
-    c.w = ft_carve2(const_cast<void *>(saved), scratch, true, L, M, lightattn, n_layers, dims);
-    ft_set_drop(c, L, ft_k48(L), p_mpnn, keep_in, nullptr, seed, step);
-    FT_TRY(tm_head_train_core(c.w.headX, M, c.w.rows_id, mut, wt, nullptr, M, lightattn, n_layers, dims, subtract_mut, params + c.lay.head,
-                              grads + c.lay.head, p_head, head_keep_in, nullptr, seed, step, nullptr, nullptr, c.w.head_ws_b, c.st,
-                              mpnn_grads ? c.w.dheadX : nullptr, dpred));
-    if (mpnn_grads) ft_backward(c);
-    return tm_check_launch("finetune_backward");
+    return ft_backward_entry("finetune_backward", false, X, S, mask, residue_idx, chain_enc, L, pos, mut, wt, M, n_final, lightattn, n_layers, dims,
+                             subtract_mut, params, slab_numel, p_mpnn, p_head, keep_in, head_keep_in, seed, step, dpred, grads, nullptr,
+                             mpnn_grads, saved, saved_bytes, scratch, scratch_bytes, stream);
+}
+
+extern "C" int tmpnn_finetune_backward_x(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx,
+                                         const int32_t *chain_enc, int64_t L, const int32_t *pos, const int32_t *mut, const int32_t *wt, int64_t M,
+                                         int n_final, int lightattn, int n_layers, const int32_t *dims, int subtract_mut, const float *params,
+                                         int64_t slab_numel, float p_mpnn, float p_head, const float *keep_in, const float *head_keep_in,
+                                         uint64_t seed, uint64_t step, const float *dpred, float *grads, float *dX, int mpnn_grads,
+                                         const void *saved, size_t saved_bytes, void *scratch, size_t scratch_bytes, tmpnn_stream_t stream) {
+    return ft_backward_entry("finetune_backward_x", true, X, S, mask, residue_idx, chain_enc, L, pos, mut, wt, M, n_final, lightattn, n_layers,
+                             dims, subtract_mut, params, slab_numel, p_mpnn, p_head, keep_in, head_keep_in, seed, step, dpred, grads, dX,
+                             mpnn_grads, saved, saved_bytes, scratch, scratch_bytes, stream);
 }
 
 // ---- the sequence loss: log p(S | X) under a decoding order, and its gradient ------------------------------------------------------
@@ -1183,18 +1204,36 @@ extern "C" int tmpnn_seqloss_forward(const float *X, const int32_t *S, const flo
     return tm_check_launch("seqloss_forward");
 }
 
-extern "C" int tmpnn_seqloss_backward(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
-                                      int64_t L, int k_neighbors, const int32_t *ranks, const float *params, int64_t slab_numel, float p_mpnn,
-                                      const float *keep_in, uint64_t seed, uint64_t step, const float *dlog_probs, float *grads,
-                                      const void *saved, size_t saved_bytes, void *scratch, size_t scratch_bytes, tmpnn_stream_t stream) {
-    FT_TRY(sq_check("seqloss_backward", X, S, mask, residue_idx, chain_enc, L, k_neighbors, params, slab_numel, p_mpnn, saved, saved_bytes));
-    FT_REQUIRE(dlog_probs && grads, "seqloss_backward: null pointer");
-    FT_TRY(ft_check_buf("seqloss_backward", "scratch", scratch, scratch_bytes, tmpnn_seqloss_scratch_bytes(L)));
+static int sq_backward_entry(const char *what, bool want_dx, const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx,
+                             const int32_t *chain_enc, int64_t L, int k_neighbors, const int32_t *ranks, const float *params, int64_t slab_numel,
+                             float p_mpnn, const float *keep_in, uint64_t seed, uint64_t step, const float *dlog_probs, float *grads, float *dX,
+                             const void *saved, size_t saved_bytes, void *scratch, size_t scratch_bytes, tmpnn_stream_t stream) {
+    FT_TRY(sq_check(what, X, S, mask, residue_idx, chain_enc, L, k_neighbors, params, slab_numel, p_mpnn, saved, saved_bytes));
+    FT_REQUIRE(dlog_probs && grads, "%s: null pointer", what);
+    FT_REQUIRE(!want_dx || dX, "%s: dX is null (tmpnn_seqloss_backward is the entry without it)", what);
+    FT_TRY(ft_check_buf(what, "scratch", scratch, scratch_bytes, tmpnn_seqloss_scratch_bytes(L)));
     // the saved part is only read: its one writer is the forward
     FtCtx c = sq_ctx(X, S, mask, residue_idx, chain_enc, L, k_neighbors, ranks, params, grads, const_cast<void *>(saved), scratch,
                      (hipStream_t)stream);
     c.dlp = dlog_probs;
+    c.dX = dX;
     ft_set_drop(c, L, ft_k48(L), p_mpnn, keep_in, nullptr, seed, step);
     ft_backward(c);
-    return tm_check_launch("seqloss_backward");
+    return tm_check_launch(what);
+}
+
+extern "C" int tmpnn_seqloss_backward(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
+                                      int64_t L, int k_neighbors, const int32_t *ranks, const float *params, int64_t slab_numel, float p_mpnn,
+                                      const float *keep_in, uint64_t seed, uint64_t step, const float *dlog_probs, float *grads,
+                                      const void *saved, size_t saved_bytes, void *scratch, size_t scratch_bytes, tmpnn_stream_t stream) {
+    return sq_backward_entry("seqloss_backward", false, X, S, mask, residue_idx, chain_enc, L, k_neighbors, ranks, params, slab_numel, p_mpnn,
+                             keep_in, seed, step, dlog_probs, grads, nullptr, saved, saved_bytes, scratch, scratch_bytes, stream);
+}
+
+extern "C" int tmpnn_seqloss_backward_x(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx, const int32_t *chain_enc,
+                                        int64_t L, int k_neighbors, const int32_t *ranks, const float *params, int64_t slab_numel, float p_mpnn,
+                                        const float *keep_in, uint64_t seed, uint64_t step, const float *dlog_probs, float *grads, float *dX,
+                                        const void *saved, size_t saved_bytes, void *scratch, size_t scratch_bytes, tmpnn_stream_t stream) {
+    return sq_backward_entry("seqloss_backward_x", true, X, S, mask, residue_idx, chain_enc, L, k_neighbors, ranks, params, slab_numel, p_mpnn,
+                             keep_in, seed, step, dlog_probs, grads, dX, saved, saved_bytes, scratch, scratch_bytes, stream);
 }

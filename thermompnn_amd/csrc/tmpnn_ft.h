@@ -1,6 +1,7 @@
 // What the translation units of the training path share: tmpnn_finetune.hip (the kernels, ft_forward / ft_backward, the carve, the
-// one-protein entries tmpnn_finetune_* / tmpnn_seqloss_*) and tmpnn_seqbatch.hip (the packed entries tmpnn_seqloss_batch_*, which run the
-// same ft_forward / ft_backward over n_proteins segments of one row space).
+// one-protein entries tmpnn_finetune_* / tmpnn_seqloss_*), tmpnn_seqbatch.hip (the packed entries tmpnn_seqloss_batch_*, which run the
+// same ft_forward / ft_backward over n_proteins segments of one row space) and tmpnn_coordgrad.hip (the last stage of the _x backwards:
+// dRBF -> dX).
 #pragma once
 #include <stdint.h>
 
@@ -60,6 +61,7 @@ struct FtCtx {
     const int32_t *ranks;                         // the sequence loss: decoding ranks [L] (null: every neighbour visible, the ddG path)
     const float *params;
     float *grads;
+    float *dX;                                    // the _x backwards: dL / dX [L,4,3] (null: ft_backward stops at W_edge / W_pos)
     FtLayout lay;
     FtWs w;
     FtDrop drop;
@@ -69,6 +71,22 @@ struct FtCtx {
                                                   // checked and copied into w.offs; null: one protein, ft_forward writes [0, L] there
     int32_t *status;                              // the packed entries: the caller's status word (null: the carve's own, never read)
 };
+
+// ---- the featurizer's geometry, shared by the forward (ft_graph_kernel) and the coordinates' backward (tmpnn_coordgrad.hip) -------------
+static __constant__ int c_ft_pa[25] = {1, 0, 2, 3, 4, 1, 1, 1, 1, 0, 0, 0, 4, 4, 3, 0, 2, 3, 4, 2, 3, 4, 2, 3, 2};   // PAIR_ORDER (:1143-1167)
+static __constant__ int c_ft_pb[25] = {1, 0, 2, 3, 4, 0, 2, 3, 4, 2, 3, 4, 2, 3, 2, 1, 1, 1, 1, 0, 0, 0, 4, 4, 3};
+
+__device__ __forceinline__ void ft_atom(const float *x, int a, float *o) {   // N, Ca, C, O, virtual Cb (:1131-1138)
+    if (a < 4) { o[0] = x[3 * a]; o[1] = x[3 * a + 1]; o[2] = x[3 * a + 2]; return; }
+    float b[3], cc[3];
+    for (int k = 0; k < 3; ++k) { b[k] = x[3 + k] - x[k]; cc[k] = x[6 + k] - x[3 + k]; }
+    const float ax = b[1] * cc[2] - b[2] * cc[1], ay = b[2] * cc[0] - b[0] * cc[2], az = b[0] * cc[1] - b[1] * cc[0];
+    const float av[3] = {ax, ay, az};
+    for (int k = 0; k < 3; ++k) o[k] = -0.58273431f * av[k] + 0.56802827f * b[k] - 0.54067466f * cc[k] + x[3 + k];
+}
+
+// tmpnn_coordgrad.hip: dRBF [E,400] (= dE0 W_edge[:, 16:416]) -> c.dX [L,4,3], through c.w.tm (30 floats per edge)
+void ft_coord_grad(const FtCtx &c, const float *dRBF);
 
 // tmpnn_finetune.hip
 FtLayout sq_layout();

@@ -131,21 +131,45 @@ extern "C" int tmpnn_seqloss_batch_forward(const float *X, const int32_t *S, con
     return tm_check_launch("seqloss_batch_forward");
 }
 
+static int sb_backward_entry(const char *what, bool want_dx, const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx,
+                             const int32_t *chain_enc, const int32_t *offsets, int n_proteins, int64_t T, int min_len, int max_len,
+                             int k_neighbors, const int32_t *ranks, const float *params, int64_t slab_numel, float p_mpnn, const float *keep_in,
+                             uint64_t seed, uint64_t step, const float *dlog_probs, float *grads, float *dX, const void *saved,
+                             size_t saved_bytes, void *scratch, size_t scratch_bytes, tmpnn_stream_t stream) {
+    int K = 0;
+    FT_TRY(sb_check(what, X, S, mask, residue_idx, chain_enc, offsets, n_proteins, T, min_len, max_len, k_neighbors, params, slab_numel, p_mpnn,
+                    saved, saved_bytes, &K));
+    FT_REQUIRE(dlog_probs && grads, "%s: null pointer", what);
+    FT_REQUIRE(!want_dx || dX, "%s: dX is null (tmpnn_seqloss_batch_backward is the entry without it)", what);
+    FT_TRY(ft_check_buf(what, "scratch", scratch, scratch_bytes, tmpnn_seqloss_batch_scratch_bytes(T, n_proteins, K)));
+    // the saved part is only read: its one writer is the forward (the graph in it carries the segments: the offsets are not read again)
+    FtCtx c = sb_ctx(X, S, mask, residue_idx, chain_enc, offsets, n_proteins, T, min_len, max_len, K, ranks, params, grads,
+                     const_cast<void *>(saved), scratch, (hipStream_t)stream);
+    c.dlp = dlog_probs;
+    c.dX = dX;
+    ft_set_drop(c, T, K, p_mpnn, keep_in, nullptr, seed, step);
+    ft_backward(c);
+    return tm_check_launch(what);
+}
+
 extern "C" int tmpnn_seqloss_batch_backward(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx,
                                             const int32_t *chain_enc, const int32_t *offsets, int n_proteins, int64_t T, int min_len, int max_len,
                                             int k_neighbors, const int32_t *ranks, const float *params, int64_t slab_numel, float p_mpnn,
                                             const float *keep_in, uint64_t seed, uint64_t step, const float *dlog_probs, float *grads,
                                             const void *saved, size_t saved_bytes, void *scratch, size_t scratch_bytes, tmpnn_stream_t stream) {
-    int K = 0;
-    FT_TRY(sb_check("seqloss_batch_backward", X, S, mask, residue_idx, chain_enc, offsets, n_proteins, T, min_len, max_len, k_neighbors, params,
-                    slab_numel, p_mpnn, saved, saved_bytes, &K));
-    FT_REQUIRE(dlog_probs && grads, "seqloss_batch_backward: null pointer");
-    FT_TRY(ft_check_buf("seqloss_batch_backward", "scratch", scratch, scratch_bytes, tmpnn_seqloss_batch_scratch_bytes(T, n_proteins, K)));
-    // the saved part is only read: its one writer is the forward (the graph in it carries the segments: the offsets are not read again)
-    FtCtx c = sb_ctx(X, S, mask, residue_idx, chain_enc, offsets, n_proteins, T, min_len, max_len, K, ranks, params, grads,
-                     const_cast<void *>(saved), scratch, (hipStream_t)stream);
-    c.dlp = dlog_probs;
-    ft_set_drop(c, T, K, p_mpnn, keep_in, nullptr, seed, step);
-    ft_backward(c);
-    return tm_check_launch("seqloss_batch_backward");
+    return sb_backward_entry("seqloss_batch_backward", false, X, S, mask, residue_idx, chain_enc, offsets, n_proteins, T, min_len, max_len,
+                             k_neighbors, ranks, params, slab_numel, p_mpnn, keep_in, seed, step, dlog_probs, grads, nullptr, saved,
+                             saved_bytes, scratch, scratch_bytes, stream);
+}
+
+// the same backward with dL / dX [T,4,3]: a row's neighbours lie in its own segment, so protein b's dX depends on its rows only
+extern "C" int tmpnn_seqloss_batch_backward_x(const float *X, const int32_t *S, const float *mask, const int32_t *residue_idx,
+                                              const int32_t *chain_enc, const int32_t *offsets, int n_proteins, int64_t T, int min_len,
+                                              int max_len, int k_neighbors, const int32_t *ranks, const float *params, int64_t slab_numel,
+                                              float p_mpnn, const float *keep_in, uint64_t seed, uint64_t step, const float *dlog_probs,
+                                              float *grads, float *dX, const void *saved, size_t saved_bytes, void *scratch,
+                                              size_t scratch_bytes, tmpnn_stream_t stream) {
+    return sb_backward_entry("seqloss_batch_backward_x", true, X, S, mask, residue_idx, chain_enc, offsets, n_proteins, T, min_len, max_len,
+                             k_neighbors, ranks, params, slab_numel, p_mpnn, keep_in, seed, step, dlog_probs, grads, dX, saved, saved_bytes,
+                             scratch, scratch_bytes, stream);
 }

@@ -12,8 +12,10 @@ The arithmetic runs in csrc/tmpnn_finetune.hip (tmpnn_seqloss_forward / _backwar
 deterministic backward of the ddG fine-tuning path with the order-masked decoder and the output layer. One
 ``torch.autograd.Function`` call per batch member, or with ``model.packed = True`` one for the whole batch
 (csrc/tmpnn_seqbatch.hip, tmpnn_seqloss_batch_*: the same kernels over the packed rows); the Function's inputs are the module's parameters in state-dict order (W_out
-included), packed once per weight version into one flat slab. Gradients with respect to coordinates are not provided: the
-``augment_eps`` noise is added on the host. The dropout masks come from the library's counter-based generator, keyed per forward from
+included), packed once per weight version into one flat slab. When ``X`` requires grad it is one more input of the Function and the
+backward is the ``_x`` entry (tmpnn_seqloss_backward_x / tmpnn_seqloss_batch_backward_x): ``X.grad`` is dL / dX with the neighbour graph
+and D_max of ``_dist`` held constant (include/tmpnn.h); the ``augment_eps`` noise is added on the host, so torch carries the gradient
+through it to the caller's ``X``. The dropout masks come from the library's counter-based generator, keyed per forward from
 torch's default CPU generator or pinned with ``thermompnn_amd.autograd.dropout_key``; the decoding order is drawn with
 ``torch.randn`` as the reference draws it, or replayed through ``randn=``.
 """
@@ -98,11 +100,32 @@ class SeqInputs:
         return (_ptr(self.X), _ptr(self.S), _ptr(self.mask), _ptr(self.ridx), _ptr(self.cenc), self.L, self.K, _ptr(self.ranks))
 
 
+def _split_x(plan, params):
+    """The Functions' trailing inputs: ProteinMPNN's parameters, then (optionally) the coordinates as they came from the caller ->
+    (params, (shape, dtype) of the coordinates or None)."""
+    if len(params) == len(plan.sizes) + 1:
+        return params[:-1], (tuple(params[-1].shape), params[-1].dtype)
+    return params, None
+
+
+def _x_grad(x_in, dX):
+    """The coordinates' slot of a backward's result: () without that input, else dX in the caller's shape and dtype (or None)."""
+    if x_in is None:
+        return ()
+    return (None if dX is None else dX.view(x_in[0]).to(x_in[1]),)
+
+
+def _wants_dx(X) -> bool:
+    return torch.is_tensor(X) and X.requires_grad and torch.is_grad_enabled()
+
+
 class SeqLossFunction(torch.autograd.Function):
-    """log_probs [L,21] of one protein under ``inp.ranks``, differentiable with respect to ProteinMPNN's parameters."""
+    """log_probs [L,21] of one protein under ``inp.ranks``, differentiable with respect to ProteinMPNN's parameters, and with respect
+    to the coordinates when they follow the parameters as one more input (``inp.X`` holds their values)."""
 
     @staticmethod
     def forward(ctx, plan, inp, p_mpnn, seed, step, *params):
+        params, ctx.x_in = _split_x(plan, params)
         slab = plan.pack(params)
         dev = slab.device
         saved = torch.empty(plan.saved_bytes(inp.L), dtype=torch.uint8, device=dev)
@@ -124,26 +147,34 @@ class SeqLossFunction(torch.autograd.Function):
         dlp = dlp.to(device=dev, dtype=torch.float32).contiguous()
         grads = torch.zeros(plan.numel, dtype=torch.float32, device=dev)
         scratch = plan.scratch(inp.L, dev)
+        dX = torch.empty_like(inp.X) if ctx.x_in is not None and ctx.needs_input_grad[-1] else None
         with torch.cuda.device(dev):
-            check(plan.lib.tmpnn_seqloss_backward(*inp.args(), _ptr(slab), plan.numel, p_mpnn, None, seed, step, _ptr(dlp), _ptr(grads),
-                                                  _ptr(saved), saved.numel(), _ptr(scratch), scratch.numel(), _stream()),
-                  "tmpnn_seqloss_backward")
+            if dX is None:
+                check(plan.lib.tmpnn_seqloss_backward(*inp.args(), _ptr(slab), plan.numel, p_mpnn, None, seed, step, _ptr(dlp), _ptr(grads),
+                                                      _ptr(saved), saved.numel(), _ptr(scratch), scratch.numel(), _stream()),
+                      "tmpnn_seqloss_backward")
+            else:
+                check(plan.lib.tmpnn_seqloss_backward_x(*inp.args(), _ptr(slab), plan.numel, p_mpnn, None, seed, step, _ptr(dlp), _ptr(grads),
+                                                        _ptr(dX), _ptr(saved), saved.numel(), _ptr(scratch), scratch.numel(), _stream()),
+                      "tmpnn_seqloss_backward_x")
         out, off = [], 0
         for i, (shape, n) in enumerate(zip(plan.shapes.values(), plan.sizes)):
             out.append(grads[off:off + n].view(shape) if ctx.needs_input_grad[5 + i] else None)
             off += n
-        return (None,) * 5 + tuple(out)
+        return (None,) * 5 + tuple(out) + _x_grad(ctx.x_in, dX)
 
 
 def sequence_log_probs(plan: SeqPlan, params, X, S, mask, residue_idx, chain_enc, ranks, k_neighbors: int, p_mpnn: float):
-    """log_probs [L,21] of one protein with a graph over ``params`` (ProteinMPNN's parameters in state-dict order)."""
+    """log_probs [L,21] of one protein with a graph over ``params`` (ProteinMPNN's parameters in state-dict order), and over ``X``
+    when it requires grad (dL / dX with the graph and D_max of _dist constant: tmpnn_seqloss_backward_x)."""
     from .autograd import _draw_key
     if params[0].device.type != "cuda":
         raise RuntimeError(_CPU_ERROR)
     dev = params[0].device
     inp = SeqInputs(*(t.to(dev) for t in (X, S, mask, residue_idx, chain_enc, ranks)), k_neighbors)
     seed, step = _draw_key() if p_mpnn > 0 else (0, 0)
-    return SeqLossFunction.apply(plan, inp, float(p_mpnn), seed, step, *params)
+    extra = (X.to(dev),) if _wants_dx(X) else ()          # the coordinates with their graph: one more input of the node
+    return SeqLossFunction.apply(plan, inp, float(p_mpnn), seed, step, *params, *extra)
 
 
 class SeqBatchInputs:
@@ -177,6 +208,7 @@ class SeqBatchFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plan, inp, status, p_mpnn, seed, step, *params):
+        params, ctx.x_in = _split_x(plan, params)
         slab = plan.pack(params)
         dev = slab.device
         need = int(plan.lib.tmpnn_seqloss_batch_saved_bytes(inp.T, inp.n, inp.K))
@@ -202,15 +234,21 @@ class SeqBatchFunction(torch.autograd.Function):
         dlp = dlp.to(device=dev, dtype=torch.float32).contiguous()
         grads = torch.zeros(plan.numel, dtype=torch.float32, device=dev)
         scratch = plan.batch_scratch(inp, dev)
+        dX = torch.empty_like(inp.X) if ctx.x_in is not None and ctx.needs_input_grad[-1] else None
         with torch.cuda.device(dev):
-            check(plan.lib.tmpnn_seqloss_batch_backward(*inp.args(), _ptr(slab), plan.numel, p_mpnn, None, seed, step, _ptr(dlp), _ptr(grads),
-                                                        _ptr(saved), saved.numel(), _ptr(scratch), scratch.numel(), _stream()),
-                  "tmpnn_seqloss_batch_backward")
+            if dX is None:
+                check(plan.lib.tmpnn_seqloss_batch_backward(*inp.args(), _ptr(slab), plan.numel, p_mpnn, None, seed, step, _ptr(dlp),
+                                                            _ptr(grads), _ptr(saved), saved.numel(), _ptr(scratch), scratch.numel(), _stream()),
+                      "tmpnn_seqloss_batch_backward")
+            else:
+                check(plan.lib.tmpnn_seqloss_batch_backward_x(*inp.args(), _ptr(slab), plan.numel, p_mpnn, None, seed, step, _ptr(dlp),
+                                                              _ptr(grads), _ptr(dX), _ptr(saved), saved.numel(), _ptr(scratch),
+                                                              scratch.numel(), _stream()), "tmpnn_seqloss_batch_backward_x")
         out, off = [], 0
         for i, (shape, n) in enumerate(zip(plan.shapes.values(), plan.sizes)):
             out.append(grads[off:off + n].view(shape) if ctx.needs_input_grad[6 + i] else None)
             off += n
-        return (None,) * 6 + tuple(out)
+        return (None,) * 6 + tuple(out) + _x_grad(ctx.x_in, dX)
 
 
 def sequence_log_probs_batch(plan: SeqPlan, params, X, S, mask, residue_idx, chain_enc, ranks, offsets, k_neighbors: int, p_mpnn: float,
@@ -234,7 +272,8 @@ def sequence_log_probs_batch(plan: SeqPlan, params, X, S, mask, residue_idx, cha
     inp = SeqBatchInputs(*(t.to(dev) for t in (X, S, mask, residue_idx, chain_enc, ranks)), offsets, k_neighbors, min_len, max_len)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     seed, step = _draw_key() if p_mpnn > 0 else (0, 0)
-    log_probs = SeqBatchFunction.apply(plan, inp, status, float(p_mpnn), seed, step, *params)
+    extra = (X.to(dev),) if _wants_dx(X) else ()          # the packed coordinates with their graph: one more input of the node
+    log_probs = SeqBatchFunction.apply(plan, inp, status, float(p_mpnn), seed, step, *params, *extra)
     st = int(status.item())
     if st:
         check(plan.lib.tmpnn_status_error(st), "tmpnn_seqloss_batch_forward")

@@ -144,14 +144,27 @@ class TransferModel(_EngineOwner):
             out = ddg if self.subtract_mut else z * self.ddg_out.weight.view(()) + self.ddg_out.bias.view(())
             return out.view(V, L, VOCAB_DIM)
 
-    def sequence_log_probs(self, pdb, chain_M=None, randn=None, packed=False) -> torch.Tensor:
+    def sequence_log_probs(self, pdb, chain_M=None, randn=None, packed=False, X=None) -> torch.Tensor:
         """log p(sequence | structure) of one parsed structure, [L, 21], under the decoding order
         ``decoding_ranks(chain_M * mask, randn)`` (chain_M None: every residue designable; randn None: drawn), with a graph over
         ``prot_mpnn``'s parameters, W_out included (thermompnn_amd/autograd.py). Needs ``differentiable = True``. Together with
         the ddG loss it is two backward passes into the same ``.grad``s. ``packed`` is the switch of
-        ``model_utils.ProteinMPNN.packed``; one structure is a batch of one, which takes the per-protein call either way."""
+        ``model_utils.ProteinMPNN.packed``; one structure is a batch of one, which takes the per-protein call either way.
+        ``X`` [L,4,3], a float tensor on the model's device, replaces the parsed coordinates (sequence, mask, numbering and chains
+        still come from ``pdb``); when it requires grad the graph reaches it: ``X.grad`` is dL / dX with the neighbour graph and
+        D_max of ``_dist`` held constant (include/tmpnn.h). ``X`` needs unfrozen ProteinMPNN parameters."""
         from . import autograd as _autograd
-        return _autograd.transfer_sequence_log_probs(self, pdb, chain_M, randn)
+        return _autograd.transfer_sequence_log_probs(self, pdb, chain_M, randn, X)
+
+    def forward_coords(self, X, pdb, mutations):
+        """The differentiable ``forward`` with ``X`` [L,4,3] (a float tensor on the model's device) in place of the parsed coordinates:
+        the same return value, and when ``X`` requires grad the ddG values carry a graph to it as well (tmpnn_finetune_backward_x;
+        with num_final_layers = 0 the head never reads the structure and ``X.grad`` is zero). Needs ``differentiable = True`` and
+        unfrozen ProteinMPNN parameters; always takes the gradient path's exact fp32 kernels."""
+        from . import autograd as _autograd
+        if not self.differentiable:
+            raise RuntimeError(_autograd._NOT_DIFFERENTIABLE.format("forward_coords"))
+        return _autograd.transfer_forward(self, pdb, mutations, X)
 
     def forward(self, pdb, mutations, tied_feat=True):
         if self.differentiable:
