@@ -7,6 +7,9 @@
 //
 //   python -m thermompnn_amd.weights weights.raw --model_path thermoMPNN_default.pt --vanilla_path v_48_020.pt
 //   scan_native weights.raw out.csv [--chain A] [--threads N] [--precision f16x2|bf16x3|fp32] [--chunk_files N] a.pdb b.pdb ...
+// With --top K [--cutoff X] [--one_per_position] [--include_cys] the output is the ranked hit list instead: the K most stabilising
+// mutations of each protein, selected on the device by tmpnn_select_hits from the table the forward left there (only the hits are
+// copied back), byte-identical to  python -m thermompnn_amd.ssm_scan FILES --chain A --top K ... --out OUT.csv.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -14,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <thread>
 #include <vector>
@@ -100,7 +104,8 @@ std::string pdb_cell(const std::string &path) {
 
 int main(int argc, char **argv) {
     std::string chain = "A", precision;
-    int threads = static_cast<int>(std::max(1u, std::thread::hardware_concurrency())), chunk_files = 256;
+    int threads = static_cast<int>(std::max(1u, std::thread::hardware_concurrency())), chunk_files = 256, top = 0, hit_flags = 0;
+    float cutoff = std::numeric_limits<float>::infinity();
     std::vector<std::string> pos;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -109,9 +114,16 @@ int main(int argc, char **argv) {
         else if (a == "--threads") threads = std::max(1, std::atoi(val()));
         else if (a == "--precision") precision = val();
         else if (a == "--chunk_files") chunk_files = std::max(1, std::atoi(val()));
+        else if (a == "--top") { top = std::atoi(val()); if (top < 1 || top > 256) die("--top: 1 to 256 mutations per protein"); }
+        else if (a == "--cutoff") cutoff = std::strtof(val(), nullptr);
+        else if (a == "--one_per_position") hit_flags |= TMPNN_HITS_ONE_PER_POSITION;
+        else if (a == "--include_cys") hit_flags |= TMPNN_HITS_INCLUDE_CYS;
         else pos.push_back(a);
     }
-    if (pos.size() < 3) die("usage: scan_native WEIGHTS.raw OUT.csv [--chain A] [--threads N] [--precision P] [--chunk_files N] FILE.pdb ...");
+    if (pos.size() < 3)
+        die("usage: scan_native WEIGHTS.raw OUT.csv [--chain A] [--threads N] [--precision P] [--chunk_files N] [--top K [--cutoff X] "
+            "[--one_per_position] [--include_cys]] FILE.pdb ...");
+    if (!top && (hit_flags || cutoff != std::numeric_limits<float>::infinity())) die("--cutoff, --one_per_position and --include_cys belong to --top K");
     const std::vector<std::string> files(pos.begin() + 2, pos.end());
 
     hipStream_t st;
@@ -128,7 +140,14 @@ int main(int argc, char **argv) {
     tmpnn_weights_t *w = make_handle(raw, precision.empty() ? nullptr : precision.c_str(), st), *w_retry = nullptr;
 
     tmpnn_csv_t *csv = nullptr;
-    tm_ok(tmpnn_csv_open(pos[1].c_str(), 0, &csv), "tmpnn_csv_open");
+    FILE *hits = nullptr;                                                  // --top: the hit list, written here row by row
+    long long hit_rows = 0;
+    if (top) {
+        if (!(hits = std::fopen(pos[1].c_str(), "wb"))) die("cannot open " + pos[1]);
+        std::fputs(",Model,Dataset,ddG_pred,position,wildtype,mutation,rank,pdb\n", hits);
+    } else {
+        tm_ok(tmpnn_csv_open(pos[1].c_str(), 0, &csv), "tmpnn_csv_open");
+    }
 
     for (size_t first = 0; first < files.size(); first += chunk_files) {
         const int n = static_cast<int>(std::min<size_t>(chunk_files, files.size() - first));
@@ -158,7 +177,7 @@ int main(int argc, char **argv) {
             if (T == 0) { h_status = 0; return; }
             tm_ok(tmpnn_ssm_forward(handle, dX, dS, dmask, dri, dce, doff, n, T, max_len, 48, dtab, nullptr, nullptr, nullptr,
                                     d_status, ws, ws_bytes, st), "tmpnn_ssm_forward");
-            hip_ok(hipMemcpyAsync(htab, dtab, T * 84, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+            if (!top) hip_ok(hipMemcpyAsync(htab, dtab, T * 84, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");      // (--top: the table stays)
             hip_ok(hipMemcpyAsync(&h_status, d_status, 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
             hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize");
         };
@@ -177,8 +196,36 @@ int main(int argc, char **argv) {
             names[i] = cells[i].c_str();
             seqs[i] = tmpnn_pdb_seq(pdb[i]);
         }
-        tm_ok(tmpnn_csv_write_ssm(csv, htab, 21, hoff, n, seqs.data(), nullptr, names.data(), nullptr, "ThermoMPNN", "custom", nullptr, nullptr,
-                                  0, threads), "tmpnn_csv_write_ssm");
+        if (top) {
+            // the table is still in dtab and S (a gap is 20) in dS: select there, copy back [n, top] hits
+            const size_t hb = tmpnn_hits_workspace_bytes(T, n, top), nk = static_cast<size_t>(n) * top;
+            char *hws = dev_alloc<char>(hb);
+            float *dv = dev_alloc<float>(nk);
+            int32_t *dp = dev_alloc<int32_t>(nk), *da = dev_alloc<int32_t>(nk), *dc = dev_alloc<int32_t>(n);
+            tm_ok(tmpnn_select_hits(dtab, 21, dS, doff, n, T, top, cutoff, hit_flags, dv, dp, da, dc, hws, hb, st), "tmpnn_select_hits");
+            std::vector<float> hv(nk);
+            std::vector<int32_t> hp(nk), ha(nk), hc(n);
+            auto d2h = [&](void *h, const void *d, size_t b) { hip_ok(hipMemcpyAsync(h, d, b, hipMemcpyDeviceToHost, st), "hipMemcpyAsync"); };
+            d2h(hv.data(), dv, nk * 4); d2h(hp.data(), dp, nk * 4); d2h(ha.data(), da, nk * 4); d2h(hc.data(), dc, n * 4);
+            hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize");
+            char num[32];
+            for (int i = 0; i < n; ++i) {
+                if (hc[i] < 0) die(files[first + i] + ": longer than 8192 residues");
+                if (std::strpbrk(names[i], ",\"\r\n")) die(files[first + i] + ": a name that needs CSV quoting (not written by this example)");
+                for (int r = 0; r < hc[i]; ++r) {
+                    const size_t o = static_cast<size_t>(i) * top + r;
+                    tmpnn_csv_format_double(static_cast<double>(hv[o]), num);
+                    std::fprintf(hits, "%lld,ThermoMPNN,custom,%s,%d,%c,%c,%d,%s\n", hit_rows++, num, hp[o], seqs[i][hp[o]],
+                                 "ACDEFGHIKLMNPQRSTVWY"[ha[o]], r, names[i]);
+                }
+            }
+            for (void *p : {static_cast<void *>(hws), static_cast<void *>(dv), static_cast<void *>(dp), static_cast<void *>(da),
+                            static_cast<void *>(dc)})
+                hip_ok(hipFree(p), "hipFree");
+        } else {
+            tm_ok(tmpnn_csv_write_ssm(csv, htab, 21, hoff, n, seqs.data(), nullptr, names.data(), nullptr, "ThermoMPNN", "custom", nullptr, nullptr,
+                                      0, threads), "tmpnn_csv_write_ssm");
+        }
         for (tmpnn_pdb_t *p : pdb) tmpnn_pdb_free(p);
         for (void *p : {static_cast<void *>(dX), static_cast<void *>(dmask), static_cast<void *>(dtab), static_cast<void *>(dS),
                         static_cast<void *>(dri), static_cast<void *>(dce), static_cast<void *>(doff), static_cast<void *>(ws)})
@@ -188,7 +235,13 @@ int main(int argc, char **argv) {
             hip_ok(hipHostFree(p), "hipHostFree");
     }
     int64_t rows = 0, bytes = 0;
-    tm_ok(tmpnn_csv_close(csv, &rows, &bytes), "tmpnn_csv_close");
+    if (top) {
+        rows = hit_rows;
+        bytes = std::ftell(hits);
+        if (std::fclose(hits) != 0) die("cannot write " + pos[1]);
+    } else {
+        tm_ok(tmpnn_csv_close(csv, &rows, &bytes), "tmpnn_csv_close");
+    }
     std::printf("%lld rows, %lld bytes -> %s\n", static_cast<long long>(rows), static_cast<long long>(bytes), pos[1].c_str());
     tmpnn_weights_destroy(w);
     if (w_retry) tmpnn_weights_destroy(w_retry);

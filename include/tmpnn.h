@@ -578,6 +578,31 @@ int tmpnn_sample_tied_each(const tmpnn_weights_t *w, const void *ctx, size_t ctx
                            const float *pssm_keep_opt, int32_t *S_out, float *probs_opt, int32_t *status_opt, void *workspace,
                            size_t workspace_bytes, tmpnn_stream_t stream);
 
+/* ---- ranked hit lists: the k most stabilising substitutions of every protein, selected on the device -----------------------------
+ * What retrieve_best_mutants + a sort of the frame would give (analysis/SSM.py:32-42,153-166), without moving a [T,21] table to the
+ * host. ddg [T, ld] (ld >= 20; the table of tmpnn_ssm_forward has ld = 21), S [T] (the residue's own letter; >= 20 or negative = no
+ * residue or 'X'), offsets [n_proteins + 1]. A CANDIDATE of protein b is (local position p, letter a < 20) at row t = offsets[b] + p with
+ * S[t] < 20, a != S[t], ddg[t, a] not NaN, a != cysteine (letter 1) unless TMPNN_HITS_INCLUDE_CYS, and ddg[t, a] <= cutoff (+inf
+ * removes no candidate; a NaN cutoff is TMPNN_E_INVALID). With TMPNN_HITS_ONE_PER_POSITION every position first keeps only its best
+ * candidate (the first minimum, as idxmin). The hits of b are its first min(k, #candidates) candidates in ascending (value, position,
+ * letter) order; values compare as fp32 numbers with -0.0 taken as +0.0, +-inf are ordinary values. Every key is distinct: the result
+ * is unique, and a protein's hits do not depend on the batch, on n_proteins or on the launch shape. No float arithmetic, no atomics:
+ * reruns give identical bits.
+ * Outputs: hit_ddg [n_proteins, k] = the table's own bits (a -0.0 stays -0.0), padded with NaN; hit_pos [n_proteins, k] the local
+ * position, hit_aa [n_proteins, k] the letter, both padded with -1; hit_count [n_proteins]. 1 <= k <= 256 (TMPNN_E_INVALID outside);
+ * every protein <= 8192 residues, the forward's own bound. The lengths live in device memory, so the host cannot check them: a longer
+ * protein gets hit_count = -1 and padding only, never an access outside the buffers (offsets are clamped into [0, T]).
+ * Two launches on `stream`: (protein, block of 256 residues) sorts its candidates' 64-bit keys in LDS and leaves its first k in the
+ * workspace; one workgroup per protein sorts the <= 32 blocks' leaders and decodes the first k. tmpnn_hits_workspace_bytes: the
+ * workspace, ((T >> 8) + n_proteins) * k keys of 8 bytes; 0 for sizes that are not served (T < 0 or > 2^31 - 1, n_proteins < 1, k
+ * outside [1, 256]). n_proteins == 0 is a no-op. Errors before any launch: null pointer, k, ld < 20, negative sizes, unknown flag
+ * bits, NaN cutoff -> TMPNN_E_INVALID; T > 2^31 - 1 -> TMPNN_E_UNSUPPORTED; a short workspace -> TMPNN_E_WORKSPACE. */
+enum { TMPNN_HITS_INCLUDE_CYS = 1, TMPNN_HITS_ONE_PER_POSITION = 2 };
+size_t tmpnn_hits_workspace_bytes(int64_t T, int n_proteins, int k);
+int tmpnn_select_hits(const float *ddg, int ld, const int32_t *S, const int32_t *offsets, int n_proteins, int64_t T, int k,
+                      float cutoff, int flags, float *hit_ddg, int32_t *hit_pos, int32_t *hit_aa, int32_t *hit_count,
+                      void *workspace, size_t workspace_bytes, tmpnn_stream_t stream);
+
 /* ---- host side: native PDB reader + packer ------------------------------------------
  * Replaces alt_parse_PDB (protein_mpnn_utils.py:183-350) + the packing of tied_featurize (:353-605) for one
  * structure: one pass over the file, all requested chains. `chains` = string of one-letter chain ids in the

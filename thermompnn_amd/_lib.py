@@ -96,6 +96,8 @@ SIGNATURES = {
                                           C.c_uint64, _p, _p, _p, _sz, _p, _sz, _p]),
     "tmpnn_seqloss_batch_backward_x": (_i, [_p, _p, _p, _p, _p, _p, _i, _i64, _i, _i, _i, _p, _p, _i64, C.c_float, _p, C.c_uint64,
                                             C.c_uint64, _p, _p, _p, _p, _sz, _p, _sz, _p]),
+    "tmpnn_hits_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "tmpnn_select_hits": (_i, [_p, _i, _p, _p, _i, _i64, _i, C.c_float, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "tmpnn_pdb_parse": (_i, [C.c_char_p, C.c_char_p, C.POINTER(_p)]),
     "tmpnn_pdb_parse_batch": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, _i, C.POINTER(_p)]),
     "tmpnn_pdb_parse_batch_status": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, _i, C.POINTER(_p), _p]),
@@ -147,6 +149,8 @@ DEBUG_SIGNATURES = {
 PRECISIONS = ("f16x2", "bf16x3", "fp32")
 STATUS_RANGE, STATUS_MAXLEN, STATUS_SELFTEST = 1, 2, 4
 E_RANGE = -5
+HITS_INCLUDE_CYS, HITS_ONE_PER_POSITION = 1, 2        # flags of tmpnn_select_hits
+HITS_MAX_K, HITS_MAX_LEN = 256, 8192
 
 
 class TmpnnError(RuntimeError):

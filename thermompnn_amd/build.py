@@ -16,7 +16,7 @@ LIB = os.path.join(HERE, "libtmpnn.so")
 DEBUG_LIB = os.path.join(HERE, "libtmpnn_debug.so")
 SOURCES = ["tmpnn_api.hip", "tmpnn_graph.hip", "tmpnn_graph_ca.hip", "tmpnn_layers.hip", "tmpnn_head.hip", "tmpnn_split.hip", "tmpnn_edge.hip", "tmpnn_msg.hip",
            "tmpnn_edge_msg.hip", "tmpnn_node.hip", "tmpnn_variants.hip", "tmpnn_sample.hip", "tmpnn_train.hip", "tmpnn_finetune.hip", "tmpnn_seqbatch.hip",
-           "tmpnn_coordgrad.hip",
+           "tmpnn_coordgrad.hip", "tmpnn_hits.hip",
            "tmpnn_pdb.cpp", "tmpnn_csv.cpp"]
 HEADERS = ["tmpnn_common.h", "tmpnn_split.h", "tmpnn_internal.h", "tmpnn_head_body.h", "tmpnn_ft.h", os.path.join("..", "..", "include", "tmpnn.h"),
            os.path.join("..", "..", "include", "tmpnn_debug.h"), "tmpnn_host_guard.hpp"]

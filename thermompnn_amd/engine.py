@@ -381,6 +381,49 @@ class Engine:
         range_retry(run, precision or self.precision, self.retry_precision, "ssm_forward")
         return res
 
+    # -- ranked hit lists ------------------------------------------------------------------------------
+    def select_hits(self, ddg, S, offsets, k: int, cutoff: Optional[float] = None, include_cys: bool = False,
+                    one_per_position: bool = False) -> Dict[str, torch.Tensor]:
+        """The ``k`` most stabilising substitutions of every protein of a packed table that is already on the device
+        (tmpnn_select_hits: two launches, no table leaves the GPU): ``ddg`` [T, ld >= 20] float32 (``ssm_forward``'s table, rows of a
+        scan's ``device_table``), ``S`` [T] the residues' own letters (>= 20: no residue), ``offsets`` [P + 1]. A candidate is a
+        substitution a != S[t] of a residue with S[t] < 20 whose value is not NaN and <= ``cutoff`` (None: +inf), cysteine only with
+        ``include_cys``; ``one_per_position`` first keeps each position's best candidate. -> dict(hit_ddg [P, k] padded with NaN,
+        hit_pos [P, k] local positions and hit_aa [P, k] padded with -1, hit_count [P]) on the device, best first: ascending (value,
+        position, letter), -0.0 taken as +0.0. 1 <= k <= 256; every protein <= 8192 residues."""
+        if not isinstance(ddg, torch.Tensor) or not ddg.is_cuda or ddg.dtype != torch.float32 or ddg.dim() != 2:
+            raise TmpnnError("select_hits: ddg must be a float32 [T, ld] tensor on the device (the table stays there; there is no CPU path)")
+        if ddg.shape[0] > 0 and (ddg.stride(1) != 1 or ddg.stride(0) < ddg.shape[1]):
+            ddg = ddg.contiguous()
+        T, ld = int(ddg.shape[0]), int(ddg.stride(0)) if ddg.shape[0] > 0 else int(ddg.shape[1])
+        if not 1 <= int(k) <= _lib.HITS_MAX_K:
+            raise TmpnnError(f"select_hits: k={k} outside [1, {_lib.HITS_MAX_K}]")
+        cut = float("inf") if cutoff is None else float(cutoff)
+        if cut != cut:
+            raise TmpnnError("select_hits: the cutoff is NaN")
+        longest = self._max_len(offsets, None)
+        if longest > _lib.HITS_MAX_LEN:
+            raise TmpnnError(f"select_hits: a protein of {longest} residues exceeds {_lib.HITS_MAX_LEN}, the forward's own bound")
+        S, offsets = self._i32(S), self._i32(offsets)
+        P = offsets.numel() - 1
+        if S.numel() != T or P < 0:
+            raise TmpnnError(f"select_hits: S has {S.numel()} entries for a table of {T} rows, offsets {offsets.numel()}")
+        dev, k = self.device, int(k)
+        res = dict(hit_ddg=torch.empty((P, k), dtype=torch.float32, device=dev), hit_pos=torch.empty((P, k), dtype=torch.int32, device=dev),
+                   hit_aa=torch.empty((P, k), dtype=torch.int32, device=dev), hit_count=torch.empty(P, dtype=torch.int32, device=dev))
+        if P == 0:
+            return res
+        need = self.lib.tmpnn_hits_workspace_bytes(T, P, k)
+        if need == 0:
+            raise TmpnnError(f"select_hits: sizes not served (T={T}, P={P}, k={k})")
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)       # (its own buffer: a scan's writer thread may call this beside a forward)
+        flags = (_lib.HITS_INCLUDE_CYS if include_cys else 0) | (_lib.HITS_ONE_PER_POSITION if one_per_position else 0)
+        with torch.cuda.device(dev):
+            check(self.lib.tmpnn_select_hits(_ptr(ddg), ld, _ptr(S), _ptr(offsets), P, T, k, cut, flags, _ptr(res["hit_ddg"]),
+                                             _ptr(res["hit_pos"]), _ptr(res["hit_aa"]), _ptr(res["hit_count"]), _ptr(ws), ws.numel(),
+                                             _stream()), "tmpnn_select_hits")
+        return res
+
     # -- many sequence variants over one backbone ----------------------------------------------------
     def encode(self, X, mask, residue_idx, chain_enc, offsets, max_len: Optional[int] = None,
                precision: Optional[str] = None) -> "EncodedBackbone":

@@ -14,11 +14,15 @@ are sharded over the N GPUs (dist.scan_files: LPT partition, the same pipeline p
 which writes); a plain ``python -m thermompnn_amd.ssm_scan`` streams chunk after chunk into the output file.
   --mutations FILE   CSV with columns pdb,position,mutation (0-based position into the parsed sequence): only the listed
                      mutants are written (BASELINE config 4: an explicit list over many proteins)
+  --top K [--cutoff X] [--one_per_position]   a ranked hit list instead of the full listing: the K (<= 256) most stabilising
+                     mutations of each protein, selected on the GPU from tables that never leave it (Engine.select_hits), written
+                     with the columns HIT_COLUMNS; single rank, no centrality column, proteins of at most 8192 residues
 """
 from __future__ import annotations
 
 import argparse
 import csv
+import os
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -145,13 +149,111 @@ def write_scan_npz(path: str, res: dict) -> None:
                  seqs=np.array(res["seqs"]), **extra)
 
 
+HIT_COLUMNS = ["Model", "Dataset", "ddG_pred", "position", "wildtype", "mutation", "rank", "pdb"]
+
+
+def hits_refusal(top, pick_best: bool = False, centrality: bool = False, out: str = "", world: int = 1) -> Optional[str]:
+    """Why a ranked hit list (``top``) cannot be combined with the other options of a scan, or None."""
+    if top is None:
+        return None
+    if not 1 <= int(top) <= 256:
+        return f"--top {top}: a hit list holds 1 to 256 mutations per protein"
+    if pick_best:
+        return "--top with --pick_best: a hit list is already a selection (use --one_per_position for one hit per position)"
+    if centrality:
+        return "--top with --centrality: a hit list has no 'neighbors' column"
+    if out.endswith(".npz"):
+        return "--top with an .npz output: a hit list is written as CSV (name the output *.csv)"
+    if world > 1:
+        return "--top in a multi-rank run: the hit list is selected on one GPU (run without the launcher)"
+    return None
+
+
+def sequence_letters(seqs: Sequence[str]) -> np.ndarray:
+    """S [T] of a scan, rebuilt from the parsed sequences: ALPHABET index, '-' (no residue) and anything unknown -> 20."""
+    lut = np.full(256, 20, np.int32)
+    for i, c in enumerate(AA20):
+        lut[ord(c)] = i
+    return lut[np.frombuffer("".join(seqs).encode("latin-1"), dtype=np.uint8)] if seqs else np.zeros(0, np.int32)
+
+
+def write_hits_csv(path: str, hits: dict, seqs: Sequence[str], names: Sequence[str], model_name: str = "ThermoMPNN",
+                   dataset: str = "custom") -> int:
+    """Hit lists (host arrays hit_ddg / hit_pos / hit_aa [P, k], hit_count [P]) -> CSV with a running index, proteins in the given
+    order, ``rank`` from 0 per protein, floats as repr(float(v)), '\\n' line ends. -> rows written."""
+    n = 0
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh, lineterminator="\n")
+        w.writerow([""] + HIT_COLUMNS)
+        for b, (seq, name) in enumerate(zip(seqs, names)):
+            pdb = name.strip(".pdb")
+            for r in range(int(hits["hit_count"][b])):
+                pos, a = int(hits["hit_pos"][b, r]), int(hits["hit_aa"][b, r])
+                w.writerow([n, model_name, dataset, repr(float(hits["hit_ddg"][b, r])), pos, seq[pos], AA20[a], r, pdb])
+                n += 1
+    return n
+
+
+def _scan_hits_to_file(engine, paths, chains, out, model_name, dataset, include_cys, top, cutoff, one_per_position, pipeline_kw):
+    """The ``top`` form of ``scan_to_file``: the pipeline fills ONE device table (a chunk the range retry reruns writes its rows of
+    it again), then one selection over the whole table; only the hits are copied back."""
+    import ctypes as C
+    from . import _lib, pipeline
+    from .native_pdb import _chains_arg
+    lib, n = _lib.load(), len(paths)
+    total = 0
+    if n:                                  # lengths first (the device table is allocated once): a parse without the fill
+        cp = (C.c_char_p * n)(*[os.fsencode(p) for p in paths])
+        cc = (C.c_char_p * n)(*[_chains_arg(c) for c in chains])
+        hs = (C.c_void_p * n)()
+        _lib.check(lib.tmpnn_pdb_parse_batch(cp, cc, n, pipeline_kw.get("parse_threads") or max(1, pipeline.usable_cpus() - 2), hs),
+                   "tmpnn_pdb_parse_batch")
+        for i in range(n):
+            total += lib.tmpnn_pdb_length(C.c_void_p(hs[i]))
+            lib.tmpnn_pdb_free(C.c_void_p(hs[i]))
+    table = torch.empty((total, 21), dtype=torch.float32, device=engine.device)
+    seqs, names, lens = [], [], []
+
+    def sink(ch):
+        seqs.extend(ch.seqs())
+        names.extend(ch.names)
+        lens.extend(int(x) for x in np.diff(ch.offsets))
+
+    stats = pipeline.scan_files(engine, paths, chains, sink, device_table=table, **pipeline_kw)
+    t0 = _now()
+    if sum(lens) != total:
+        raise RuntimeError("a file changed between the length pre-pass and the scan")
+    offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    with torch.cuda.device(engine.device):
+        res = engine.select_hits(table, sequence_letters(seqs), offsets, top, cutoff=cutoff, include_cys=include_cys,
+                                 one_per_position=one_per_position)
+        hits = {k: v.cpu().numpy() for k, v in res.items()}
+    rows = write_hits_csv(out, hits, seqs, names, model_name, dataset)
+    stats.sink_s += _now() - t0
+    stats.wall_s += _now() - t0
+    return rows, stats
+
+
 def scan_to_file(engine, paths: Sequence[str], chains: Sequence, out: str, model_name: str = "ThermoMPNN",
                  dataset: str = "custom", pick_best: bool = False, include_cys: bool = False, centrality: bool = False,
-                 n_threads: int = 0, **pipeline_kw):
+                 n_threads: int = 0, top: Optional[int] = None, cutoff: Optional[float] = None, one_per_position: bool = False,
+                 **pipeline_kw):
     """Single-GPU streaming form: PDB files -> ``out`` (``.npz``: binary tables; anything else: the reference's CSV layout)
     with parse(k+1) || forward(k) || write(k-1) — a chunk's rows are formatted and written while the GPU works on the next
-    chunk, and nothing but the current chunks is held in memory. -> (rows or residues written, pipeline.ScanStats)."""
+    chunk, and nothing but the current chunks is held in memory. -> (rows or residues written, pipeline.ScanStats).
+    ``top`` = k: a ranked hit list instead — the tables stay on the device (84 bytes per residue of the whole scan), the k best
+    substitutions of every protein are selected there (``Engine.select_hits``; ``cutoff``, ``include_cys``, ``one_per_position`` as
+    there) and written as CSV with the columns ``HIT_COLUMNS``; single rank, no centrality column, at most 8192 residues per protein."""
     from . import native_csv, pipeline
+    if top is not None or cutoff is not None or one_per_position:
+        if top is None:
+            raise ValueError("cutoff / one_per_position select a hit list: pass top=k as well")
+        world = torch.distributed.get_world_size() if torch.distributed.is_available() and torch.distributed.is_initialized() else 1
+        why = hits_refusal(top, pick_best, centrality, out, world)
+        if why:
+            raise ValueError(why)
+        return _scan_hits_to_file(engine, paths, list(chains), out, model_name, dataset, include_cys, int(top), cutoff, one_per_position,
+                                  pipeline_kw)
     if out.endswith(".npz"):
         acc = dict(t=[], nb=[], lens=[], seqs=[], names=[])
 
@@ -254,6 +356,10 @@ def main(argv=None):
     ap.add_argument("--include_cys", action="store_true", default=False, help="Include cysteine as potential mutation option.")
     ap.add_argument("--centrality", action="store_true", default=False, help="Calculate centrality value for each residue (# neighbors).")
     ap.add_argument("--mutations", default="", help="CSV (pdb,position,mutation): write only these mutants")
+    ap.add_argument("--top", type=int, default=None, metavar="K",
+                    help="write a ranked hit list instead: the K (1..256) most stabilising mutations of each protein, selected on the GPU")
+    ap.add_argument("--cutoff", type=float, default=None, help="with --top: keep only mutations with ddG_pred <= this value")
+    ap.add_argument("--one_per_position", action="store_true", default=False, help="with --top: at most one hit per position (its best)")
     ap.add_argument("--precision", default=None, choices=["f16x2", "bf16x3", "fp32"])
     ap.add_argument("--chunk_files", type=int, default=96, help="files per pipeline chunk (parse || forward || write overlap)")
     ap.add_argument("--device_tables", action="store_true", default=False,
@@ -263,6 +369,13 @@ def main(argv=None):
                     help="read --model_path with the unrestricted pickle loader (it can execute code from the file); the default "
                          "restricted loader already reads Lightning checkpoints such as thermoMPNN_default.pt")
     args = ap.parse_args(argv)
+    if args.top is None and (args.cutoff is not None or args.one_per_position):
+        ap.error("--cutoff and --one_per_position belong to a hit list: give --top K as well")
+    why = hits_refusal(args.top, args.pick_best, args.centrality, args.out, int(os.environ.get("WORLD_SIZE", "1")))
+    if why is None and args.top is not None and args.mutations:
+        why = "--top with --mutations: an explicit mutation list is not ranked"
+    if why:
+        ap.error(why)
 
     from . import dist as tdist
     from .custom_inference import load_model
@@ -275,7 +388,8 @@ def main(argv=None):
         if world == 1 and not args.mutations:
             # one GPU: stream chunks straight into the output while the next ones are parsed and computed
             n_rows, stats = scan_to_file(engine, args.pdbs, chains, args.out, "ThermoMPNN", args.dataset_name, args.pick_best,
-                                         args.include_cys, args.centrality, chunk_files=args.chunk_files)
+                                         args.include_cys, args.centrality, chunk_files=args.chunk_files, top=args.top,
+                                         cutoff=args.cutoff, one_per_position=args.one_per_position)
             n_prot = stats.files
         elif not args.mutations and not args.out.endswith(".npz"):
             # N GPUs -> CSV: every rank formats its own LPT shard with the final running indices, the ranks exchange byte counts and

@@ -108,6 +108,26 @@ class TransferModel(_EngineOwner):
                 ddg, z = res["ddg"], eng.ddg_head(res["hidden"][2], res["hidden"][1], S[0], want_z=True)[1]
             return ddg if self.subtract_mut else z * self.ddg_out.weight.view(()) + self.ddg_out.bias.view(())
 
+    def hit_list(self, pdb, k: int, cutoff=None, include_cys: bool = False, one_per_position: bool = False):
+        """The ``k`` most stabilising substitutions of one parsed structure, best first, as ``Mutation(position, wildtype, mutation,
+        ddG, pdb)`` (ddG a Python float): ONE fused forward (``ssm_table``) and ONE selection on the device
+        (``Engine.select_hits``); only the hits are copied back. Positions without a residue ('-') and 'X' have no candidates;
+        ``cutoff`` keeps substitutions with ddG <= cutoff; cysteine only with ``include_cys``; ``one_per_position`` keeps each
+        position's best substitution first (retrieve_best_mutants, analysis/SSM.py:32-42)."""
+        from .datasets import Mutation
+        entry = pdb[0] if isinstance(pdb, (list, tuple)) else pdb
+        seq = entry["seq"]
+        table = self.ssm_table(pdb)
+        eng = self.engine()
+        S = torch.tensor([_AA_INDEX[c] if c in _AA_INDEX and c != "X" else 20 for c in seq], dtype=torch.int32)
+        with torch.cuda.device(eng.device):
+            res = eng.select_hits(table, S, torch.tensor([0, len(seq)], dtype=torch.int32), k, cutoff=cutoff, include_cys=include_cys,
+                                  one_per_position=one_per_position)
+            n = int(res["hit_count"][0])
+            val, pos, aa = res["hit_ddg"][0, :n].cpu().numpy(), res["hit_pos"][0, :n].cpu().numpy(), res["hit_aa"][0, :n].cpu().numpy()
+        name = entry.get("name", "")
+        return [Mutation(int(p), seq[int(p)], ALPHABET[int(a)], float(v), name) for v, p, a in zip(val, pos, aa)]
+
     def variant_tables(self, pdb, variants) -> torch.Tensor:
         """``ssm_table`` of the same backbone under V other sequences, [V, L, 21] on the model's device: the encoder runs once, the
         decoder and the head once per variant (Engine.encode + Engine.decode_variants). A variant is a full one-letter sequence of
