@@ -1,5 +1,6 @@
 """The contract of tmpnn_select_hits (include/tmpnn.h) restated in numpy: the candidate rule, then np.lexsort((aa, pos, value + 0.0)).
-Shared by tests/test_hits_host.py and tests/test_gpu_hits.py; every device comparison against it is exact."""
+Shared by tests/test_hits_host.py, tests/test_gpu_hits.py and tests/test_gpu_hits_network.py; every device comparison against it is
+exact."""
 import numpy as np
 
 CYS = 1          # 'C' in ACDEFGHIKLMNPQRSTVWYX
@@ -25,7 +26,8 @@ def hits_reference(table, S, offsets, k, cutoff=None, include_cys=False, one_per
         if not include_cys:
             ok &= aa != CYS
         if one_per_position:                         # the first minimum of each position, as idxmin (NaN never wins)
-            w = np.where(ok, v.astype(np.float64), np.inf)
+            with np.errstate(invalid="ignore"):      # (a signalling NaN in the table: the cast quiets it, `ok` keeps it out)
+                w = np.where(ok, v.astype(np.float64), np.inf)
             first = ok & (w == w.min(axis=1, keepdims=True))      # the minimum's places among the candidates (+inf may be one)
             keep = np.zeros_like(ok)
             keep[np.arange(t1 - t0), np.argmax(first, axis=1)] = True

@@ -413,6 +413,12 @@ class Engine:
                    hit_aa=torch.empty((P, k), dtype=torch.int32, device=dev), hit_count=torch.empty(P, dtype=torch.int32, device=dev))
         if P == 0:
             return res
+        if T == 0:                                                  # proteins without a row: padding, no launch (an empty table has no address)
+            res["hit_ddg"].fill_(float("nan"))
+            res["hit_pos"].fill_(-1)
+            res["hit_aa"].fill_(-1)
+            res["hit_count"].zero_()
+            return res
         need = self.lib.tmpnn_hits_workspace_bytes(T, P, k)
         if need == 0:
             raise TmpnnError(f"select_hits: sizes not served (T={T}, P={P}, k={k})")
