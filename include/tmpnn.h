@@ -603,6 +603,39 @@ int tmpnn_select_hits(const float *ddg, int ld, const int32_t *S, const int32_t 
                       float cutoff, int flags, float *hit_ddg, int32_t *hit_pos, int32_t *hit_aa, int32_t *hit_count,
                       void *workspace, size_t workspace_bytes, tmpnn_stream_t stream);
 
+/* ---- streaming hit lists over variant tables: the k smallest of base[v] + ddg[v, q, b], carried from call to call ----------------
+ * For selections whose table is too large to exist, such as all double mutants of a protein ([P, 20, L, 20]): decode a chunk of
+ * variants (tmpnn_decode_variants), reduce it to k keys while it is hot, pass the k keys on to the next chunk. One call takes V
+ * variants of ONE protein of L rows: ddg [V, L, ld] (ld >= 20; relative to the variant's own residue), S_var [V, L], and per variant,
+ * on the device, base [V] (fp32), tag [V] and skip [V] (int32; skip -1 = none). A CANDIDATE is (v, q, b) with 0 <= tag[v] <= 65535,
+ * S_var[v, q] < 20 (unsigned compare: negative = no residue), b < 20, b != S_var[v, q], q != skip[v] (q > skip[v] with
+ * TMPNN_VHITS_UPPER), b != cysteine (letter 1) unless TMPNN_VHITS_INCLUDE_CYS, and a value that is not NaN and <= cutoff (+inf
+ * removes no candidate). The VALUE is base[v] + ddg[v, q, b]: one IEEE fp32 round-to-nearest add, the only float operation
+ * (+inf + -inf is NaN: no candidate; a variant whose tag is out of range or whose base is NaN contributes nothing). Its 64-bit KEY
+ * is the order-preserving image of the sum's bits (-0.0 taken as +0.0; tmpnn_select_hits's) in the high word and
+ * tag << 16 | q << 5 | b in the low word, so L <= 2048; ascending keys are ascending (value, tag, position, letter), and all ones
+ * means "none". For double mutants tag = p * 32 + a: 11 + 5 + 11 + 5 bits.
+ * STATE: `state` [k], 64-bit keys, owned by the caller, on the device. Without TMPNN_VHITS_CONTINUE the call selects from its own
+ * variants; with it the k keys in `state` (left by earlier calls with the same k, padded with all ones) take part. After the call
+ * `state` holds the k smallest keys of everything seen, ascending. The caller promises distinct tags over all calls of one
+ * selection: every key is then distinct, the result is unique and does not depend on how the variants were cut into calls, on the
+ * order of the calls, on V or on the launch shape. No atomics: reruns give identical bits.
+ * Outputs, decoded from the state by every call: hit_ddg [k] = the sum's bits recovered from the key (a -0.0 sum is reported as
+ * +0.0), padded with NaN; hit_tag, hit_pos, hit_aa [k] padded with -1; hit_count [1].
+ * Two launches on `stream`: min(items, 8192 / m - 1) workgroups (m = the power of two >= k, an item = a variant's block of 256
+ * residues) each keep their m leaders in LDS over the items they loop over and leave k of them in the workspace; one workgroup
+ * merges these with the state and decodes. V == 0 or L == 0 launches the merge only (the input pointers may then be NULL): with
+ * CONTINUE the state is kept and decoded, without it the state becomes empty, the outputs padding and hit_count 0.
+ * tmpnn_variant_hits_workspace_bytes: min(items, 8192 / m - 1) * k keys of 8 bytes; 0 for sizes that are not served. Errors before
+ * any launch: null pointer, k outside [1, 256], ld < 20, negative sizes, unknown flag bits, NaN cutoff -> TMPNN_E_INVALID; L > 2048
+ * or V * L > 2^31 - 1 -> TMPNN_E_UNSUPPORTED; a short workspace -> TMPNN_E_WORKSPACE. */
+enum { TMPNN_VHITS_INCLUDE_CYS = 1, TMPNN_VHITS_UPPER = 2, TMPNN_VHITS_CONTINUE = 4 };
+size_t tmpnn_variant_hits_workspace_bytes(int64_t V, int64_t L, int k);   /* 0 for sizes not served */
+int tmpnn_select_variant_hits(const float *ddg, int ld, const int32_t *S_var, const float *base, const int32_t *tag,
+                              const int32_t *skip, int64_t V, int64_t L, int k, float cutoff, int flags,
+                              uint64_t *state, float *hit_ddg, int32_t *hit_tag, int32_t *hit_pos, int32_t *hit_aa,
+                              int32_t *hit_count, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream);
+
 /* ---- host side: native PDB reader + packer ------------------------------------------
  * Replaces alt_parse_PDB (protein_mpnn_utils.py:183-350) + the packing of tied_featurize (:353-605) for one
  * structure: one pass over the file, all requested chains. `chains` = string of one-letter chain ids in the

@@ -16,9 +16,9 @@ LIB = os.path.join(HERE, "libtmpnn.so")
 DEBUG_LIB = os.path.join(HERE, "libtmpnn_debug.so")
 SOURCES = ["tmpnn_api.hip", "tmpnn_graph.hip", "tmpnn_graph_ca.hip", "tmpnn_layers.hip", "tmpnn_head.hip", "tmpnn_split.hip", "tmpnn_edge.hip", "tmpnn_msg.hip",
            "tmpnn_edge_msg.hip", "tmpnn_node.hip", "tmpnn_variants.hip", "tmpnn_sample.hip", "tmpnn_train.hip", "tmpnn_finetune.hip", "tmpnn_seqbatch.hip",
-           "tmpnn_coordgrad.hip", "tmpnn_hits.hip",
+           "tmpnn_coordgrad.hip", "tmpnn_hits.hip", "tmpnn_variant_hits.hip",
            "tmpnn_pdb.cpp", "tmpnn_csv.cpp"]
-HEADERS = ["tmpnn_common.h", "tmpnn_split.h", "tmpnn_internal.h", "tmpnn_head_body.h", "tmpnn_ft.h", os.path.join("..", "..", "include", "tmpnn.h"),
+HEADERS = ["tmpnn_common.h", "tmpnn_split.h", "tmpnn_internal.h", "tmpnn_head_body.h", "tmpnn_ft.h", "tmpnn_hits.h", os.path.join("..", "..", "include", "tmpnn.h"),
            os.path.join("..", "..", "include", "tmpnn_debug.h"), "tmpnn_host_guard.hpp"]
 # -mcode-object-version=5: tm_nblk() / tm_bdim() (tmpnn_common.h) read gridDim / blockDim at fixed offsets of the v5
 # implicit-argument block; pinned here and checked on the device by tmpnn_selftest.
@@ -34,6 +34,9 @@ DEVICE_FLAGS = ["-mno-amdgpu-ieee", "-fno-honor-nans"]
 NAN3_FILES = ("tmpnn_split.hip", "tmpnn_edge.hip", "tmpnn_msg.hip", "tmpnn_edge_msg.hip", "tmpnn_node.hip", "tmpnn_variants.hip",
               "tmpnn_sample.hip")
 FILE_FLAGS = {f: ["-DTM_GELU_NAN3=1"] for f in NAN3_FILES}
+# ... and the streaming selection over variant tables: its one float operation, base + ddG, must give the NaN of +inf + -inf for the
+# bit test behind it to see; under -fno-honor-nans that sum is poison to the compiler (and -mno-amdgpu-ieee needs that flag).
+FILE_FLAGS["tmpnn_variant_hits.hip"] = []
 
 
 def _hipcc() -> str:

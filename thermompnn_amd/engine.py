@@ -430,6 +430,60 @@ class Engine:
                                              _stream()), "tmpnn_select_hits")
         return res
 
+    def select_variant_hits(self, ddg, S_var, base, tag, k: int, skip=None, cutoff: Optional[float] = None, include_cys: bool = False,
+                            upper: bool = False, state: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """The ``k`` smallest values ``base[v] + ddg[v, q, b]`` over a chunk of variant tables that is already on the device, and over
+        what earlier calls left in ``state`` (tmpnn_select_variant_hits: two launches): ``ddg`` [V, L, ld >= 20] float32
+        (``decode_variants``' tables), ``S_var`` [V, L] the variants' own letters, and per variant ``base`` [V] (float32), ``tag`` [V]
+        (0 .. 65535, distinct over all calls of one selection) and ``skip`` [V] (a position without candidates; None or -1: none).
+        A candidate is a substitution b != S_var[v, q] of a residue with S_var[v, q] < 20 at q != skip[v] (``upper``: q > skip[v])
+        whose sum — one fp32 add — is not NaN and <= ``cutoff`` (None: +inf), cysteine only with ``include_cys``. ``state=None``
+        starts a selection; passing back the returned ``state`` (int64 [k], the 64-bit keys; updated in place) continues it, and the
+        result does not depend on how the variants were cut into calls. -> dict(hit_ddg [k] padded with NaN, hit_tag / hit_pos /
+        hit_aa [k] padded with -1, hit_count [1], state) on the device, best first: ascending (value, tag, position, letter), -0.0
+        taken as +0.0. 1 <= k <= 256, L <= 2048, one protein per selection."""
+        if not isinstance(ddg, torch.Tensor) or not ddg.is_cuda or ddg.dtype != torch.float32 or ddg.dim() != 3:
+            raise TmpnnError("select_variant_hits: ddg must be a float32 [V, L, ld] tensor on the device (the tables stay there; there is no CPU path)")
+        V, L, cols = (int(n) for n in ddg.shape)
+        if V > 0 and L > 0 and (ddg.stride(2) != 1 or ddg.stride(1) < cols or ddg.stride(0) != L * ddg.stride(1)):
+            ddg = ddg.contiguous()
+        ld = int(ddg.stride(1)) if V > 0 and L > 0 else cols
+        if not 1 <= int(k) <= _lib.HITS_MAX_K:
+            raise TmpnnError(f"select_variant_hits: k={k} outside [1, {_lib.HITS_MAX_K}]")
+        cut = float("inf") if cutoff is None else float(cutoff)
+        if cut != cut:
+            raise TmpnnError("select_variant_hits: the cutoff is NaN")
+        if L > _lib.VHITS_MAX_LEN:
+            raise TmpnnError(f"select_variant_hits: L={L} residues exceed {_lib.VHITS_MAX_LEN}, the key's 11 position bits")
+        dev, k = self.device, int(k)
+        S_var, tag = self._i32(S_var), self._i32(tag)
+        skip = torch.full((V,), -1, dtype=torch.int32, device=dev) if skip is None else self._i32(skip)
+        base = self._f32(base)
+        if tuple(S_var.shape) != (V, L) or base.numel() != V or tag.numel() != V or skip.numel() != V:
+            raise TmpnnError(f"select_variant_hits: tables {(V, L, cols)} need S_var [V, L] and base, tag, skip [V]; got "
+                             f"{tuple(S_var.shape)}, {base.numel()}, {tag.numel()}, {skip.numel()}")
+        flags = (_lib.VHITS_INCLUDE_CYS if include_cys else 0) | (_lib.VHITS_UPPER if upper else 0)
+        if state is not None:
+            if not isinstance(state, torch.Tensor) or not state.is_cuda or state.dtype != torch.int64 or tuple(state.shape) != (k,) or \
+                    not state.is_contiguous():
+                raise TmpnnError(f"select_variant_hits: state must be the int64 [{k}] device tensor an earlier call with k={k} returned")
+            flags |= _lib.VHITS_CONTINUE
+        else:
+            state = torch.empty(k, dtype=torch.int64, device=dev)
+        need = self.lib.tmpnn_variant_hits_workspace_bytes(V, L, k)
+        if need == 0:
+            raise TmpnnError(f"select_variant_hits: sizes not served (V={V}, L={L}, k={k})")
+        res = dict(hit_ddg=torch.empty(k, dtype=torch.float32, device=dev), hit_tag=torch.empty(k, dtype=torch.int32, device=dev),
+                   hit_pos=torch.empty(k, dtype=torch.int32, device=dev), hit_aa=torch.empty(k, dtype=torch.int32, device=dev),
+                   hit_count=torch.empty(1, dtype=torch.int32, device=dev), state=state)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            check(self.lib.tmpnn_select_variant_hits(_ptr(ddg), ld, _ptr(S_var), _ptr(base), _ptr(tag), _ptr(skip), V, L, k, cut, flags,
+                                                     _ptr(state), _ptr(res["hit_ddg"]), _ptr(res["hit_tag"]), _ptr(res["hit_pos"]),
+                                                     _ptr(res["hit_aa"]), _ptr(res["hit_count"]), _ptr(ws), ws.numel(), _stream()),
+                  "tmpnn_select_variant_hits")
+        return res
+
     # -- many sequence variants over one backbone ----------------------------------------------------
     def encode(self, X, mask, residue_idx, chain_enc, offsets, max_len: Optional[int] = None,
                precision: Optional[str] = None) -> "EncodedBackbone":

@@ -137,20 +137,41 @@ class TransferModel(_EngineOwner):
         ``subtract_mut=False`` models return the un-subtracted head output, as ``ssm_table`` does."""
         from .variant_scan import variant_matrix
         entry = pdb[0] if isinstance(pdb, (list, tuple)) else pdb
-        device = next(self.parameters()).device
-        feats = tied_featurize([entry], device, None, None, None, None, None, None, ca_only=False)
-        X, mask, chain_enc, residue_idx = feats[0], feats[2], feats[5], feats[12]
         if isinstance(variants, (np.ndarray, torch.Tensor)):
             Sv = torch.as_tensor(variants)
         else:
             Sv = torch.from_numpy(variant_matrix(entry["seq"], list(variants)))
+        if Sv.dim() != 2 or Sv.shape[1] != len(entry["seq"]):          # (before the encoder runs; _tables_over checks it against the encoding)
+            raise ValueError(f"variants: expected [V, {len(entry['seq'])}] sequences, got {tuple(Sv.shape)}")
+        return self._tables_over(self._encode_structure(entry), Sv)
+
+    def double_mutant_hits(self, pdb, k: int, **kw):
+        """The ``k`` most stabilising double mutants of one parsed structure, best first, as ``variant_scan.PairHit``: the backbone
+        is encoded once, the single-substitution backgrounds are decoded a chunk at a time and every chunk is reduced to ``k`` keys
+        on the device (``variant_scan.double_mutant_hits``, which documents the options)."""
+        from .variant_scan import double_mutant_hits
+        return double_mutant_hits(self, pdb, k, **kw)
+
+    def _encode_structure(self, entry):
+        """One parsed structure -> its EncodedBackbone (Engine.encode: the part of a forward that never reads the sequence)."""
+        device = next(self.parameters()).device
+        feats = tied_featurize([entry], device, None, None, None, None, None, None, ca_only=False)
+        X, mask, chain_enc, residue_idx = feats[0], feats[2], feats[5], feats[12]
         eng = self.engine()
         L = X.shape[1]
+        with torch.cuda.device(eng.device):
+            return eng.encode(X[0], mask[0], residue_idx[0], chain_enc[0], torch.tensor([0, L], dtype=torch.int32), max_len=L)
+
+    def _tables_over(self, enc, Sv) -> torch.Tensor:
+        """The body of ``variant_tables`` behind the encoder: ``Sv`` [V, L] index matrix -> [V, L, 21] over an EncodedBackbone, which
+        a caller that decodes chunk after chunk (``double_mutant_hits``) makes once."""
+        Sv = torch.as_tensor(Sv)
+        eng = self.engine()
+        L = enc.T
         if Sv.dim() != 2 or Sv.shape[1] != L:
             raise ValueError(f"variants: expected [V, {L}] sequences, got {tuple(Sv.shape)}")
         V = Sv.shape[0]
         with torch.cuda.device(eng.device):
-            enc = eng.encode(X[0], mask[0], residue_idx[0], chain_enc[0], torch.tensor([0, L], dtype=torch.int32), max_len=L)
             std = self.subtract_mut and not self.generic_head
             res = eng.decode_variants(enc, Sv, want_ddg=not self.generic_head, want_hidden=not std)
             if std:

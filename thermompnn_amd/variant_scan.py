@@ -2,17 +2,24 @@
 variant with the backbone's edge tiles shared between variants (Engine.decode_variants, csrc/tmpnn_variants.hip).
 
     python -m thermompnn_amd.variant_scan a.pdb --chain A (--variants FILE | --all-singles) --out x.npz [--synthetic_weights N]
+    python -m thermompnn_amd.variant_scan a.pdb --chain A --top-pairs K [--cutoff X] [--include_cys] [--unordered] --out hits.csv
 
 FILE holds one variant per line: a full one-letter sequence of the parsed length, or a comma-separated list of substitutions
 such as ``A12G,K45E`` (wild type, 1-based position in the parsed sequence, new residue). Writes ``tables`` float32 [V, L, 21]
 (entry [v, pos, a]: ddG of mutating position pos of variant v to ALPHABET[a], relative to the variant's own residue),
 ``variants`` (the V sequences) and ``wild_type``.
-Not here: CSV output and the native writer, multi-GPU sharding of the variants, hipGraph capture, the training paths,
-ProteinMPNN.forward and examples/."""
+``--top-pairs K`` writes the K most stabilising double mutants instead, one CSV row per hit (``double_mutant_hits``): every
+single-substitution background is decoded, a chunk at a time, and each chunk of tables is reduced to K keys on the device
+(Engine.select_variant_hits, csrc/tmpnn_variant_hits.hip), so the [P, 20, L, 20] table of ``double_mutant_table`` never exists.
+Limits of the pair selection: L <= 2048, K <= 256, one protein, one rank, no one-per-site-pair reduction.
+Not here: the native writer, multi-GPU sharding of the variants, hipGraph capture, the training paths, ProteinMPNN.forward and
+examples/."""
 from __future__ import annotations
 
 import argparse
+import csv
 import re
+from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence
 
 import numpy as np
@@ -119,7 +126,115 @@ def double_mutant_table(model, pdb, positions: Optional[Sequence[int]] = None, c
     return out
 
 
-def main(argv=None):
+@dataclass
+class PairHit:
+    """One double mutant: ``first`` is the background substitution p:a, ``second`` the substitution q:b made on that background
+    (``Mutation.ddG`` of ``first`` is table_wt[p, a]; ``second`` carries none: table_{p:a}[q, b] stays on the device, only its sum
+    with the first comes back). ``ddG`` is that fp32 sum, table_wt[p, a] + table_{p:a}[q, b], which the device ranked;
+    ``ddG_first`` = table_wt[p, a], ``ddG_additive`` = table_wt[p, a] + table_wt[q, b] and ``epistasis`` = ddG - ddG_additive are
+    computed on the host, in double precision, from the fp32 table entries."""
+    first: Mutation
+    second: Mutation
+    ddG: float
+    ddG_first: float
+    ddG_additive: float
+    epistasis: float
+
+
+PAIR_MAX_LEN, PAIR_MAX_K, CYS = 2048, 256, _CODE["C"]
+
+
+def pair_tag(p, a):
+    """The selection's tag of background p:a, p * 32 + a: 11 + 5 bits, so it fits the key's 16 tag bits up to L = 2048."""
+    return p * 32 + a
+
+
+def split_tag(tag):
+    return tag >> 5, tag & 31
+
+
+def double_mutant_hits(model, pdb, k: int, positions: Optional[Sequence[int]] = None, cutoff: Optional[float] = None,
+                       include_cys: bool = False, unordered: bool = False, chunk: int = 256,
+                       _tables: Optional[Callable] = None, _select: Optional[Callable] = None) -> List[PairHit]:
+    """The ``k`` most stabilising double mutants (p:a, q:b) of one parsed structure, best first: the smallest
+        ddG(p:a, q:b) = table_wt[p, a] + table_{p:a}[q, b]                                     (``double_mutant_table``'s entries)
+    in ascending (ddG, p, a, q, b) order with -0.0 taken as +0.0, without the [P, 20, L, 20] table: the backbone is encoded ONCE,
+    the wild type is decoded, then the single-substitution backgrounds ``chunk`` at a time, and every chunk of tables is reduced to
+    k keys on the device while the next one reuses its memory (``Engine.select_variant_hits`` with base = table_wt[p, a],
+    tag = p * 32 + a, skip = p; the k keys are carried from chunk to chunk). Never more than one chunk of tables is allocated.
+    Backgrounds: every a != the wild type's letter (those are single mutants) at ``positions`` (default: every residue with one of
+    the 20 letters), cysteine only with ``include_cys`` — which holds for the second substitution too. Second sites: every q != p
+    with a letter, b != its letter, ddG not NaN and <= ``cutoff``. The default keeps both orders of a site pair (p:a then q:b, and
+    q:b then p:a: different numbers); ``unordered`` keeps q > p only, one path per site pair. L <= 2048, 1 <= k <= 256.
+    (``_tables(S [V, L]) -> [V, L, 21]`` and ``_select(ddg, S_var, base, tag, k, skip=, cutoff=, include_cys=, upper=, state=)``:
+    the table function and the selection, defaults the model's and its engine's.)"""
+    entry = pdb[0] if isinstance(pdb, (list, tuple)) else pdb
+    seq = entry["seq"]
+    L, wt_idx = len(seq), sequence_indices(seq)
+    if not 1 <= int(k) <= PAIR_MAX_K:
+        raise ValueError(f"double_mutant_hits: k={k} outside [1, {PAIR_MAX_K}]")
+    if L > PAIR_MAX_LEN:
+        raise ValueError(f"double_mutant_hits: {L} residues exceed {PAIR_MAX_LEN} (the selection's key holds 11 position bits)")
+    if int(chunk) < 1:
+        raise ValueError(f"double_mutant_hits: chunk={chunk}")
+    if positions is None:
+        positions = [p for p in range(L) if wt_idx[p] < 20]
+    positions = sorted({int(p) for p in positions})
+    for p in positions:
+        if not 0 <= p < L or wt_idx[p] >= 20:
+            raise ValueError(f"position {p}: outside the sequence or a residue without one of the 20 letters")
+    if _tables is None:
+        enc = model._encode_structure(entry)                           # the only encoder run
+        _tables = lambda s: model._tables_over(enc, s)
+    if _select is None:
+        _select = model.engine().select_variant_hits
+    pairs = [(p, a) for p in positions for a in range(20) if a != wt_idx[p] and (include_cys or a != CYS)]
+    wt = _tables(wt_idx[None])[0]                                      # [L, 21]
+    if not pairs:
+        return []
+    pos_of, aa_of = (np.array(x, dtype=np.int64) for x in zip(*pairs))
+    res = state = None
+    for v0 in range(0, len(pairs), int(chunk)):
+        p_c, a_c = pos_of[v0:v0 + int(chunk)], aa_of[v0:v0 + int(chunk)]
+        S = np.tile(wt_idx, (len(p_c), 1))
+        S[np.arange(len(p_c)), p_c] = a_c
+        t = _tables(S)                                                 # [n, L, 21]: the previous chunk's tables are free by now
+        base = wt[torch.as_tensor(p_c, device=wt.device), torch.as_tensor(a_c, device=wt.device)]
+        res = _select(t, S, base, pair_tag(p_c, a_c), int(k), skip=p_c, cutoff=cutoff, include_cys=include_cys, upper=unordered,
+                      state=state)
+        state = res["state"]
+        del t
+    n = int(res["hit_count"][0])
+    val, tag, q_h, b_h = (np.asarray(res[key][:n].cpu()) for key in ("hit_ddg", "hit_tag", "hit_pos", "hit_aa"))
+    table = np.asarray(wt.cpu(), dtype=np.float32)
+    name = entry.get("name", "")
+    hits = []
+    for v, tg, q, b in zip(val, tag, q_h, b_h):
+        p, a = (int(x) for x in split_tag(int(tg)))
+        q, b = int(q), int(b)
+        first, add = float(table[p, a]), float(table[p, a]) + float(table[q, b])
+        hits.append(PairHit(Mutation(p, seq[p], ALPHABET[a], first, name), Mutation(q, seq[q], ALPHABET[b], None, name),
+                            float(v), first, add, float(v) - add))
+    return hits
+
+
+PAIR_CSV_HEADER = ["rank", "first", "second", "ddG", "ddG_first", "ddG_additive", "epistasis"]
+
+
+def write_pair_hits_csv(path: str, hits: Sequence[PairHit]) -> int:
+    """One row per hit, best first: rank (0-based), the two substitutions in the variant file's notation (``A12G``: wild type,
+    1-based position, new residue), then ddG, ddG_first, ddG_additive and epistasis as ``repr`` of the Python floats."""
+    sub = lambda m: f"{m.wildtype}{m.position + 1}{m.mutation}"
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh, lineterminator="\n")
+        w.writerow(PAIR_CSV_HEADER)
+        for r, h in enumerate(hits):
+            w.writerow([r, sub(h.first), sub(h.second), repr(h.ddG), repr(h.ddG_first), repr(h.ddG_additive), repr(h.epistasis)])
+    return len(hits)
+
+
+def main(argv=None, _tables: Optional[Callable] = None, _select: Optional[Callable] = None):
+    """(``_tables`` / ``_select``: ``double_mutant_hits``' hooks for --top-pairs; with ``_tables`` no model is loaded.)"""
     from .custom_inference import load_model
     from .pdb_io import alt_parse_PDB
     ap = argparse.ArgumentParser(description="ThermoMPNN ddG tables of one backbone under many sequence variants on MI355X")
@@ -128,16 +243,34 @@ def main(argv=None):
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--variants", help="file with one variant per line: a full sequence or a list like A12G,K45E")
     src.add_argument("--all-singles", action="store_true", help="every single-substitution background (19 per residue)")
-    ap.add_argument("--out", required=True, help="output .npz")
+    src.add_argument("--top-pairs", type=int, default=None, metavar="K",
+                     help="the K most stabilising double mutants, selected on the GPU, as a CSV (1 <= K <= 256)")
+    ap.add_argument("--out", required=True, help="output .npz (--top-pairs: .csv)")
+    ap.add_argument("--cutoff", type=float, default=None, help="--top-pairs: keep double mutants with ddG <= cutoff")
+    ap.add_argument("--include_cys", action="store_true", help="--top-pairs: substitutions to cysteine take part")
+    ap.add_argument("--unordered", action="store_true", help="--top-pairs: one path per site pair (second site behind the first)")
     ap.add_argument("--model_path", default="")
     ap.add_argument("--thermompnn_dir", default=".")
     ap.add_argument("--synthetic_weights", type=int, default=None)
     ap.add_argument("--precision", default=None)
     ap.add_argument("--chunk", type=int, default=256, help="variants decoded per call")
     a = ap.parse_args(argv)
-    model = load_model(a.model_path or None, a.thermompnn_dir, a.synthetic_weights, precision=a.precision)
+    if a.top_pairs is None and (a.cutoff is not None or a.include_cys or a.unordered):
+        ap.error("--cutoff, --include_cys and --unordered belong to --top-pairs")
+    if a.top_pairs is not None and not 1 <= a.top_pairs <= PAIR_MAX_K:
+        ap.error(f"--top-pairs {a.top_pairs}: outside [1, {PAIR_MAX_K}]")
+    if a.top_pairs is not None and a.out.endswith(".npz"):
+        ap.error("--top-pairs writes a CSV, not an .npz")
+    model = None if _tables is not None else load_model(a.model_path or None, a.thermompnn_dir, a.synthetic_weights, precision=a.precision)
     pdb = alt_parse_PDB(a.pdb, a.chain)
     seq = pdb[0]["seq"]
+    if a.top_pairs is not None:
+        with torch.no_grad():
+            hits = double_mutant_hits(model, pdb, a.top_pairs, cutoff=a.cutoff, include_cys=a.include_cys, unordered=a.unordered,
+                                      chunk=a.chunk, _tables=_tables, _select=_select)
+        write_pair_hits_csv(a.out, hits)
+        print(f"{len(hits)} double mutants of {len(seq)} residues -> {a.out}")
+        return 0
     if a.all_singles:
         _, S = single_backgrounds(seq)
         base = sequence_indices(seq)
