@@ -636,6 +636,49 @@ int tmpnn_select_variant_hits(const float *ddg, int ld, const int32_t *S_var, co
                               uint64_t *state, float *hit_ddg, int32_t *hit_tag, int32_t *hit_pos, int32_t *hit_aa,
                               int32_t *hit_count, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream);
 
+/* ---- per-site-pair maps over variant tables: every (row, position)'s best value and epistasis, carried from call to call ---------
+ * The other reduction of a table that is too large to exist ([P, 20, L, 20] for the double mutants of a protein): not the k best of
+ * all, but for every pair (state row, position q) its best value, the extremes of its epistasis, and the mean size of it. One call
+ * takes V variants of ONE protein of L rows, all on the device: ddg [V, L, ld] (ld >= 20), S_var [V, L], per variant base [V] (fp32),
+ * row [V], letter [V] and skip [V] (int32; skip -1 = none), the wild-type table wt [L, ld_wt] (ld_wt >= 20), and R, the number of
+ * state rows. A CANDIDATE is (v, q, b) with 0 <= row[v] < R and 0 <= letter[v] < 20 (a variant outside either range contributes
+ * nothing), S_var[v, q] < 20 (unsigned compare: negative = no residue), b < 20, b != S_var[v, q], q != skip[v] (q > skip[v] with
+ * TMPNN_PMAP_UPPER), and b != cysteine (letter 1) unless TMPNN_PMAP_INCLUDE_CYS. For double mutants row = the index of the first
+ * site p, letter = a, skip = p and base = wt[p, a].
+ * STATE: five arrays of R L entries, owned by the caller, on the device, entry row * L + q. With a = letter[v]:
+ *   best [R L] uint64     the smallest KEY  hits_ord(base[v] + ddg[v, q, b]) << 32 | a << 5 | b  over candidates whose sum is not NaN.
+ *                         The sum is one IEEE fp32 round-to-nearest add. hits_ord(bits) is tmpnn_select_hits' order-preserving image
+ *                         of fp32 bits on uint32: 0x80000000 (-0.0) is first taken as 0, then a word with the sign bit set is
+ *                         inverted and any other gets the sign bit set. So the smallest key is the smallest value (-0.0 counts as
+ *                         +0.0, +-inf are ordinary values), ties going to the smallest (a, b). To decode: o = key >> 32; the value's
+ *                         bits are o ^ 0x80000000 if o has bit 31 set, else ~o; a = (key >> 5) & 31; b = key & 31.
+ *   eps_lo [R L] uint64   the same key on e = ddg[v, q, b] - wt[q, b] (one fp32 subtract), over candidates whose e is not NaN: the
+ *                         most negative epistasis of the pair.
+ *   eps_hi [R L] uint64   the key with high word ~hits_ord(e): the smallest key is the LARGEST e, ties again to the smallest (a, b).
+ *                         To decode, invert the high word first.
+ *   eps_abs_sum [R L] fp32 and count [R L] int32. Per (v, q) an inner sum starts at +0.0 and takes |e| of the candidates with a
+ *                         non-NaN e in ascending b, one fp32 add each, and each counts 1. Then, for every variant of the call
+ *                         whose row lies in [0, R), in ascending v: sum = sum + inner (one fp32 add, also where inner is +0.0) and
+ *                         count += its count. This order is the contract: it makes the sum's bits independent of how the variants
+ *                         are cut into calls.
+ * All ones in a key means "none". No multiply takes part, so nothing can be contracted; no atomics: reruns give identical bits.
+ * Without TMPNN_PMAP_CONTINUE the call first sets the WHOLE state to empty (keys all ones, sum +0.0, count 0); with it the state
+ * takes part, and entries of rows that no variant of the call names keep their bits. The caller promises that within one call the
+ * variants of one row are contiguous (a row may go on in the next call); a row met in two separate runs of one call is undefined.
+ * Two launches on `stream`: one thread per table row (v, q) leaves a record (three keys, the inner sum, the count) in the workspace
+ * and, without CONTINUE, the launch empties the state; then one thread per (first variant of a run, q) folds the run's records in
+ * ascending v into the state. With V == 0 or L == 0 (the input pointers may then be NULL) the call only resets the state, or keeps it
+ * with CONTINUE; with R == 0 or L == 0 the state is empty, its pointers may be NULL and nothing is launched.
+ * tmpnn_pair_map_workspace_bytes: V L records of 32 bytes as five arrays; 0 for sizes that are not served. Errors
+ * before any launch: null pointer, ld or ld_wt < 20, negative sizes, unknown flag bits -> TMPNN_E_INVALID; L > 2048, or V * L or
+ * R * L > 2^31 - 1 -> TMPNN_E_UNSUPPORTED; a short workspace -> TMPNN_E_WORKSPACE. */
+enum { TMPNN_PMAP_INCLUDE_CYS = 1, TMPNN_PMAP_UPPER = 2, TMPNN_PMAP_CONTINUE = 4 };
+size_t tmpnn_pair_map_workspace_bytes(int64_t V, int64_t L);              /* 0 for sizes not served */
+int tmpnn_pair_map(const float *ddg, int ld, const int32_t *S_var, const float *base, const int32_t *row, const int32_t *letter,
+                   const int32_t *skip, const float *wt, int ld_wt, int64_t V, int64_t L, int64_t R, int flags, uint64_t *best,
+                   uint64_t *eps_lo, uint64_t *eps_hi, float *eps_abs_sum, int32_t *count, void *workspace, size_t workspace_bytes,
+                   tmpnn_stream_t stream);
+
 /* ---- host side: native PDB reader + packer ------------------------------------------
  * Replaces alt_parse_PDB (protein_mpnn_utils.py:183-350) + the packing of tied_featurize (:353-605) for one
  * structure: one pass over the file, all requested chains. `chains` = string of one-letter chain ids in the

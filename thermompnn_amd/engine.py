@@ -484,6 +484,63 @@ class Engine:
                   "tmpnn_select_variant_hits")
         return res
 
+    def pair_map(self, ddg, S_var, base, row, letter, wt, R: int, skip=None, include_cys: bool = False, upper: bool = False,
+                 state: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """One chunk of variant tables that is already on the device reduced into a per-(row, position) state (tmpnn_pair_map: two
+        launches): ``ddg`` [V, L, ld >= 20] float32 (``decode_variants``' tables), ``S_var`` [V, L] the variants' own letters, per
+        variant ``base`` [V] (float32), ``row`` [V] (the state row, 0 .. R - 1), ``letter`` [V] (0 .. 19) and ``skip`` [V] (a position
+        without candidates; None or -1: none), and the wild-type table ``wt`` [L, >= 20] float32 on the device. A candidate is a
+        substitution b != S_var[v, q] of a residue with S_var[v, q] < 20 at q != skip[v] (``upper``: q > skip[v]), cysteine only
+        with ``include_cys``; a variant whose row or letter is out of range contributes nothing. The variants of one row must be
+        contiguous within a call (checked here when ``row`` is a numpy array or a list; a row may go on in the next call).
+        ``state=None`` starts a map; passing back the returned dict continues it (updated in place), and its bits do not depend on
+        how the variants were cut into calls. -> dict(best, eps_lo, eps_hi: int64 [R, L] keys, all ones = none; eps_abs_sum float32
+        [R, L]; count int32 [R, L]) on the device: include/tmpnn.h has the key layout, ``decode_pair_map`` reads it. L <= 2048."""
+        if not isinstance(ddg, torch.Tensor) or not ddg.is_cuda or ddg.dtype != torch.float32 or ddg.dim() != 3:
+            raise TmpnnError("pair_map: ddg must be a float32 [V, L, ld] tensor on the device (the tables stay there; there is no CPU path)")
+        V, L, cols = (int(n) for n in ddg.shape)
+        if V > 0 and L > 0 and (ddg.stride(2) != 1 or ddg.stride(1) < cols or ddg.stride(0) != L * ddg.stride(1)):
+            ddg = ddg.contiguous()
+        ld = int(ddg.stride(1)) if V > 0 and L > 0 else cols
+        if not isinstance(wt, torch.Tensor) or not wt.is_cuda or wt.dtype != torch.float32 or wt.dim() != 2 or int(wt.shape[0]) != L:
+            raise TmpnnError(f"pair_map: wt must be a float32 [{L}, >= 20] tensor on the device, the wild type's table")
+        if L > 0 and (wt.stride(1) != 1 or wt.stride(0) < wt.shape[1]):
+            wt = wt.contiguous()
+        ld_wt = int(wt.stride(0)) if L > 0 else int(wt.shape[1])
+        R = int(R)
+        if R < 0:
+            raise TmpnnError(f"pair_map: R={R}")
+        if L > _lib.PMAP_MAX_LEN:
+            raise TmpnnError(f"pair_map: L={L} residues exceed {_lib.PMAP_MAX_LEN}")
+        need = self.lib.tmpnn_pair_map_workspace_bytes(V, L)
+        if need == 0 or R * L > 0x7fffffff:
+            raise TmpnnError(f"pair_map: sizes not served (V={V}, L={L}, R={R})")
+        if isinstance(row, (np.ndarray, list, tuple)):
+            check_row_runs(row, R)
+        dev = self.device
+        S_var, row, letter = self._i32(S_var), self._i32(row), self._i32(letter)
+        skip = torch.full((V,), -1, dtype=torch.int32, device=dev) if skip is None else self._i32(skip)
+        base = self._f32(base)
+        if tuple(S_var.shape) != (V, L) or base.numel() != V or row.numel() != V or letter.numel() != V or skip.numel() != V:
+            raise TmpnnError(f"pair_map: tables {(V, L, cols)} need S_var [V, L] and base, row, letter, skip [V]; got "
+                             f"{tuple(S_var.shape)}, {base.numel()}, {row.numel()}, {letter.numel()}, {skip.numel()}")
+        flags = (_lib.PMAP_INCLUDE_CYS if include_cys else 0) | (_lib.PMAP_UPPER if upper else 0)
+        if state is not None:
+            for name, dt in _lib.PMAP_STATE:
+                t = state.get(name) if isinstance(state, dict) else None
+                if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != getattr(torch, dt) or tuple(t.shape) != (R, L) or \
+                        not t.is_contiguous():
+                    raise TmpnnError(f"pair_map: state[{name!r}] must be the {dt} [{R}, {L}] device tensor an earlier call returned")
+            flags |= _lib.PMAP_CONTINUE
+        else:
+            state = {name: torch.empty((R, L), dtype=getattr(torch, dt), device=dev) for name, dt in _lib.PMAP_STATE}
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            check(self.lib.tmpnn_pair_map(_ptr(ddg), ld, _ptr(S_var), _ptr(base), _ptr(row), _ptr(letter), _ptr(skip), _ptr(wt), ld_wt, V, L, R,
+                                          flags, *[_ptr(state[name]) for name, _ in _lib.PMAP_STATE], _ptr(ws), ws.numel(), _stream()),
+                  "tmpnn_pair_map")
+        return state
+
     # -- many sequence variants over one backbone ----------------------------------------------------
     def encode(self, X, mask, residue_idx, chain_enc, offsets, max_len: Optional[int] = None,
                precision: Optional[str] = None) -> "EncodedBackbone":
@@ -745,6 +802,58 @@ class Engine:
 # -- host side of the four sample entries: the checks, the chunk plans and the launch order (plain torch / numpy: they run without a GPU) --
 EACH_ROWS_MAX = ((1 << 24) - 1) // 3          # chains * rows of one launch (3 * N * rows < 2**24, the chain kernel's row arithmetic)
 SAMPLE_TABLES = ("bias", "allowed", "pssm_mix", "pssm_bias", "pssm_keep")     # per residue: [T,21], pssm_mix [T]
+
+
+def check_row_runs(row, R: int) -> None:
+    """tmpnn_pair_map's promise, checked on the host: within one call the variants of one state row are contiguous (rows outside
+    [0, R) name no state row and may repeat). TmpnnError with the row and the variant at which it comes back."""
+    r = np.asarray(row).reshape(-1).astype(np.int64)
+    heads = np.flatnonzero(np.concatenate([[True], r[1:] != r[:-1]])) if r.size else np.zeros(0, np.int64)
+    heads = heads[(r[heads] >= 0) & (r[heads] < int(R))]
+    seen = {}
+    for v in heads.tolist():
+        if int(r[v]) in seen:
+            raise TmpnnError(f"pair_map: the variants of one row must be contiguous within a call: row {int(r[v])} begins at variant "
+                             f"{seen[int(r[v])]} and comes back at variant {v}")
+        seen[int(r[v])] = v
+
+
+def decode_pair_map(state) -> Dict[str, object]:
+    """The state of ``Engine.pair_map`` read: integer operations of torch where the state lives (nothing is copied), or of numpy on
+    numpy arrays. -> dict(best_ddG, eps_min, eps_max: float32 [R, L], NaN where there is none — the value's own bits, a -0.0 as +0.0;
+    best_a / best_b, eps_min_a / eps_min_b, eps_max_a / eps_max_b: int32, the letter of the variant and the substituted letter, -1
+    where there is none; eps_abs_mean = eps_abs_sum / count in float32, NaN at count 0; count)."""
+    on_torch = isinstance(state["best"], torch.Tensor)
+    xp = torch if on_torch else np
+    out = {}
+
+    def read(keys, inverted):
+        k = keys if on_torch else np.asarray(keys).view(np.int64)
+        none = k == -1
+        o = (k >> 32) & 0xffffffff
+        if inverted:
+            o = o ^ 0xffffffff
+        bits = xp.where((o >> 31) == 1, o ^ 0x80000000, o ^ 0xffffffff)        # hits_ord undone
+        bits = xp.where(none, xp.full_like(bits, 0x7fc00000), bits)
+        if on_torch:
+            val = (bits - ((bits >> 31) << 32)).to(torch.int32).view(torch.float32)
+            return val, xp.where(none, -1, (k >> 5) & 31).to(torch.int32), xp.where(none, -1, k & 31).to(torch.int32)
+        val = bits.astype(np.uint32).view(np.float32)
+        return val, np.where(none, -1, (k >> 5) & 31).astype(np.int32), np.where(none, -1, k & 31).astype(np.int32)
+
+    for name, key, inverted in (("best", "best", False), ("eps_min", "eps_lo", False), ("eps_max", "eps_hi", True)):
+        val, a, b = read(state[key], inverted)
+        out["best_ddG" if name == "best" else name], out[name + "_a"], out[name + "_b"] = val, a, b
+    total, count = state["eps_abs_sum"], state["count"]
+    if on_torch:
+        mean = total / count.clamp(min=1).to(torch.float32)
+        out["eps_abs_mean"] = torch.where(count == 0, torch.full_like(mean, float("nan")), mean)
+    else:
+        total, count = np.asarray(total, dtype=np.float32), np.asarray(count)
+        mean = total / np.maximum(count, 1).astype(np.float32)
+        out["eps_abs_mean"] = np.where(count == 0, np.float32("nan"), mean).astype(np.float32)
+    out["count"] = count
+    return out
 
 
 def sample_args(what: str, T: int, dev, order, close, S_fixed, free, u, temperature, weight, bias, allowed, pssm_mix, pssm_bias, pssm_keep):

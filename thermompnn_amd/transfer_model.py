@@ -152,6 +152,13 @@ class TransferModel(_EngineOwner):
         from .variant_scan import double_mutant_hits
         return double_mutant_hits(self, pdb, k, **kw)
 
+    def double_mutant_map(self, pdb, **kw):
+        """Every site pair's best double mutant, the extremes of its epistasis and the mean size of it, as ``variant_scan.PairMap``:
+        the backbone is encoded once, the single-substitution backgrounds are decoded a chunk at a time and every chunk is reduced
+        into the [P, L] state on the device (``variant_scan.double_mutant_map``, which documents the options)."""
+        from .variant_scan import double_mutant_map
+        return double_mutant_map(self, pdb, **kw)
+
     def _encode_structure(self, entry):
         """One parsed structure -> its EncodedBackbone (Engine.encode: the part of a forward that never reads the sequence)."""
         device = next(self.parameters()).device

@@ -3,6 +3,7 @@ variant with the backbone's edge tiles shared between variants (Engine.decode_va
 
     python -m thermompnn_amd.variant_scan a.pdb --chain A (--variants FILE | --all-singles) --out x.npz [--synthetic_weights N]
     python -m thermompnn_amd.variant_scan a.pdb --chain A --top-pairs K [--cutoff X] [--include_cys] [--unordered] --out hits.csv
+    python -m thermompnn_amd.variant_scan a.pdb --chain A --pair-map [--include_cys] [--unordered] --out map.npz
 
 FILE holds one variant per line: a full one-letter sequence of the parsed length, or a comma-separated list of substitutions
 such as ``A12G,K45E`` (wild type, 1-based position in the parsed sequence, new residue). Writes ``tables`` float32 [V, L, 21]
@@ -11,7 +12,11 @@ such as ``A12G,K45E`` (wild type, 1-based position in the parsed sequence, new r
 ``--top-pairs K`` writes the K most stabilising double mutants instead, one CSV row per hit (``double_mutant_hits``): every
 single-substitution background is decoded, a chunk at a time, and each chunk of tables is reduced to K keys on the device
 (Engine.select_variant_hits, csrc/tmpnn_variant_hits.hip), so the [P, 20, L, 20] table of ``double_mutant_table`` never exists.
-Limits of the pair selection: L <= 2048, K <= 256, one protein, one rank, no one-per-site-pair reduction.
+Limits of the pair selection: L <= 2048, K <= 256, one protein, one rank; the one-per-site-pair reduction is ``--pair-map``.
+``--pair-map`` writes, for every site pair (p, q), its best double mutant with its letters, the most negative and the most positive
+epistasis with theirs, the mean |epistasis| and the number of double mutants, as [L, L] arrays (``double_mutant_map`` / ``PairMap``):
+the same chunk loop, each chunk reduced into the [L, L] state on the device (Engine.pair_map, csrc/tmpnn_pair_map.hip).
+Limits of the pair map: L <= 2048, one protein, one rank; the state is five [L, L] arrays (32 bytes per site pair).
 Not here: the native writer, multi-GPU sharding of the variants, hipGraph capture, the training paths, ProteinMPNN.forward and
 examples/."""
 from __future__ import annotations
@@ -233,8 +238,92 @@ def write_pair_hits_csv(path: str, hits: Sequence[PairHit]) -> int:
     return len(hits)
 
 
-def main(argv=None, _tables: Optional[Callable] = None, _select: Optional[Callable] = None):
-    """(``_tables`` / ``_select``: ``double_mutant_hits``' hooks for --top-pairs; with ``_tables`` no model is loaded.)"""
+@dataclass
+class PairMap:
+    """Every site pair's best double mutant and its coupling, [R, L] numpy arrays on the host: row r is the first site
+    ``positions[r]`` (p), column q the second site. With ddG(p:a, q:b) = table_wt[p, a] + table_{p:a}[q, b] and the epistasis
+    e = table_{p:a}[q, b] - table_wt[q, b] (what q:b does on the background p:a, less what it does on the wild type; both fp32):
+    ``best_ddG`` the smallest ddG of the pair and ``best_a`` / ``best_b`` its letters (ALPHABET indices; ties: the smallest (a, b));
+    ``eps_min`` / ``eps_max`` the most negative and the most positive e with their letters; ``eps_abs_mean`` the mean |e| over the
+    pair's ``count`` double mutants — near zero: an additive pair. NaN and -1 where a pair has no double mutant (q = p, a '-' or 'X'
+    residue, q < p with ``unordered``). ``wt`` is the wild type's table [L, 21], ``seq`` the parsed sequence."""
+    positions: np.ndarray
+    best_ddG: np.ndarray
+    best_a: np.ndarray
+    best_b: np.ndarray
+    eps_min: np.ndarray
+    eps_min_a: np.ndarray
+    eps_min_b: np.ndarray
+    eps_max: np.ndarray
+    eps_max_a: np.ndarray
+    eps_max_b: np.ndarray
+    eps_abs_mean: np.ndarray
+    count: np.ndarray
+    wt: np.ndarray
+    seq: str
+
+    ARRAYS = ("positions", "best_ddG", "best_a", "best_b", "eps_min", "eps_min_a", "eps_min_b", "eps_max", "eps_max_a", "eps_max_b",
+              "eps_abs_mean", "count", "wt")
+
+
+def double_mutant_map(model, pdb, positions: Optional[Sequence[int]] = None, include_cys: bool = False, unordered: bool = False,
+                      chunk: int = 256, _tables: Optional[Callable] = None, _reduce: Optional[Callable] = None) -> PairMap:
+    """For EVERY site pair (p, q) of one parsed structure its best double mutant, the extremes of its epistasis and the mean size of
+    it (``PairMap``), without the [P, 20, L, 20] table: ``double_mutant_hits``' loop — the backbone is encoded ONCE, the wild type is
+    decoded, then the single-substitution backgrounds ``chunk`` at a time in ascending (p, a) order — with every chunk of tables
+    reduced on the device into an [R, L] state (``Engine.pair_map`` with base = table_wt[p, a], row = the index of p in
+    ``positions``, letter = a, skip = p; the state is carried from chunk to chunk and its bits do not depend on ``chunk``). Never
+    more than one chunk of tables plus the state is allocated. Backgrounds and second substitutions as in ``double_mutant_hits``:
+    every a != the wild type's letter at ``positions`` (sorted; default: every residue with one of the 20 letters), every q != p
+    with a letter (``unordered``: q > p only), b != its letter, cysteine on either side only with ``include_cys``. L <= 2048.
+    (``_tables(S [V, L]) -> [V, L, 21]`` and ``_reduce(ddg, S_var, base, row, letter, wt, R, skip=, include_cys=, upper=, state=)``:
+    the table function and the reduction, defaults the model's and its engine's.)"""
+    from .engine import decode_pair_map
+    entry = pdb[0] if isinstance(pdb, (list, tuple)) else pdb
+    seq = entry["seq"]
+    L, wt_idx = len(seq), sequence_indices(seq)
+    if L > PAIR_MAX_LEN:
+        raise ValueError(f"double_mutant_map: {L} residues exceed {PAIR_MAX_LEN}")
+    if int(chunk) < 1:
+        raise ValueError(f"double_mutant_map: chunk={chunk}")
+    if positions is None:
+        positions = [p for p in range(L) if wt_idx[p] < 20]
+    positions = sorted({int(p) for p in positions})
+    for p in positions:
+        if not 0 <= p < L or wt_idx[p] >= 20:
+            raise ValueError(f"position {p}: outside the sequence or a residue without one of the 20 letters")
+    if _tables is None:
+        enc = model._encode_structure(entry)                           # the only encoder run
+        _tables = lambda s: model._tables_over(enc, s)
+    if _reduce is None:
+        _reduce = model.engine().pair_map
+    R = len(positions)
+    pairs = [(r, p, a) for r, p in enumerate(positions) for a in range(20) if a != wt_idx[p] and (include_cys or a != CYS)]
+    wt = _tables(wt_idx[None])[0]                                      # [L, 21]
+    row_of, pos_of, aa_of = (np.array(x, dtype=np.int64) for x in zip(*pairs)) if pairs else (np.zeros(0, np.int64),) * 3
+    state = None
+    for v0 in range(0, max(len(pairs), 1), int(chunk)):                # (no background: one empty call makes the empty state)
+        r_c, p_c, a_c = row_of[v0:v0 + int(chunk)], pos_of[v0:v0 + int(chunk)], aa_of[v0:v0 + int(chunk)]
+        S = np.tile(wt_idx, (len(p_c), 1))
+        S[np.arange(len(p_c)), p_c] = a_c
+        t = _tables(S) if len(p_c) else wt.new_zeros((0, L, wt.shape[1]))   # [n, L, 21]: the previous chunk's tables are free by now
+        base = wt[torch.as_tensor(p_c, device=wt.device), torch.as_tensor(a_c, device=wt.device)]
+        state = _reduce(t, S, base, r_c, a_c, wt, R, skip=p_c, include_cys=include_cys, upper=unordered, state=state)
+        del t
+    dec = decode_pair_map(state)
+    host = {k: np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v) for k, v in dec.items()}
+    return PairMap(positions=np.array(positions, dtype=np.int64), wt=np.asarray(wt.cpu(), dtype=np.float32), seq=seq, **host)
+
+
+def write_pair_map_npz(path: str, m: PairMap) -> None:
+    """``PairMap``'s arrays under their own names, plus ``seq``."""
+    with open(path, "wb") as fh:
+        np.savez(fh, seq=np.array(m.seq), **{name: getattr(m, name) for name in PairMap.ARRAYS})
+
+
+def main(argv=None, _tables: Optional[Callable] = None, _select: Optional[Callable] = None, _reduce: Optional[Callable] = None):
+    """(``_tables`` / ``_select`` / ``_reduce``: the hooks of ``double_mutant_hits`` for --top-pairs and of ``double_mutant_map`` for
+    --pair-map; with ``_tables`` no model is loaded.)"""
     from .custom_inference import load_model
     from .pdb_io import alt_parse_PDB
     ap = argparse.ArgumentParser(description="ThermoMPNN ddG tables of one backbone under many sequence variants on MI355X")
@@ -245,18 +334,23 @@ def main(argv=None, _tables: Optional[Callable] = None, _select: Optional[Callab
     src.add_argument("--all-singles", action="store_true", help="every single-substitution background (19 per residue)")
     src.add_argument("--top-pairs", type=int, default=None, metavar="K",
                      help="the K most stabilising double mutants, selected on the GPU, as a CSV (1 <= K <= 256)")
+    src.add_argument("--pair-map", action="store_true",
+                     help="every site pair's best double mutant and epistasis, reduced on the GPU, as an .npz of [L, L] maps")
     ap.add_argument("--out", required=True, help="output .npz (--top-pairs: .csv)")
     ap.add_argument("--cutoff", type=float, default=None, help="--top-pairs: keep double mutants with ddG <= cutoff")
-    ap.add_argument("--include_cys", action="store_true", help="--top-pairs: substitutions to cysteine take part")
-    ap.add_argument("--unordered", action="store_true", help="--top-pairs: one path per site pair (second site behind the first)")
+    ap.add_argument("--include_cys", action="store_true", help="--top-pairs, --pair-map: substitutions to cysteine take part")
+    ap.add_argument("--unordered", action="store_true",
+                    help="--top-pairs, --pair-map: one path per site pair (second site behind the first)")
     ap.add_argument("--model_path", default="")
     ap.add_argument("--thermompnn_dir", default=".")
     ap.add_argument("--synthetic_weights", type=int, default=None)
     ap.add_argument("--precision", default=None)
     ap.add_argument("--chunk", type=int, default=256, help="variants decoded per call")
     a = ap.parse_args(argv)
-    if a.top_pairs is None and (a.cutoff is not None or a.include_cys or a.unordered):
-        ap.error("--cutoff, --include_cys and --unordered belong to --top-pairs")
+    if a.top_pairs is None and a.cutoff is not None:
+        ap.error("--cutoff belongs to --top-pairs")
+    if a.top_pairs is None and not a.pair_map and (a.include_cys or a.unordered):
+        ap.error("--include_cys and --unordered belong to --top-pairs and --pair-map")
     if a.top_pairs is not None and not 1 <= a.top_pairs <= PAIR_MAX_K:
         ap.error(f"--top-pairs {a.top_pairs}: outside [1, {PAIR_MAX_K}]")
     if a.top_pairs is not None and a.out.endswith(".npz"):
@@ -270,6 +364,13 @@ def main(argv=None, _tables: Optional[Callable] = None, _select: Optional[Callab
                                       chunk=a.chunk, _tables=_tables, _select=_select)
         write_pair_hits_csv(a.out, hits)
         print(f"{len(hits)} double mutants of {len(seq)} residues -> {a.out}")
+        return 0
+    if a.pair_map:
+        with torch.no_grad():
+            m = double_mutant_map(model, pdb, include_cys=a.include_cys, unordered=a.unordered, chunk=a.chunk, _tables=_tables,
+                                  _reduce=_reduce)
+        write_pair_map_npz(a.out, m)
+        print(f"{int((m.count > 0).sum())} site pairs of {len(seq)} residues, {int(m.count.sum())} double mutants -> {a.out}")
         return 0
     if a.all_singles:
         _, S = single_backgrounds(seq)
