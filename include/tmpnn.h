@@ -679,6 +679,43 @@ int tmpnn_pair_map(const float *ddg, int ld, const int32_t *S_var, const float *
                    uint64_t *eps_lo, uint64_t *eps_hi, float *eps_abs_sum, int32_t *count, void *workspace, size_t workspace_bytes,
                    tmpnn_stream_t stream);
 
+/* ---- one step of a beam search over n-point mutants: the k best DISTINCT children of a beam, with their sequence rows ------------
+ * A search of order n is n decodes (tmpnn_decode_variants) plus n steps over one encoded backbone; no table goes to the host and no
+ * sequence comes back. One call takes the V members of a beam over ONE protein of L rows, all on the device: ddg [V, L, ld] (ld >= 20;
+ * relative to the member's own residue), S_var [V, L], score [V] (fp32: the member's cumulative ddG against the wild type), depth d
+ * (1 <= d <= 8: the size of the children), muts [V, d - 1] (int32: the member's substitutions as q << 5 | b, ascending, distinct
+ * positions; may be NULL when d = 1; a member with a negative entry is DEAD and contributes nothing), allowed_opt [L] (int32, nonzero =
+ * the position may be mutated; NULL = all).
+ * A CANDIDATE is (v, q, b) with member v alive and score[v] not NaN, S_var[v, q] < 20 (unsigned compare: negative = no residue),
+ * b < 20, b != S_var[v, q], q not a position of muts[v], allowed[q] nonzero, b != cysteine (letter 1) unless TMPNN_BEAM_INCLUDE_CYS,
+ * and a value that is not NaN and <= cutoff (+inf removes no candidate). The VALUE is score[v] + ddg[v, q, b]: one IEEE fp32
+ * round-to-nearest add, the only float operation. Its 64-bit KEY is tmpnn_select_hits' order word of the sum's bits (-0.0 taken as
+ * +0.0) in the high word and v << 16 | q << 5 | b in the low word, so L <= 2048 and V <= 65536.
+ * The CHILD SET of a candidate is muts[v] with q << 5 | b added, sorted ascending; two candidates are duplicates when their child sets
+ * are equal. RESULT: walk the candidates in ascending key order, keep a candidate when no earlier candidate has the same child set,
+ * stop after k kept. Every distinct set is so represented by its smallest key: its smallest path value, ties going to the smaller
+ * parent slot, then q, then b.
+ * Outputs, best first: out_muts [k, d] (ascending), out_score [k] (the sum's bits recovered from the key; a -0.0 sum comes back as
+ * +0.0), out_parent [k] (the member's slot), out_S [k, L] (S_var[parent] with q <- b), out_count [1]. Padding rows hold -1 in out_muts
+ * and out_parent, NaN in out_score and 20 in out_S — a legal decoder letter that makes no candidates, so a padded beam can be decoded
+ * and stepped again as it is (its padded rows are dead by their muts).
+ * The caller PROMISES that live members are distinct sets. A child set of size d then has at most d parents in the beam, each with
+ * exactly one candidate, so the first k distinct sets lie within the k d smallest keys; the entry serves k d <= 256. With members that
+ * are not distinct the result is an unspecified subset: still no access outside the buffers, every returned set valid and distinct.
+ * Three launches on `stream`, no atomics (reruns give identical bits): min(items, 8192 / m - 1) workgroups (m = the power of two
+ * >= k d, an item = a member's block of 256 residues) keep their m leaders in LDS and leave k d keys each in the workspace; one
+ * workgroup sorts them, builds the child sets, drops the duplicates and writes the first k; (row, block of 256 residues) writes out_S.
+ * With V == 0 or L == 0 the input pointers may be NULL (and out_S with L == 0); the call writes padding and count 0.
+ * tmpnn_beam_step_workspace_bytes: 0 for sizes that are not served. Errors before any launch: null pointer, k < 1, depth outside
+ * [1, 8], ld < 20, negative sizes, unknown flag bits, NaN cutoff -> TMPNN_E_INVALID; k depth > 256, L > 2048, V > 65536 or
+ * V * L > 2^31 - 1 -> TMPNN_E_UNSUPPORTED; a short workspace -> TMPNN_E_WORKSPACE. */
+enum { TMPNN_BEAM_INCLUDE_CYS = 1 };
+size_t tmpnn_beam_step_workspace_bytes(int64_t V, int64_t L, int k, int depth);   /* 0 for sizes not served */
+int tmpnn_beam_step(const float *ddg, int ld, const int32_t *S_var, const float *score, const int32_t *muts, int depth,
+                    const int32_t *allowed_opt, int64_t V, int64_t L, int k, float cutoff, int flags, int32_t *out_muts,
+                    float *out_score, int32_t *out_parent, int32_t *out_S, int32_t *out_count, void *workspace,
+                    size_t workspace_bytes, tmpnn_stream_t stream);
+
 /* ---- host side: native PDB reader + packer ------------------------------------------
  * Replaces alt_parse_PDB (protein_mpnn_utils.py:183-350) + the packing of tied_featurize (:353-605) for one
  * structure: one pass over the file, all requested chains. `chains` = string of one-letter chain ids in the

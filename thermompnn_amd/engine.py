@@ -484,6 +484,69 @@ class Engine:
                   "tmpnn_select_variant_hits")
         return res
 
+    def beam_step(self, ddg, S_var, score, muts, depth: int, k: int, allowed=None, cutoff: Optional[float] = None,
+                  include_cys: bool = False) -> Dict[str, torch.Tensor]:
+        """One step of a beam search over n-point mutants, all on the device (tmpnn_beam_step: three launches): from the V members of
+        a beam — ``ddg`` [V, L, ld >= 20] float32 (``decode_variants``' tables of the members), ``S_var`` [V, L] their letters,
+        ``score`` [V] their cumulative ddG, ``muts`` [V, depth - 1] their substitutions as q << 5 | b, ascending (None when
+        ``depth`` = 1; a member with a negative entry is dead) — the ``k`` best DISTINCT children of ``depth`` substitutions. A
+        candidate is a substitution b != S_var[v, q] of a residue with S_var[v, q] < 20 at a position q that the member has not
+        mutated and ``allowed`` [L] (None: all) marks nonzero, whose value score[v] + ddg[v, q, b] — one fp32 add — is not NaN and
+        <= ``cutoff`` (None: +inf), cysteine only with ``include_cys``. Candidates that make the same set of substitutions are one
+        child, represented by its smallest (value, parent slot, q, b). The caller promises that live members are distinct sets.
+        -> dict(out_muts [k, depth] and out_parent [k] padded with -1, out_score [k] padded with NaN, out_S [k, L] int32 padded with
+        20, out_count [1]) on the device, best first; a padded result can be decoded and stepped again as it is.
+        1 <= depth <= 8, k * depth <= 256, L <= 2048, V <= 65536, one protein."""
+        if not isinstance(ddg, torch.Tensor) or not ddg.is_cuda or ddg.dtype != torch.float32 or ddg.dim() != 3:
+            raise TmpnnError("beam_step: ddg must be a float32 [V, L, ld] tensor on the device (the tables stay there; there is no CPU path)")
+        V, L, cols = (int(n) for n in ddg.shape)
+        if V > 0 and L > 0 and (ddg.stride(2) != 1 or ddg.stride(1) < cols or ddg.stride(0) != L * ddg.stride(1)):
+            ddg = ddg.contiguous()
+        ld = int(ddg.stride(1)) if V > 0 and L > 0 else cols
+        depth, k = int(depth), int(k)
+        if not 1 <= depth <= _lib.BEAM_MAX_DEPTH:
+            raise TmpnnError(f"beam_step: depth={depth} outside [1, {_lib.BEAM_MAX_DEPTH}]")
+        if k < 1 or k * depth > _lib.BEAM_MAX_KD:
+            raise TmpnnError(f"beam_step: k={k} at depth {depth}: k must be at least 1 and k * depth at most {_lib.BEAM_MAX_KD}")
+        cut = float("inf") if cutoff is None else float(cutoff)
+        if cut != cut:
+            raise TmpnnError("beam_step: the cutoff is NaN")
+        if L > _lib.BEAM_MAX_LEN:
+            raise TmpnnError(f"beam_step: L={L} residues exceed {_lib.BEAM_MAX_LEN}, the key's 11 position bits")
+        if V > _lib.BEAM_MAX_V:
+            raise TmpnnError(f"beam_step: V={V} members exceed {_lib.BEAM_MAX_V}, the key's 16 member bits")
+        dev = self.device
+        S_var, score = self._i32(S_var), self._f32(score)
+        if muts is None:
+            if depth > 1:
+                raise TmpnnError(f"beam_step: depth {depth} needs muts [V, {depth - 1}]")
+        else:
+            muts = self._i32(muts)
+            if tuple(muts.shape) != (V, depth - 1):
+                raise TmpnnError(f"beam_step: muts must be [{V}, {depth - 1}] at depth {depth}, got {tuple(muts.shape)}")
+            if depth == 1:
+                muts = None
+        if allowed is not None:
+            allowed = self._i32(allowed)
+            if allowed.numel() != L:
+                raise TmpnnError(f"beam_step: allowed has {allowed.numel()} entries for {L} residues")
+        if tuple(S_var.shape) != (V, L) or score.numel() != V:
+            raise TmpnnError(f"beam_step: tables {(V, L, cols)} need S_var [V, L] and score [V]; got {tuple(S_var.shape)}, {score.numel()}")
+        need = self.lib.tmpnn_beam_step_workspace_bytes(V, L, k, depth)
+        if need == 0:
+            raise TmpnnError(f"beam_step: sizes not served (V={V}, L={L}, k={k}, depth={depth})")
+        res = dict(out_muts=torch.empty((k, depth), dtype=torch.int32, device=dev), out_score=torch.empty(k, dtype=torch.float32, device=dev),
+                   out_parent=torch.empty(k, dtype=torch.int32, device=dev), out_S=torch.empty((k, L), dtype=torch.int32, device=dev),
+                   out_count=torch.empty(1, dtype=torch.int32, device=dev))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        flags = _lib.BEAM_INCLUDE_CYS if include_cys else 0
+        with torch.cuda.device(dev):
+            check(self.lib.tmpnn_beam_step(_ptr(ddg), ld, _ptr(S_var), _ptr(score), _ptr(muts), depth, _ptr(allowed), V, L, k, cut, flags,
+                                           _ptr(res["out_muts"]), _ptr(res["out_score"]), _ptr(res["out_parent"]),
+                                           _ptr(res["out_S"]) if L > 0 else None, _ptr(res["out_count"]), _ptr(ws), ws.numel(), _stream()),
+                  "tmpnn_beam_step")
+        return res
+
     def pair_map(self, ddg, S_var, base, row, letter, wt, R: int, skip=None, include_cys: bool = False, upper: bool = False,
                  state: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """One chunk of variant tables that is already on the device reduced into a per-(row, position) state (tmpnn_pair_map: two

@@ -159,6 +159,14 @@ class TransferModel(_EngineOwner):
         from .variant_scan import double_mutant_map
         return double_mutant_map(self, pdb, **kw)
 
+    def multi_mutant_search(self, pdb, order: int, beam: int, **kw):
+        """A beam search for the most stabilising mutants of 1 .. ``order`` substitutions of one parsed structure, one list of
+        ``variant_scan.MultiHit`` per level, best first: the backbone is encoded once, every round decodes the beam's sequences in
+        their own backgrounds and one step on the device keeps the ``beam`` best distinct children
+        (``variant_scan.multi_mutant_search``, which documents the number, the coverage and the options)."""
+        from .variant_scan import multi_mutant_search
+        return multi_mutant_search(self, pdb, order, beam, **kw)
+
     def _encode_structure(self, entry):
         """One parsed structure -> its EncodedBackbone (Engine.encode: the part of a forward that never reads the sequence)."""
         device = next(self.parameters()).device

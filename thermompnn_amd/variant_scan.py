@@ -4,6 +4,7 @@ variant with the backbone's edge tiles shared between variants (Engine.decode_va
     python -m thermompnn_amd.variant_scan a.pdb --chain A (--variants FILE | --all-singles) --out x.npz [--synthetic_weights N]
     python -m thermompnn_amd.variant_scan a.pdb --chain A --top-pairs K [--cutoff X] [--include_cys] [--unordered] --out hits.csv
     python -m thermompnn_amd.variant_scan a.pdb --chain A --pair-map [--include_cys] [--unordered] --out map.npz
+    python -m thermompnn_amd.variant_scan a.pdb --chain A --combine N --beam K [--cutoff X] [--include_cys] --out hits.csv
 
 FILE holds one variant per line: a full one-letter sequence of the parsed length, or a comma-separated list of substitutions
 such as ``A12G,K45E`` (wild type, 1-based position in the parsed sequence, new residue). Writes ``tables`` float32 [V, L, 21]
@@ -17,6 +18,11 @@ Limits of the pair selection: L <= 2048, K <= 256, one protein, one rank; the on
 epistasis with theirs, the mean |epistasis| and the number of double mutants, as [L, L] arrays (``double_mutant_map`` / ``PairMap``):
 the same chunk loop, each chunk reduced into the [L, L] state on the device (Engine.pair_map, csrc/tmpnn_pair_map.hip).
 Limits of the pair map: L <= 2048, one protein, one rank; the state is five [L, L] arrays (32 bytes per site pair).
+``--combine N --beam K`` writes the most stabilising mutants of 1 .. N substitutions found by a beam search of width K, one CSV row
+per mutant, levels ascending (``multi_mutant_search`` / ``MultiHit``): every round decodes the beam's sequences in their own
+backgrounds and one step on the device keeps the K best distinct children with their sequence rows (Engine.beam_step,
+csrc/tmpnn_beam.hip); no table goes to the host and no sequence comes back.
+Limits of the beam search: L <= 2048, N <= 8, K * N <= 256, one protein, one rank.
 Not here: the native writer, multi-GPU sharding of the variants, hipGraph capture, the training paths, ProteinMPNN.forward and
 examples/."""
 from __future__ import annotations
@@ -321,9 +327,116 @@ def write_pair_map_npz(path: str, m: PairMap) -> None:
         np.savez(fh, seq=np.array(m.seq), **{name: getattr(m, name) for name in PairMap.ARRAYS})
 
 
-def main(argv=None, _tables: Optional[Callable] = None, _select: Optional[Callable] = None, _reduce: Optional[Callable] = None):
-    """(``_tables`` / ``_select`` / ``_reduce``: the hooks of ``double_mutant_hits`` for --top-pairs and of ``double_mutant_map`` for
-    --pair-map; with ``_tables`` no model is loaded.)"""
+@dataclass
+class MultiHit:
+    """One n-point mutant found by ``multi_mutant_search``: ``mutations`` its substitutions, a tuple of ``Mutation`` ascending by
+    position (``Mutation.ddG``: the wild-type table's entry, what the substitution does alone). ``ddG`` is the fp32 sum of the steps'
+    ddG along the best path found, each step decoded in its own background, which the device ranked; ``ddG_additive`` the sum of the
+    wild-type table's entries and ``epistasis`` = ddG - ddG_additive are computed on the host, in double precision, from the fp32
+    numbers. ``parent``: the rank, in the level below, of the member this one was made from (level 1: 0, the wild type)."""
+    mutations: tuple
+    ddG: float
+    ddG_additive: float
+    epistasis: float
+    parent: int
+
+
+BEAM_MAX_ORDER, BEAM_MAX_KD = 8, 256
+
+
+def multi_mutant_search(model, pdb, order: int, beam: int, positions: Optional[Sequence[int]] = None, cutoff: Optional[float] = None,
+                        include_cys: bool = False, _tables: Optional[Callable] = None, _step: Optional[Callable] = None) -> List[List[MultiHit]]:
+    """A beam search for the most stabilising mutants of 1 .. ``order`` substitutions of one parsed structure -> one list of
+    ``MultiHit`` per level, best first, at most ``beam`` each.
+    What the number is: a mutant's ddG is the SUM OF THE STEPS' ddG ALONG THE BEST PATH FOUND, each step decoded in its own
+    background: level d's members are decoded as they are (the backbone is encoded ONCE; every round is one decode of the beam's
+    sequences plus one ``Engine.beam_step``), and a child's value is its parent's value plus the parent's table entry [q, b], one
+    fp32 add. It is not a sum of single-mutant numbers; ``ddG_additive`` is that sum, and ``epistasis`` the difference.
+    What the search covers: level 1 is exhaustive. A higher level is exhaustive only when the level below held EVERY candidate
+    (its list is shorter than ``beam``); otherwise it holds the best children of the ``beam`` members kept, and a mutant whose every
+    sub-mutant fell out of the beam is never seen.
+    Paths: a set of substitutions can be reached from each of its sub-mutants in the beam, in a different order and with a different
+    sum. All orders whose parent is in the beam are considered and the SMALLEST sum is kept (for a pair: p:a then q:b, and q:b then
+    p:a); ties go to the better-ranked parent.
+    Candidates: every position in ``positions`` (default: every residue with one of the 20 letters) that the member has not mutated,
+    every letter but the member's own, cysteine only with ``include_cys``, a sum that is not NaN and <= ``cutoff``. The tables and the
+    beam stay on the device between rounds; the host reads one count per round and the lists at the end.
+    ValueError: order outside [1, 8], beam < 1, beam * order > 256, more than 2048 residues, a position outside the sequence or
+    without one of the 20 letters.
+    (``_tables(S [V, L]) -> [V, L, 21]`` and ``_step(ddg, S_var, score, muts, depth, k, allowed=, cutoff=, include_cys=)``: the table
+    function and the step, defaults the model's and its engine's.)"""
+    entry = pdb[0] if isinstance(pdb, (list, tuple)) else pdb
+    seq = entry["seq"]
+    L, wt_idx = len(seq), sequence_indices(seq)
+    order, beam = int(order), int(beam)
+    if not 1 <= order <= BEAM_MAX_ORDER:
+        raise ValueError(f"multi_mutant_search: order={order} outside [1, {BEAM_MAX_ORDER}]")
+    if beam < 1 or beam * order > BEAM_MAX_KD:
+        raise ValueError(f"multi_mutant_search: beam={beam} at order {order}: beam must be at least 1 and beam * order at most {BEAM_MAX_KD}")
+    if L > PAIR_MAX_LEN:
+        raise ValueError(f"multi_mutant_search: {L} residues exceed {PAIR_MAX_LEN} (the step's key holds 11 position bits)")
+    allowed = None
+    if positions is not None:
+        allowed = np.zeros(L, dtype=np.int32)
+        for p in positions:
+            if not 0 <= int(p) < L or wt_idx[int(p)] >= 20:
+                raise ValueError(f"position {p}: outside the sequence or a residue without one of the 20 letters")
+            allowed[int(p)] = 1
+    if _tables is None:
+        enc = model._encode_structure(entry)                           # the only encoder run
+        _tables = lambda s: model._tables_over(enc, s)
+    if _step is None:
+        _step = model.engine().beam_step
+    S, score, muts, wt, rounds = wt_idx[None], np.zeros(1, dtype=np.float32), None, None, []
+    for d in range(1, order + 1):
+        t = _tables(S)                                                 # [V, L, 21]: the previous round's tables are free by now
+        if d == 1:
+            wt = t[0]
+        res = _step(t, S, score, muts, d, beam, allowed=allowed, cutoff=cutoff, include_cys=include_cys)
+        del t
+        n = int(res["out_count"][0])                                   # the round's one read on the host
+        if n == 0:
+            break
+        S, score, muts = res["out_S"][:n], res["out_score"][:n], res["out_muts"][:n]
+        rounds.append((res["out_muts"][:n], res["out_score"][:n], res["out_parent"][:n]))
+    table = np.asarray(wt.cpu(), dtype=np.float32)
+    name = entry.get("name", "")
+    levels = []
+    for m_d, s_d, p_d in rounds:
+        m_h, s_h, p_h = (np.asarray(x.cpu()) for x in (m_d, s_d, p_d))
+        hits = []
+        for row, val, par in zip(m_h, s_h, p_h):
+            subs = [(int(e) >> 5, int(e) & 31) for e in row]
+            add = sum(float(table[q, b]) for q, b in subs)
+            hits.append(MultiHit(tuple(Mutation(q, seq[q], ALPHABET[b], float(table[q, b]), name) for q, b in subs), float(val), add,
+                                 float(val) - add, int(par)))
+        levels.append(hits)
+    return levels + [[] for _ in range(order - len(levels))]
+
+
+MULTI_CSV_HEADER = ["order", "rank", "mutations", "ddG", "ddG_additive", "epistasis"]
+
+
+def write_multi_hits_csv(path: str, levels: Sequence[Sequence[MultiHit]]) -> int:
+    """One row per mutant, levels ascending and best first within a level: order (the number of substitutions), rank (0-based within
+    the level), the substitutions in the variant file's notation joined by ':' (``A12G:K45E``: wild type, 1-based position, new
+    residue, ascending by position), then ddG, ddG_additive and epistasis as ``repr`` of the Python floats."""
+    sub = lambda m: f"{m.wildtype}{m.position + 1}{m.mutation}"
+    rows = 0
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh, lineterminator="\n")
+        w.writerow(MULTI_CSV_HEADER)
+        for d, hits in enumerate(levels, 1):
+            for r, h in enumerate(hits):
+                w.writerow([d, r, ":".join(sub(m) for m in h.mutations), repr(h.ddG), repr(h.ddG_additive), repr(h.epistasis)])
+                rows += 1
+    return rows
+
+
+def main(argv=None, _tables: Optional[Callable] = None, _select: Optional[Callable] = None, _reduce: Optional[Callable] = None,
+         _step: Optional[Callable] = None):
+    """(``_tables`` / ``_select`` / ``_reduce`` / ``_step``: the hooks of ``double_mutant_hits`` for --top-pairs, of
+    ``double_mutant_map`` for --pair-map and of ``multi_mutant_search`` for --combine; with ``_tables`` no model is loaded.)"""
     from .custom_inference import load_model
     from .pdb_io import alt_parse_PDB
     ap = argparse.ArgumentParser(description="ThermoMPNN ddG tables of one backbone under many sequence variants on MI355X")
@@ -336,9 +449,12 @@ def main(argv=None, _tables: Optional[Callable] = None, _select: Optional[Callab
                      help="the K most stabilising double mutants, selected on the GPU, as a CSV (1 <= K <= 256)")
     src.add_argument("--pair-map", action="store_true",
                      help="every site pair's best double mutant and epistasis, reduced on the GPU, as an .npz of [L, L] maps")
-    ap.add_argument("--out", required=True, help="output .npz (--top-pairs: .csv)")
-    ap.add_argument("--cutoff", type=float, default=None, help="--top-pairs: keep double mutants with ddG <= cutoff")
-    ap.add_argument("--include_cys", action="store_true", help="--top-pairs, --pair-map: substitutions to cysteine take part")
+    src.add_argument("--combine", type=int, default=None, metavar="N",
+                     help="beam search for the most stabilising mutants of 1 .. N substitutions, on the GPU, as a CSV (needs --beam)")
+    ap.add_argument("--beam", type=int, default=None, metavar="K", help="--combine: mutants kept per level (K * N <= 256)")
+    ap.add_argument("--out", required=True, help="output .npz (--top-pairs, --combine: .csv)")
+    ap.add_argument("--cutoff", type=float, default=None, help="--top-pairs, --combine: keep mutants with ddG <= cutoff")
+    ap.add_argument("--include_cys", action="store_true", help="--top-pairs, --pair-map, --combine: substitutions to cysteine take part")
     ap.add_argument("--unordered", action="store_true",
                     help="--top-pairs, --pair-map: one path per site pair (second site behind the first)")
     ap.add_argument("--model_path", default="")
@@ -347,10 +463,18 @@ def main(argv=None, _tables: Optional[Callable] = None, _select: Optional[Callab
     ap.add_argument("--precision", default=None)
     ap.add_argument("--chunk", type=int, default=256, help="variants decoded per call")
     a = ap.parse_args(argv)
-    if a.top_pairs is None and a.cutoff is not None:
-        ap.error("--cutoff belongs to --top-pairs")
-    if a.top_pairs is None and not a.pair_map and (a.include_cys or a.unordered):
-        ap.error("--include_cys and --unordered belong to --top-pairs and --pair-map")
+    if a.top_pairs is None and a.combine is None and a.cutoff is not None:
+        ap.error("--cutoff belongs to --top-pairs and --combine")
+    if a.top_pairs is None and not a.pair_map and (a.unordered or (a.include_cys and a.combine is None)):
+        ap.error("--include_cys and --unordered belong to --top-pairs and --pair-map (--include_cys to --combine too)")
+    if (a.combine is None) != (a.beam is None):
+        ap.error("--combine N and --beam K go together")
+    if a.combine is not None and not 1 <= a.combine <= BEAM_MAX_ORDER:
+        ap.error(f"--combine {a.combine}: outside [1, {BEAM_MAX_ORDER}]")
+    if a.combine is not None and (a.beam < 1 or a.beam * a.combine > BEAM_MAX_KD):
+        ap.error(f"--beam {a.beam}: at least 1, and --beam times --combine at most {BEAM_MAX_KD}")
+    if a.combine is not None and a.out.endswith(".npz"):
+        ap.error("--combine writes a CSV, not an .npz")
     if a.top_pairs is not None and not 1 <= a.top_pairs <= PAIR_MAX_K:
         ap.error(f"--top-pairs {a.top_pairs}: outside [1, {PAIR_MAX_K}]")
     if a.top_pairs is not None and a.out.endswith(".npz"):
@@ -364,6 +488,13 @@ def main(argv=None, _tables: Optional[Callable] = None, _select: Optional[Callab
                                       chunk=a.chunk, _tables=_tables, _select=_select)
         write_pair_hits_csv(a.out, hits)
         print(f"{len(hits)} double mutants of {len(seq)} residues -> {a.out}")
+        return 0
+    if a.combine is not None:
+        with torch.no_grad():
+            levels = multi_mutant_search(model, pdb, a.combine, a.beam, cutoff=a.cutoff, include_cys=a.include_cys, _tables=_tables,
+                                         _step=_step)
+        rows = write_multi_hits_csv(a.out, levels)
+        print(f"{rows} mutants of 1 .. {a.combine} substitutions of {len(seq)} residues -> {a.out}")
         return 0
     if a.pair_map:
         with torch.no_grad():
