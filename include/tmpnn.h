@@ -716,6 +716,39 @@ int tmpnn_beam_step(const float *ddg, int ld, const int32_t *S_var, const float 
                     float *out_score, int32_t *out_parent, int32_t *out_S, int32_t *out_count, void *workspace,
                     size_t workspace_bytes, tmpnn_stream_t stream);
 
+/* ---- conformer ensembles: per-mutation ddG statistics across the members of an ensemble -------------------------------------------
+ * Whether a substitution is stabilising in ALL NMR models, AF2 ranks or MD frames, or in one conformer only. The members of an
+ * ensemble are a ragged packed batch of tmpnn_ssm_forward (a protein's table does not depend on its batch); this entry reduces the
+ * packed table across the members. All pointers are device pointers: ddg [T, ld] (ld >= 20), S [T] (the row's own letter; negative
+ * or >= 20 = the row takes no part, unsigned compare), desc [E, 4] int32 = (row0, M, L, out_row0) per ensemble: M members of L rows
+ * each, contiguous, member m's position q at table row row0 + m L + q, its results at output rows out_row0 + q. max_len >= every L.
+ * Outputs [T_out, 20] each: mean, spread, lo, hi (fp32), lo_member, hi_member, count, below (int32); status [E] (int32).
+ * The descriptors live in device memory, so the DEVICE checks them, in 64-bit arithmetic: row0, M, L, out_row0 >= 0, L <= max_len,
+ * row0 + M L <= T, out_row0 + L <= T_out. An ensemble that fails gets status[e] = -1 and none of its output rows is written; a good
+ * one gets status[e] = 0. No access ever leaves the buffers. Output ranges that overlap are the caller's error: undefined values,
+ * still inside the buffers.
+ * Per output entry (e, q, b < 20): member m PARTICIPATES when (uint32)S[row] < 20 and x = ddg[row, b] is not NaN (tested on the bits).
+ *   count      the number of participants n;  below  the number of participants with x <= cutoff (+inf counts every one).
+ *   mean       s starts at +0.0 and takes the participants in ASCENDING m, one fp32 round-to-nearest add each; mean = s / (float)n,
+ *              correctly rounded.
+ *   spread     t starts at +0.0; in ascending m: d = x - mean (one subtract), t = t + d * d (one multiply, one add, NOT contracted);
+ *              spread = sqrt(t / (float)n): a correctly rounded divide, then a correctly rounded square root. The population form
+ *              (ddof = 0): the spread of the ensemble as given, 0 for one member.
+ *   Any NaN this arithmetic produces (inf - inf, +inf + -inf) is written as 0x7fc00000.
+ *   lo, lo_member   the smallest key hits_ord(bits(x)) << 32 | m over the participants (hits_ord: tmpnn_pair_map's; -0.0 taken as
+ *              +0.0, +-inf ordinary values): lo_member = that key's m, so ties go to the smallest m; lo = that member's own table
+ *              bits (a -0.0 stays -0.0).
+ *   hi, hi_member   the same with ~hits_ord in the high word: the largest value, ties again to the smallest m.
+ *   n = 0 (M = 0 included): mean, spread, lo, hi = 0x7fc00000, the members -1, count and below 0.
+ * The order of the sums is the contract: every bit is reproducible on a rerun and independent of E, of the ensemble's place in the
+ * batch and of the launch shape. One launch on `stream`, one thread per output entry on a grid of (ceil(20 max_len / 256), E); no
+ * workspace, no atomics. E == 0 is a no-op. Errors before any launch: null pointer (ddg and S may be NULL when T == 0, the outputs
+ * when T_out == 0), ld < 20, negative sizes, NaN cutoff -> TMPNN_E_INVALID; T or T_out > 2^31 - 1, max_len > 8192 or E > 65535 ->
+ * TMPNN_E_UNSUPPORTED. */
+int tmpnn_ensemble_stats(const float *ddg, int ld, const int32_t *S, const int32_t *desc, int E, int64_t T, int64_t T_out,
+                         int max_len, float cutoff, float *mean, float *spread, float *lo, float *hi, int32_t *lo_member,
+                         int32_t *hi_member, int32_t *count, int32_t *below, int32_t *status, tmpnn_stream_t stream);
+
 /* ---- host side: native PDB reader + packer ------------------------------------------
  * Replaces alt_parse_PDB (protein_mpnn_utils.py:183-350) + the packing of tied_featurize (:353-605) for one
  * structure: one pass over the file, all requested chains. `chains` = string of one-letter chain ids in the

@@ -104,6 +104,7 @@ SIGNATURES = {
     "tmpnn_pair_map": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "tmpnn_beam_step_workspace_bytes": (_sz, [_i64, _i64, _i, _i]),
     "tmpnn_beam_step": (_i, [_p, _i, _p, _p, _p, _i, _p, _i64, _i64, _i, C.c_float, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "tmpnn_ensemble_stats": (_i, [_p, _i, _p, _p, _i, _i64, _i64, _i, C.c_float, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "tmpnn_pdb_parse": (_i, [C.c_char_p, C.c_char_p, C.POINTER(_p)]),
     "tmpnn_pdb_parse_batch": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, _i, C.POINTER(_p)]),
     "tmpnn_pdb_parse_batch_status": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, _i, C.POINTER(_p), _p]),
@@ -163,6 +164,9 @@ PMAP_INCLUDE_CYS, PMAP_UPPER, PMAP_CONTINUE = 1, 2, 4      # flags of tmpnn_pair
 PMAP_MAX_LEN = 2048
 BEAM_INCLUDE_CYS = 1                                       # the flag of tmpnn_beam_step
 BEAM_MAX_LEN, BEAM_MAX_V, BEAM_MAX_DEPTH, BEAM_MAX_KD = 2048, 65536, 8, 256   # 11 position and 16 member bits; k * depth <= HITS_MAX_K
+ENS_MAX_LEN, ENS_MAX_E = 8192, 65535                       # tmpnn_ensemble_stats: the forward's own length bound, grid.y
+ENS_ARRAYS = (("mean", "float32"), ("spread", "float32"), ("lo", "float32"), ("hi", "float32"), ("lo_member", "int32"),
+              ("hi_member", "int32"), ("count", "int32"), ("below", "int32"))
 PMAP_STATE = (("best", "int64"), ("eps_lo", "int64"), ("eps_hi", "int64"), ("eps_abs_sum", "float32"), ("count", "int32"))
 
 

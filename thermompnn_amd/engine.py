@@ -604,6 +604,56 @@ class Engine:
                   "tmpnn_pair_map")
         return state
 
+    # -- conformer ensembles -------------------------------------------------------------------------
+    def ensemble_stats(self, ddg, S, members: Sequence[int], lengths: Sequence[int], cutoff: Optional[float] = None) -> Dict[str, torch.Tensor]:
+        """Per-mutation statistics across the members of conformer ensembles, from a packed table that is already on the device
+        (tmpnn_ensemble_stats: one launch, no workspace): ``ddg`` [T, ld >= 20] float32 (``ssm_forward``'s table of the packed
+        members), ``S`` [T] the rows' own letters (>= 20 or negative: the row takes no part), and per ensemble, on the host,
+        ``members`` (M) and ``lengths`` (L): ensemble e is M[e] members of L[e] rows each, the ensembles contiguous and in order, so
+        sum(M L) == T. -> dict(mean, spread, lo, hi float32 and lo_member, hi_member, count, below int32, each [sum(L), 20];
+        offsets [E + 1] of the ensembles' output rows; status [E], 0 for every ensemble this method describes) on the device. The
+        mean is a chain of fp32 adds in ascending member order, the spread the population form around it (include/tmpnn.h has the
+        contract to the operation); ``below`` counts the members at or below ``cutoff`` (None: +inf). L <= 8192."""
+        if not isinstance(ddg, torch.Tensor) or not ddg.is_cuda or ddg.dtype != torch.float32 or ddg.dim() != 2:
+            raise TmpnnError("ensemble_stats: ddg must be a float32 [T, ld] tensor on the device (the table stays there; there is no CPU path)")
+        if ddg.shape[0] > 0 and (ddg.stride(1) != 1 or ddg.stride(0) < ddg.shape[1]):
+            ddg = ddg.contiguous()
+        T, ld = int(ddg.shape[0]), int(ddg.stride(0)) if ddg.shape[0] > 0 else int(ddg.shape[1])
+        cut = float("inf") if cutoff is None else float(cutoff)
+        if cut != cut:
+            raise TmpnnError("ensemble_stats: the cutoff is NaN")
+        M, L = np.asarray(members, dtype=np.int64).reshape(-1), np.asarray(lengths, dtype=np.int64).reshape(-1)
+        E = int(M.size)
+        if L.size != E or (M < 0).any() or (L < 0).any():
+            raise TmpnnError(f"ensemble_stats: members and lengths must be {E} non-negative numbers each, one per ensemble")
+        if E > _lib.ENS_MAX_E:
+            raise TmpnnError(f"ensemble_stats: {E} ensembles exceed {_lib.ENS_MAX_E} per call")
+        max_len = int(L.max()) if E else 0
+        if max_len > _lib.ENS_MAX_LEN:
+            raise TmpnnError(f"ensemble_stats: an ensemble of {max_len} residues exceeds {_lib.ENS_MAX_LEN}, the forward's own bound")
+        if int((M * L).sum()) != T:
+            raise TmpnnError(f"ensemble_stats: the ensembles describe {int((M * L).sum())} rows, the table has {T}")
+        S = self._i32(S)
+        if S.numel() != T:
+            raise TmpnnError(f"ensemble_stats: S has {S.numel()} entries for a table of {T} rows")
+        out_off = np.concatenate([[0], np.cumsum(L)])
+        T_out = int(out_off[-1])
+        if T_out > 0x7fffffff:
+            raise TmpnnError(f"ensemble_stats: {T_out} output rows exceed 2^31 - 1")
+        row0 = np.concatenate([[0], np.cumsum(M * L)])[:-1]
+        dev = self.device
+        desc = torch.from_numpy(np.stack([row0, M, L, out_off[:-1]], axis=1).astype(np.int32).reshape(E, 4)).to(dev)
+        res = {name: torch.empty((T_out, 20), dtype=getattr(torch, dt), device=dev) for name, dt in _lib.ENS_ARRAYS}
+        res["offsets"] = torch.from_numpy(out_off.astype(np.int32)).to(dev)
+        res["status"] = torch.zeros(E, dtype=torch.int32, device=dev)
+        if E == 0:
+            return res
+        with torch.cuda.device(dev):
+            check(self.lib.tmpnn_ensemble_stats(_ptr(ddg) if T > 0 else None, ld, _ptr(S) if T > 0 else None, _ptr(desc), E, T, T_out, max_len,
+                                                cut, *[_ptr(res[name]) if T_out > 0 else None for name, _ in _lib.ENS_ARRAYS],
+                                                _ptr(res["status"]), _stream()), "tmpnn_ensemble_stats")
+        return res
+
     # -- many sequence variants over one backbone ----------------------------------------------------
     def encode(self, X, mask, residue_idx, chain_enc, offsets, max_len: Optional[int] = None,
                precision: Optional[str] = None) -> "EncodedBackbone":

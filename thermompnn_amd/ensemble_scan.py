@@ -1,0 +1,142 @@
+"""Scan conformer ensembles: per-mutation ddG statistics across NMR models, AF2 ranks or MD frames, reduced on the GPU.
+
+    python -m thermompnn_amd.ensemble_scan nmr.pdb [more.pdb ...] --chain A --out stats.npz   (or stats.csv)
+    python -m thermompnn_amd.ensemble_scan rank_0.pdb rank_1.pdb rank_2.pdb --members --chain A --out stats.npz
+    python -m thermompnn_amd.ensemble_scan nmr.pdb --chain A --top 20 --rank worst [--cutoff X] [--min_members N] --out hits.csv
+
+Every multi-MODEL file is one ensemble (``pdb_io.parse_pdb_models``; a file without MODEL records is an ensemble of one); with
+``--members`` all files together are the members of ONE ensemble. All ensembles of a call go through one fused forward per chunk of
+``--chunk_residues`` residues and ONE reduction on the device (``ensemble.scan_ensembles``, csrc/tmpnn_ensemble.hip).
+``.npz``: mean, spread, lo, hi (float32), lo_member, hi_member, count, below (int32), [sum(L), 20] each, rows ``offsets[e] ..
+offsets[e + 1]`` being ensemble e; ``seqs``, ``names``, ``members`` (M per ensemble) and ``member_names``.
+``.csv``: one line per (ensemble, position, letter other than the wild type; positions without a residue in any member have none)
+with the columns ``TABLE_COLUMNS``.
+``--top K``: the K best substitutions of every ensemble by ``--rank`` (mean; worst = the largest ddG over the members, so a hit is
+stabilising in every conformer; best), as a CSV with ``ssm_scan.HIT_COLUMNS`` plus the statistics (``ensemble.select_ensemble_hits``).
+Limits: members of equal length and sequence, L <= 8192, 65 535 ensembles, K <= 256, the released head, one rank, the Python parser."""
+from __future__ import annotations
+
+import argparse
+import csv
+import os
+from typing import List, Sequence
+
+import numpy as np
+import torch
+
+from .datasets import ALPHABET
+from .ensemble import RANKS, STAT_NAMES, scan_ensembles, select_ensemble_hits
+from .ssm_scan import HIT_COLUMNS
+
+TABLE_COLUMNS = ["Model", "Dataset", "pdb", "position", "wildtype", "mutation"] + list(STAT_NAMES)
+
+
+def _num(v) -> str:
+    return repr(float(v)) if isinstance(v, (float, np.floating)) else str(int(v))
+
+
+def write_ensemble_npz(path: str, res: dict) -> None:
+    arrays = {name: res["stats"][name].cpu().numpy() for name in STAT_NAMES}
+    with open(path, "wb") as fh:
+        np.savez(fh, **arrays, offsets=res["stats"]["offsets"].cpu().numpy(), seqs=np.array(res["seqs"]), names=np.array(res["ensemble_names"]),
+                 members=np.array(res["members"], np.int32), member_names=np.array([n for group in res["names"] for n in group]))
+
+
+def write_ensemble_csv(path: str, res: dict, model_name: str = "ThermoMPNN", dataset: str = "custom") -> int:
+    """-> rows written. Floats as repr(float(v)), '\\n' line ends, a running index first, as the other CSVs of the package."""
+    arrays = {name: res["stats"][name].cpu().numpy() for name in STAT_NAMES}
+    offsets = res["stats"]["offsets"].cpu().numpy()
+    n = 0
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh, lineterminator="\n")
+        w.writerow([""] + TABLE_COLUMNS)
+        for e, (seq, name) in enumerate(zip(res["seqs"], res["ensemble_names"])):
+            for q, wt in enumerate(seq):
+                if wt not in ALPHABET[:20]:
+                    continue
+                row = int(offsets[e]) + q
+                for b in range(20):
+                    if ALPHABET[b] == wt:
+                        continue
+                    w.writerow([n, model_name, dataset, name, q, wt, ALPHABET[b]] + [_num(arrays[s][row, b]) for s in STAT_NAMES])
+                    n += 1
+    return n
+
+
+def write_ensemble_hits_csv(path: str, hits: Sequence[Sequence], names: Sequence[str], model_name: str = "ThermoMPNN",
+                            dataset: str = "custom") -> int:
+    n = 0
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh, lineterminator="\n")
+        w.writerow([""] + HIT_COLUMNS + list(STAT_NAMES))
+        for name, group in zip(names, hits):
+            for r, h in enumerate(group):
+                w.writerow([n, model_name, dataset, repr(h.ddG), h.position, h.wildtype, h.mutation, r, name] +
+                           [_num(getattr(h, s)) if s in ("lo_member", "hi_member", "count", "below") else repr(getattr(h, s)) for s in STAT_NAMES])
+                n += 1
+    return n
+
+
+def read_ensembles(paths: Sequence[str], chain, members: bool):
+    """-> (ensembles: lists of parsed members, ensemble names)."""
+    from .pdb_io import parse_pdb_models
+    stem = lambda p: os.path.basename(p)[:-4]
+    parsed = [parse_pdb_models(p, chain) for p in paths]
+    if members:
+        return [[e for group in parsed for e in group]], [stem(paths[0])]
+    return parsed, [stem(p) for p in paths]
+
+
+def main(argv=None) -> int:
+    from .custom_inference import load_model
+    ap = argparse.ArgumentParser(description="ThermoMPNN ddG statistics over conformer ensembles on MI355X")
+    ap.add_argument("pdbs", nargs="+", help="multi-MODEL PDB files, one ensemble each (--members: the members of one ensemble)")
+    ap.add_argument("--chain", default="A")
+    ap.add_argument("--members", action="store_true", help="all files together are the members of ONE ensemble")
+    ap.add_argument("--out", required=True, help="output .npz or .csv (--top: .csv)")
+    ap.add_argument("--top", type=int, default=None, metavar="K", help="the K best substitutions of every ensemble as a CSV (1 <= K <= 256)")
+    ap.add_argument("--rank", default=None, choices=sorted(RANKS), help="--top: the statistic to rank by (default mean)")
+    ap.add_argument("--cutoff", type=float, default=None, help="`below` counts the members with ddG <= cutoff; --top: keep hits <= cutoff")
+    ap.add_argument("--min_members", type=int, default=None, help="--top: only entries in which at least N members take part")
+    ap.add_argument("--include_cys", action="store_true", help="--top: substitutions to cysteine take part")
+    ap.add_argument("--one_per_position", action="store_true", help="--top: each position's best substitution only")
+    ap.add_argument("--model_name", default="ThermoMPNN")
+    ap.add_argument("--dataset", default="custom")
+    ap.add_argument("--model_path", default="")
+    ap.add_argument("--thermompnn_dir", default=".")
+    ap.add_argument("--synthetic_weights", type=int, default=None)
+    ap.add_argument("--precision", default=None)
+    ap.add_argument("--chunk_residues", type=int, default=1 << 18, help="residues per forward")
+    a = ap.parse_args(argv)
+    if a.top is None and (a.rank or a.min_members is not None or a.include_cys or a.one_per_position):
+        ap.error("--rank, --min_members, --include_cys and --one_per_position belong to --top")
+    if a.top is not None and not 1 <= a.top <= 256:
+        ap.error(f"--top {a.top}: a hit list holds 1 to 256 mutations per ensemble")
+    if a.top is not None and not a.out.endswith(".csv"):
+        ap.error("--top writes a CSV (name the output *.csv)")
+    if a.top is None and not a.out.endswith((".npz", ".csv")):
+        ap.error("--out: name the output *.npz or *.csv")
+    if a.cutoff is not None and a.cutoff != a.cutoff:
+        ap.error("--cutoff is NaN")
+    ensembles, names = read_ensembles(a.pdbs, a.chain, a.members)
+    model = load_model(a.model_path or None, a.thermompnn_dir, a.synthetic_weights, precision=a.precision)
+    with torch.no_grad():
+        res = scan_ensembles(model, ensembles, cutoff=a.cutoff, chunk_residues=a.chunk_residues)
+        res["ensemble_names"] = names
+        if a.top is not None:
+            hits: List[list] = select_ensemble_hits(model.engine(), res["stats"], res["seqs"], a.top, a.rank or "mean", a.cutoff,
+                                                    a.include_cys, a.one_per_position, a.min_members)
+            rows = write_ensemble_hits_csv(a.out, hits, names, a.model_name, a.dataset)
+            print(f"{rows} hits of {len(names)} ensembles ({sum(res['members'])} members) -> {a.out}")
+            return 0
+    if a.out.endswith(".npz"):
+        write_ensemble_npz(a.out, res)
+        print(f"{len(names)} ensembles, {sum(res['members'])} members, {sum(len(s) for s in res['seqs'])} positions -> {a.out}")
+    else:
+        rows = write_ensemble_csv(a.out, res, a.model_name, a.dataset)
+        print(f"{rows} rows of {len(names)} ensembles ({sum(res['members'])} members) -> {a.out}")
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

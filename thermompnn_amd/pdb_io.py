@@ -65,20 +65,24 @@ class _ChainAcc:
         return xyz, "".join(seq), list(self.raw_resn)
 
 
-def _scan_pdb(path: str, wanted: Optional[set]) -> Dict[str, _ChainAcc]:
+def _scan_lines(lines, wanted: Optional[set]) -> Dict[str, _ChainAcc]:
     chains: Dict[str, _ChainAcc] = {}
-    with open(path, "rb") as fh:
-        for raw in fh:
-            line = raw.decode("utf-8", "ignore").rstrip()
-            if line[:6] == "HETATM" and line[17:20] == "MSE":     # selenomethionine -> MET (:217-220)
-                line = line.replace("HETATM", "ATOM  ").replace("MSE", "MET")
-            if line[:4] != "ATOM":
-                continue
-            ch = line[21:22]
-            if wanted is not None and ch not in wanted:
-                continue
-            chains.setdefault(ch, _ChainAcc()).add(line)
+    for raw in lines:
+        line = raw.decode("utf-8", "ignore").rstrip()
+        if line[:6] == "HETATM" and line[17:20] == "MSE":     # selenomethionine -> MET (:217-220)
+            line = line.replace("HETATM", "ATOM  ").replace("MSE", "MET")
+        if line[:4] != "ATOM":
+            continue
+        ch = line[21:22]
+        if wanted is not None and ch not in wanted:
+            continue
+        chains.setdefault(ch, _ChainAcc()).add(line)
     return chains
+
+
+def _scan_pdb(path: str, wanted: Optional[set]) -> Dict[str, _ChainAcc]:
+    with open(path, "rb") as fh:
+        return _scan_lines(fh, wanted)
 
 
 def alt_parse_PDB(path_to_pdb: str, input_chain_list=None, ca_only: bool = False, side_chains: bool = False):
@@ -91,8 +95,11 @@ def alt_parse_PDB(path_to_pdb: str, input_chain_list=None, ca_only: bool = False
         raise NotImplementedError("side_chains=True is not on the ThermoMPNN inference path")
     letters = list(input_chain_list) if input_chain_list else list(_DEFAULT_CHAINS)
     atoms = ("CA",) if ca_only else BACKBONE
-    parsed = _scan_pdb(path_to_pdb, set(letters))
+    return [_assemble(_scan_pdb(path_to_pdb, set(letters)), letters, atoms, ca_only, path_to_pdb[path_to_pdb.rfind("/") + 1:-4])]
 
+
+def _assemble(parsed: Dict[str, _ChainAcc], letters, atoms, ca_only: bool, name: str) -> dict:
+    """The scanned chains of one structure -> the entry ``alt_parse_PDB`` returns."""
     out: dict = {"resn_list": []}
     concat = []
     n_found = 0
@@ -112,11 +119,41 @@ def alt_parse_PDB(path_to_pdb: str, input_chain_list=None, ca_only: bool = False
             coords = {f"{a}_chain_{letter}": xyz[:, i, :].tolist() for i, a in enumerate(BACKBONE)}
         out["coords_chain_" + letter] = coords
         n_found += 1
-    out["name"] = path_to_pdb[path_to_pdb.rfind("/") + 1:-4]
+    out["name"] = name
     out["num_of_chains"] = n_found
     out["seq"] = "".join(concat)
     out["resn_list"] = last_resn
-    return [out]
+    return out
+
+
+def parse_pdb_models(path_to_pdb: str, input_chain_list=None, ca_only: bool = False) -> List[dict]:
+    """A multi-MODEL PDB file (NMR models, AF2 ranks, MD frames) -> one ``alt_parse_PDB``-style dict per ``MODEL ... ENDMDL`` block,
+    in file order, named ``<file>_m<serial>`` (the serial of the MODEL record; the block's ordinal where that is no number). Within a
+    block the first occurrence of an atom wins, as in ``alt_parse_PDB``; records outside every block are not read. A file without
+    MODEL records gives exactly ``alt_parse_PDB(path_to_pdb, input_chain_list, ca_only)`` (which, on a multi-MODEL file, still reads
+    the first occurrence of every atom, i.e. the first model). Python parser only: the native reader reads no MODEL records."""
+    blocks, current = [], None
+    with open(path_to_pdb, "rb") as fh:
+        for raw in fh:
+            tag = raw[:6]
+            if tag.rstrip() == b"MODEL":
+                field = raw[10:14].decode("utf-8", "ignore").strip() or raw[5:].decode("utf-8", "ignore").strip()
+                current = [field, []]
+                blocks.append(current)
+            elif tag.startswith(b"ENDMDL"):
+                current = None
+            elif current is not None:
+                current[1].append(raw)
+    if not blocks:
+        return alt_parse_PDB(path_to_pdb, input_chain_list, ca_only)
+    letters = list(input_chain_list) if input_chain_list else list(_DEFAULT_CHAINS)
+    atoms = ("CA",) if ca_only else BACKBONE
+    stem = path_to_pdb[path_to_pdb.rfind("/") + 1:-4]
+    out = []
+    for k, (field, lines) in enumerate(blocks):
+        serial = int(field) if field.lstrip("-").isdigit() else k + 1
+        out.append(_assemble(_scan_lines(lines, set(letters)), letters, atoms, ca_only, f"{stem}_m{serial}"))
+    return out
 
 
 def _chain_letters(entry: dict) -> List[str]:

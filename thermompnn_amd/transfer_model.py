@@ -167,6 +167,25 @@ class TransferModel(_EngineOwner):
         from .variant_scan import multi_mutant_search
         return multi_mutant_search(self, pdb, order, beam, **kw)
 
+    def ensemble_table(self, members, cutoff=None):
+        """Per-mutation statistics across the parsed members of ONE conformer ensemble (``pdb_io.parse_pdb_models`` of a multi-MODEL
+        file, or one ``alt_parse_PDB`` entry per file), as ``ensemble.EnsembleTable``: mean, spread, lo, hi, lo_member, hi_member,
+        count, below, [L, 20] each, on the model's device. One ``tied_featurize``, ONE fused forward over the packed members and ONE
+        reduction on the device (``Engine.ensemble_stats``). ``cutoff`` (None: +inf) is what ``below`` counts against. Serves the
+        released head configuration with ``subtract_mut``; NotImplementedError otherwise."""
+        from .ensemble import ensemble_table
+        return ensemble_table(self, members, cutoff=cutoff)
+
+    def ensemble_hits(self, members, k: int, rank: str = "mean", cutoff=None, include_cys: bool = False, one_per_position: bool = False,
+                      min_members=None):
+        """The ``k`` most stabilising substitutions of one conformer ensemble, best first, as ``ensemble.EnsembleHit``: the
+        statistics of ``ensemble_table`` and ONE selection on the device over the table ``rank`` names — "mean", "worst" (the
+        largest ddG over the members: stabilising in every conformer) or "best" (the smallest). ``min_members`` drops entries in
+        which fewer members take part; the other options are ``hit_list``'s. Only the hits and their statistics are copied back."""
+        from .ensemble import ensemble_hits
+        return ensemble_hits(self, members, k, rank=rank, cutoff=cutoff, include_cys=include_cys, one_per_position=one_per_position,
+                             min_members=min_members)
+
     def _encode_structure(self, entry):
         """One parsed structure -> its EncodedBackbone (Engine.encode: the part of a forward that never reads the sequence)."""
         device = next(self.parameters()).device
