@@ -749,6 +749,44 @@ int tmpnn_ensemble_stats(const float *ddg, int ld, const int32_t *S, const int32
                          int max_len, float cutoff, float *mean, float *spread, float *lo, float *hi, int32_t *lo_member,
                          int32_t *hi_member, int32_t *count, int32_t *below, int32_t *status, tmpnn_stream_t stream);
 
+/* ---- bootstrap confidence intervals of the benchmark metrics (the reference's analysis/bootstrap.py) ------------------------------
+ * B resamples with replacement of a table of N rows, and per resample and prediction column the five metrics of the benchmarking
+ * script. No resample is sorted: the ranks inside a resample follow from one histogram over the tie groups of the original column and
+ * one prefix sum, and every rank sum is an exact integer. All pointers are device pointers.
+ * Inputs: values [C, N] float32, finite: row 0 the measured ddG, rows 1 .. C-1 the M = C - 1 prediction columns, 1 <= M <= 8.
+ *   gid [C, N] int32: gid[c, i] = the 0-based dense rank of values[c, i] among the column's distinct values, equality being IEEE ==
+ *   (-0.0 and +0.0 share a group; torch.unique(sorted=True, return_inverse=True) gives it, once per dataset).
+ *   idx [B, N] int32: the N draws of each of the B resamples. N <= 2^20, B <= 2^20 per call.
+ * Integer statistics of resample b and column c: cnt[g] = the number of draws d with gid[c, idx[b, d]] == g, P its inclusive prefix
+ *   sum, X[g] = P[g - 1] + P[g] + 1 (twice the tie-averaged rank of group g inside the resample). For prediction column m, in int64,
+ *   exactly: Sxy = sum_d X_m X_0, Sxx = sum_d X_m^2, Syy = sum_d X_0^2 (each X at the draw's own group); base = N (N + 1)^2.
+ *   4 N^3 < 2^63 holds up to N = 2^20: the N limit. ranks [B, M, 3] int64 = (Sxy, Sxx, Syy).
+ * metrics [B, M, 5] float64 = (r2, mse, rmse, spearman, pearson), the reference's column order:
+ *   spearman = (Sxy - base) / (sqrt(Sxx - base) sqrt(Syy - base)), from the integers.
+ *   With p, t the column's and the measured value at the draws, mp, mt their means (sum / N), pc = p - mp, tc = t - mt, all float64:
+ *   mse = sum (p - t)^2 / N, rmse = sqrt(mse), r2 = 1 - sum (p - t)^2 / sum tc^2, pearson = sum pc tc / sqrt(sum pc^2 sum tc^2): the
+ *   population forms of the host's metrics.get_metrics, centred on the resample's own means.
+ *   Degeneracy is decided on the integers: Sxx == base (the column is constant inside the resample; N == 1 always is) -> spearman and
+ *   pearson are NaN; Syy == base -> r2 is NaN as well. mse and rmse are always defined.
+ * status [B] int32: 0 fine; -1 an idx entry of the resample is outside [0, N); -2 (when no idx entry is) a gid entry the resample
+ *   meets is outside [0, N). Such a resample writes nothing else: its rows of metrics and ranks keep their bytes. Every index is
+ *   compared with N before it addresses anything: no input makes the kernel read or write outside the buffers.
+ * Determinism: a resample's outputs are a function of its own idx row (and values, gid) only: not of B, the row's slot, the workgroup
+ *   that ran it, the form, or a rerun. The histogram uses integer atomics (no order in the result); there are no float atomics. Order
+ *   of a float64 sum: thread t of 1024 takes the draws t, t + 1024, ... in ascending order; a wavefront folds its 64 threads at
+ *   distances 32, 16, .. 1 (lane l takes lane l + distance); the 16 wavefront sums are added in ascending order. No contraction.
+ * One launch on `stream`, one workgroup per resample on a persistent grid. The histogram and the scanned X of the measured column
+ * (built once per resample) and of the current prediction column are u32 arrays in LDS for N <= 16384 (the LDS form, no workspace:
+ * tmpnn_bootstrap_workspace_bytes is 0 and workspace may be NULL) or in the workspace (larger N, or TMPNN_BOOT_FORCE_WORKSPACE at any
+ * N: min(B, 256) slots of 2 N words). Both forms give the same bits, the float64 outputs included.
+ * B == 0 or N == 0 is a no-op. Errors before any launch: negative sizes, C outside [2, 9], unknown flag bits, null pointer ->
+ * TMPNN_E_INVALID; N or B > 2^20 -> TMPNN_E_UNSUPPORTED; a short workspace -> TMPNN_E_WORKSPACE. */
+enum { TMPNN_BOOT_FORCE_WORKSPACE = 1 };
+size_t tmpnn_bootstrap_workspace_bytes(int C, int64_t N, int64_t B, int flags);   /* 0 for the LDS form and for sizes not served */
+int tmpnn_bootstrap_metrics(const float *values, const int32_t *gid, int C, int64_t N, const int32_t *idx, int64_t B, double *metrics,
+                            int64_t *ranks, int32_t *status, void *workspace, size_t workspace_bytes, int flags,
+                            tmpnn_stream_t stream);
+
 /* ---- host side: native PDB reader + packer ------------------------------------------
  * Replaces alt_parse_PDB (protein_mpnn_utils.py:183-350) + the packing of tied_featurize (:353-605) for one
  * structure: one pass over the file, all requested chains. `chains` = string of one-letter chain ids in the

@@ -105,6 +105,8 @@ SIGNATURES = {
     "tmpnn_beam_step_workspace_bytes": (_sz, [_i64, _i64, _i, _i]),
     "tmpnn_beam_step": (_i, [_p, _i, _p, _p, _p, _i, _p, _i64, _i64, _i, C.c_float, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "tmpnn_ensemble_stats": (_i, [_p, _i, _p, _p, _i, _i64, _i64, _i, C.c_float, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "tmpnn_bootstrap_workspace_bytes": (_sz, [_i, _i64, _i64, _i]),
+    "tmpnn_bootstrap_metrics": (_i, [_p, _p, _i, _i64, _p, _i64, _p, _p, _p, _p, _sz, _i, _p]),
     "tmpnn_pdb_parse": (_i, [C.c_char_p, C.c_char_p, C.POINTER(_p)]),
     "tmpnn_pdb_parse_batch": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, _i, C.POINTER(_p)]),
     "tmpnn_pdb_parse_batch_status": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, _i, C.POINTER(_p), _p]),
@@ -167,6 +169,9 @@ BEAM_MAX_LEN, BEAM_MAX_V, BEAM_MAX_DEPTH, BEAM_MAX_KD = 2048, 65536, 8, 256   # 
 ENS_MAX_LEN, ENS_MAX_E = 8192, 65535                       # tmpnn_ensemble_stats: the forward's own length bound, grid.y
 ENS_ARRAYS = (("mean", "float32"), ("spread", "float32"), ("lo", "float32"), ("hi", "float32"), ("lo_member", "int32"),
               ("hi_member", "int32"), ("count", "int32"), ("below", "int32"))
+BOOT_LDS_N, BOOT_MAX_N, BOOT_MAX_B, BOOT_MAX_M = 16384, 1 << 20, 1 << 20, 8   # tmpnn_bootstrap_metrics: the LDS form's N, 4 N^3 < 2^63
+BOOT_FORCE_WORKSPACE = 1                                   # the flag of tmpnn_bootstrap_metrics
+BOOT_METRICS = ("r2", "mse", "rmse", "spearman", "pearson")
 PMAP_STATE = (("best", "int64"), ("eps_lo", "int64"), ("eps_hi", "int64"), ("eps_abs_sum", "float32"), ("count", "int32"))
 
 

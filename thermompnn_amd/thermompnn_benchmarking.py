@@ -92,10 +92,10 @@ def get_trained_model(model_name, config, checkpt_dir="models/", override_custom
     return model
 
 
-def run_prediction_default(name, model, dataset_name, dataset, results, keep_preds: bool = False):
+def run_prediction_default(name, model, dataset_name, dataset, results, keep_preds: bool = False, scored=None):
     """Reference loop (:87-119): ``model(pdb, mutations)`` per protein, metrics over every mutation with a measured ddG.
     Appends {"Model", "Dataset", "ddG r2" ... "ddG pearson"} to ``results``; with ``keep_preds`` also returns the raw rows
-    (the run_prediction_keep_preds variant, :122-187, without pandas)."""
+    (the run_prediction_keep_preds variant, :122-187, without pandas). ``scored``: a list that receives (pred, measured)."""
     from .metrics import get_metrics
     pred_all, true_all, rows = [], [], []
     for pdb, mutations in dataset:
@@ -114,6 +114,8 @@ def run_prediction_default(name, model, dataset_name, dataset, results, keep_pre
                 rows.append({"Model": name, "Dataset": dataset_name, "ddG_true": float(m.ddG), "ddG_pred": v,
                              "position": m.position, "wildtype": m.wildtype, "mutation": m.mutation,
                              "pdb": (m.pdb or "").strip(".pdb")})
+    if scored is not None:
+        scored.append((pred_all, true_all))
     met = get_metrics(pred_all, true_all)
     column = {"Model": name, "Dataset": dataset_name}
     for k in ("r2", "mse", "rmse", "spearman", "pearson"):
@@ -158,13 +160,14 @@ KEEP_PREDS_COLUMNS = ["WT Seq", "Model", "Dataset", "ddG_true", "ddG_pred", "pos
                       "best_AA", "pdb"]
 
 
-def run_prediction_keep_preds(name, model, dataset_name, dataset, results, centrality: bool = False, out_dir: str = "."):
+def run_prediction_keep_preds(name, model, dataset_name, dataset, results, centrality: bool = False, out_dir: str = ".", scored=None):
     """The reference's evaluation loop that also saves the raw predictions (:122-187): metrics appended to ``results`` as
     ``run_prediction_default`` does, and ``<name>_<dataset_name>_raw_preds.csv`` in the layout its pandas frame gets — the
     unnamed running index, the KEEP_PREDS_COLUMNS, one row per LISTED mutation: a mutation without a measured ddG still gets
     its row with only 'WT Seq' / 'Model' / 'Dataset' filled (:159-167), 'WT Seq' = ``dataset.wt_seqs[key]`` and left empty for
     S669 sets (:166), 'pdb' character-set-stripped (:150), 'neighbors' only with ``centrality``, 'best_AA' always empty.
-    One forward per protein and ONE device-to-host copy of its predictions (the reference syncs twice per mutation)."""
+    One forward per protein and ONE device-to-host copy of its predictions (the reference syncs twice per mutation).
+    ``scored``: a list that receives (pred, measured)."""
     import csv
     import os
     from .metrics import get_metrics
@@ -199,6 +202,8 @@ def run_prediction_keep_preds(name, model, dataset_name, dataset, results, centr
                 wt = dataset.wt_seqs[m.pdb if "Megascale" not in dataset_name else m.pdb + ".pdb"]
                 row["WT Seq"] = "" if wt is None else wt
             rows.append(row)
+    if scored is not None:
+        scored.append((pred_all, true_all))
     met = get_metrics(pred_all, true_all)
     column = {"Model": name, "Dataset": dataset_name}
     for k in ("r2", "mse", "rmse", "spearman", "pearson"):
@@ -213,20 +218,37 @@ def run_prediction_keep_preds(name, model, dataset_name, dataset, results, centr
     return results
 
 
-def evaluate_datasets(models: dict, datasets: dict, keep_preds: bool = False, centrality: bool = False, out_dir: str = "."):
+def evaluate_datasets(models: dict, datasets: dict, keep_preds: bool = False, centrality: bool = False, out_dir: str = ".",
+                      bootstrap: int = 0, seed: int = 0):
     """The driver loop of the reference's benchmarking script (:242-253): every model over every dataset, then
     ``ThermoMPNN_metrics.csv`` (index, Model, Dataset, ddG r2 / mse / rmse / spearman / pearson) in ``out_dir``.
-    -> the list of metric rows (each also carries ``n``, the number of scored mutations)."""
+    -> the list of metric rows (each also carries ``n``, the number of scored mutations).
+    ``bootstrap`` > 0 also writes ``ThermoMPNN_metrics_bootstrap.csv``: Model, Dataset, n and per metric the mean, the standard
+    deviation and the 95 % percentile interval (lo, hi) over that many resamples of the scored mutations (bootstrap.py, on the
+    models' device, draws fixed by ``seed``). The return value and ``ThermoMPNN_metrics.csv`` do not depend on it."""
     import csv
     import os
-    results = []
+    results, boot_rows = [], []
     for name, model in models.items():
         model = model.eval()
         for dataset_name, dataset in datasets.items():
+            scored = [] if bootstrap > 0 else None
             if keep_preds:
-                run_prediction_keep_preds(name, model, dataset_name, dataset, results, centrality=centrality, out_dir=out_dir)
+                run_prediction_keep_preds(name, model, dataset_name, dataset, results, centrality=centrality, out_dir=out_dir, scored=scored)
             else:
-                run_prediction_default(name, model, dataset_name, dataset, results)
+                run_prediction_default(name, model, dataset_name, dataset, results, scored=scored)
+            if scored and len(scored[0][0]) > 0:                          # (a dataset without a scored mutation has no row)
+                from .bootstrap import METRICS, bootstrap_metrics
+                res = bootstrap_metrics(scored[0][0], scored[0][1], bootstrap, seed=seed, device=next(model.parameters()).device)
+                per = res.summary(0.95)[res.names[0]]
+                boot_rows.append([name, dataset_name, res.n] + [per[k][s] for k in METRICS for s in ("mean", "std", "lo", "hi")])
+    if bootstrap > 0:
+        from .bootstrap import METRICS
+        with open(os.path.join(out_dir, "ThermoMPNN_metrics_bootstrap.csv"), "w", newline="") as fh:
+            w = csv.writer(fh, lineterminator="\n")
+            w.writerow(["", "Model", "Dataset", "n"] + [f"ddG {k} {s}" for k in METRICS for s in ("mean", "std", "lo", "hi")])
+            for i, r in enumerate(boot_rows):
+                w.writerow([i] + [("" if isinstance(x, float) and x != x else x) for x in r])
     cols = ["Model", "Dataset"] + [f"ddG {k}" for k in ("r2", "mse", "rmse", "spearman", "pearson")]
     with open(os.path.join(out_dir, "ThermoMPNN_metrics.csv"), "w", newline="") as fh:
         w = csv.writer(fh, lineterminator="\n")
