@@ -22,6 +22,11 @@
 // near-coalesced without an LDS stage); pass 1 over the members makes the sum, the keys and the counts, pass 2 re-reads the same words
 // (L2 hits) for the deviations. Every thread first checks its ensemble's descriptor in 64-bit arithmetic; an ensemble that fails writes
 // status -1 and nothing else. No LDS, no barriers, no workspace, no atomics: every output entry has one writer.
+//
+// TWO FORMS of the one kernel, templated on the addressing. Plain (tmpnn_ensemble_stats): member m's position q is table row
+// row0 + m L + q. Through a row map (tmpnn_ensemble_stats_rows, for members of unequal length that tmpnn_align_global has laid on one
+// axis): the row is rows[map0 + m L + q], and the member is out at q unless (uint32)row < T. Everything behind the row is shared, and
+// the plain form compiles to the instructions it had before the map form existed.
 #include <stdint.h>
 
 #include "tmpnn_internal.h"
@@ -45,6 +50,8 @@ struct EnsArgs {
     float *mean, *spread, *lo, *hi; // [T_out, 20] each
     int32_t *lo_member, *hi_member, *count, *below;
     int32_t *status;                // [E]
+    const int32_t *rows;            // [R]: the form through a row map only (last, so that the plain form's fields stay where they were)
+    int64_t R;
 };
 
 __device__ __forceinline__ bool ens_is_nan(uint32_t bits) { return (bits & 0x7fffffffu) > 0x7f800000u; }
@@ -53,11 +60,23 @@ __device__ __forceinline__ uint32_t ens_canon(float x) {
     return ens_is_nan(b) ? ENS_NAN : b;
 }
 
-__global__ __launch_bounds__(ENS_THREADS) void ens_stats_kernel(EnsArgs a) {
+// Member m's position q -> its table row. The plain form: row0 + m L + q, always a row of the table (the descriptor check). ROWS: the
+// entry rows[row0 + m L + q] of the map (row0 is the descriptor's map0), a row when (uint32)r < T; anything else: the member is out.
+template <bool ROWS> __device__ __forceinline__ bool ens_row(const EnsArgs &a, int64_t row0, int64_t m, int64_t L, int64_t q, int64_t &row) {
+    row = row0 + m * L + q;
+    if (ROWS) {
+        const uint32_t r = (uint32_t)a.rows[row];
+        row = (int64_t)r;
+        return r < (uint32_t)a.T;                                             // (T <= 2^31 - 1: the entry's own bound)
+    }
+    return true;
+}
+
+template <bool ROWS> __global__ __launch_bounds__(ENS_THREADS) void ens_stats_kernel(EnsArgs a) {
     const int e = blockIdx.y;
     const int64_t row0 = a.desc[4 * e], M = a.desc[4 * e + 1], L = a.desc[4 * e + 2], out0 = a.desc[4 * e + 3];
     // (M, L < 2^31: M L < 2^62 and the sums below stay inside int64)
-    const bool ok = row0 >= 0 && M >= 0 && L >= 0 && out0 >= 0 && L <= a.max_len && row0 + M * L <= a.T && out0 + L <= a.T_out;
+    const bool ok = row0 >= 0 && M >= 0 && L >= 0 && out0 >= 0 && L <= a.max_len && row0 + M * L <= (ROWS ? a.R : a.T) && out0 + L <= a.T_out;
     if (blockIdx.x == 0 && threadIdx.x == 0) a.status[e] = ok ? 0 : -1;
     if (!ok) return;
     const int64_t i = (int64_t)blockIdx.x * ENS_THREADS + threadIdx.x;
@@ -71,7 +90,8 @@ __global__ __launch_bounds__(ENS_THREADS) void ens_stats_kernel(EnsArgs a) {
     uint32_t o_lo = 0, o_hi = 0, x_lo = ENS_NAN, x_hi = ENS_NAN;
     int32_t m_lo = -1, m_hi = -1;
     for (int64_t m = 0; m < M; ++m) {
-        const int64_t row = row0 + m * L + q;
+        int64_t row;
+        if (!ens_row<ROWS>(a, row0, m, L, q, row)) continue;
         if ((uint32_t)a.S[row] >= 20u) continue;
         const float x = a.ddg[row * a.ld + b];
         const uint32_t xb = __float_as_uint(x);
@@ -100,7 +120,8 @@ __global__ __launch_bounds__(ENS_THREADS) void ens_stats_kernel(EnsArgs a) {
         // pass 2, ascending m again: d = x - mean, t = t + d * d, three roundings per member
         float t = 0.0f;
         for (int64_t m = 0; m < M; ++m) {
-            const int64_t row = row0 + m * L + q;
+            int64_t row;
+            if (!ens_row<ROWS>(a, row0, m, L, q, row)) continue;
             if ((uint32_t)a.S[row] >= 20u) continue;
             const float x = a.ddg[row * a.ld + b];
             if (ens_is_nan(__float_as_uint(x))) continue;
@@ -121,28 +142,46 @@ __global__ __launch_bounds__(ENS_THREADS) void ens_stats_kernel(EnsArgs a) {
     a.below[at] = below;
 }
 
-// ---- the C-ABI entry ------------------------------------------------------------------------------------------------------------
+// ---- the C-ABI entries ----------------------------------------------------------------------------------------------------------
+// one body for both entries: `what` names the entry in its messages, by_rows picks the form
+static int ens_launch(const char *what, bool by_rows, const float *ddg, int ld, const int32_t *S, const int32_t *rows, int64_t R,
+                      const int32_t *desc, int E, int64_t T, int64_t T_out, int max_len, float cutoff, float *mean, float *spread,
+                      float *lo, float *hi, int32_t *lo_member, int32_t *hi_member, int32_t *count, int32_t *below, int32_t *status,
+                      tmpnn_stream_t stream) {
+    if (E < 0 || T < 0 || T_out < 0 || max_len < 0 || R < 0)
+        return tm_set_error(TMPNN_E_INVALID, "%s: bad sizes (E=%d, T=%lld, T_out=%lld, max_len=%d, R=%lld)", what, E, (long long)T,
+                            (long long)T_out, max_len, (long long)R);
+    if (ld < 20) return tm_set_error(TMPNN_E_INVALID, "%s: ld=%d, a ddG table has at least 20 columns", what, ld);
+    if (cutoff != cutoff) return tm_set_error(TMPNN_E_INVALID, "%s: the cutoff is NaN", what);
+    if ((T > 0 && (!ddg || !S)) || (E > 0 && (!desc || !status)) || (R > 0 && !rows) ||
+        (T_out > 0 && (!mean || !spread || !lo || !hi || !lo_member || !hi_member || !count || !below)))
+        return tm_set_error(TMPNN_E_INVALID, "%s: null pointer", what);
+    if (T > (int64_t)0x7fffffff || T_out > (int64_t)0x7fffffff)
+        return tm_set_error(TMPNN_E_UNSUPPORTED, "%s: T=%lld or T_out=%lld exceeds 2^31 - 1", what, (long long)T, (long long)T_out);
+    if (max_len > ENS_MAX_LEN) return tm_set_error(TMPNN_E_UNSUPPORTED, "%s: max_len=%d exceeds %d", what, max_len, ENS_MAX_LEN);
+    if (E > ENS_MAX_E) return tm_set_error(TMPNN_E_UNSUPPORTED, "%s: E=%d exceeds %d ensembles per call", what, E, ENS_MAX_E);
+    if (E == 0) return TMPNN_OK;
+    const EnsArgs a{ddg, ld, S, desc, T, T_out, max_len, cutoff, mean, spread, lo, hi, lo_member, hi_member, count, below, status, rows, R};
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned gx = max_len > 0 ? (unsigned)((20 * (int64_t)max_len + ENS_THREADS - 1) / ENS_THREADS) : 1u;   // (<= 640; one group
+    tm_prof_begin(by_rows ? "ens_stats_rows" : "ens_stats", st);                                                  //  still writes status)
+    if (by_rows) hipLaunchKernelGGL(ens_stats_kernel<true>, dim3(gx, (unsigned)E), dim3(ENS_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(ens_stats_kernel<false>, dim3(gx, (unsigned)E), dim3(ENS_THREADS), 0, st, a);
+    tm_prof_end(st);
+    return tm_check_launch("ens_stats_kernel");
+}
+
 extern "C" int tmpnn_ensemble_stats(const float *ddg, int ld, const int32_t *S, const int32_t *desc, int E, int64_t T, int64_t T_out,
                                     int max_len, float cutoff, float *mean, float *spread, float *lo, float *hi, int32_t *lo_member,
                                     int32_t *hi_member, int32_t *count, int32_t *below, int32_t *status, tmpnn_stream_t stream) {
-    if (E < 0 || T < 0 || T_out < 0 || max_len < 0)
-        return tm_set_error(TMPNN_E_INVALID, "ensemble_stats: bad sizes (E=%d, T=%lld, T_out=%lld, max_len=%d)", E, (long long)T,
-                            (long long)T_out, max_len);
-    if (ld < 20) return tm_set_error(TMPNN_E_INVALID, "ensemble_stats: ld=%d, a ddG table has at least 20 columns", ld);
-    if (cutoff != cutoff) return tm_set_error(TMPNN_E_INVALID, "ensemble_stats: the cutoff is NaN");
-    if ((T > 0 && (!ddg || !S)) || (E > 0 && (!desc || !status)) ||
-        (T_out > 0 && (!mean || !spread || !lo || !hi || !lo_member || !hi_member || !count || !below)))
-        return tm_set_error(TMPNN_E_INVALID, "ensemble_stats: null pointer");
-    if (T > (int64_t)0x7fffffff || T_out > (int64_t)0x7fffffff)
-        return tm_set_error(TMPNN_E_UNSUPPORTED, "ensemble_stats: T=%lld or T_out=%lld exceeds 2^31 - 1", (long long)T, (long long)T_out);
-    if (max_len > ENS_MAX_LEN) return tm_set_error(TMPNN_E_UNSUPPORTED, "ensemble_stats: max_len=%d exceeds %d", max_len, ENS_MAX_LEN);
-    if (E > ENS_MAX_E) return tm_set_error(TMPNN_E_UNSUPPORTED, "ensemble_stats: E=%d exceeds %d ensembles per call", E, ENS_MAX_E);
-    if (E == 0) return TMPNN_OK;
-    const EnsArgs a{ddg, ld, S, desc, T, T_out, max_len, cutoff, mean, spread, lo, hi, lo_member, hi_member, count, below, status};
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned gx = max_len > 0 ? (unsigned)((20 * (int64_t)max_len + ENS_THREADS - 1) / ENS_THREADS) : 1u;   // (<= 640; one group
-    tm_prof_begin("ens_stats", st);                                                                               //  still writes status)
-    hipLaunchKernelGGL(ens_stats_kernel, dim3(gx, (unsigned)E), dim3(ENS_THREADS), 0, st, a);
-    tm_prof_end(st);
-    return tm_check_launch("ens_stats_kernel");
+    return ens_launch("ensemble_stats", false, ddg, ld, S, nullptr, 0, desc, E, T, T_out, max_len, cutoff, mean, spread, lo, hi, lo_member,
+                      hi_member, count, below, status, stream);
+}
+
+extern "C" int tmpnn_ensemble_stats_rows(const float *ddg, int ld, const int32_t *S, const int32_t *rows, int64_t R, const int32_t *desc,
+                                         int E, int64_t T, int64_t T_out, int max_len, float cutoff, float *mean, float *spread, float *lo,
+                                         float *hi, int32_t *lo_member, int32_t *hi_member, int32_t *count, int32_t *below,
+                                         int32_t *status, tmpnn_stream_t stream) {
+    return ens_launch("ensemble_stats_rows", true, ddg, ld, S, rows, R, desc, E, T, T_out, max_len, cutoff, mean, spread, lo, hi,
+                      lo_member, hi_member, count, below, status, stream);
 }

@@ -605,7 +605,8 @@ class Engine:
         return state
 
     # -- conformer ensembles -------------------------------------------------------------------------
-    def ensemble_stats(self, ddg, S, members: Sequence[int], lengths: Sequence[int], cutoff: Optional[float] = None) -> Dict[str, torch.Tensor]:
+    def ensemble_stats(self, ddg, S, members: Sequence[int], lengths: Sequence[int], cutoff: Optional[float] = None,
+                       rows=None) -> Dict[str, torch.Tensor]:
         """Per-mutation statistics across the members of conformer ensembles, from a packed table that is already on the device
         (tmpnn_ensemble_stats: one launch, no workspace): ``ddg`` [T, ld >= 20] float32 (``ssm_forward``'s table of the packed
         members), ``S`` [T] the rows' own letters (>= 20 or negative: the row takes no part), and per ensemble, on the host,
@@ -613,7 +614,10 @@ class Engine:
         sum(M L) == T. -> dict(mean, spread, lo, hi float32 and lo_member, hi_member, count, below int32, each [sum(L), 20];
         offsets [E + 1] of the ensembles' output rows; status [E], 0 for every ensemble this method describes) on the device. The
         mean is a chain of fp32 adds in ascending member order, the spread the population form around it (include/tmpnn.h has the
-        contract to the operation); ``below`` counts the members at or below ``cutoff`` (None: +inf). L <= 8192."""
+        contract to the operation); ``below`` counts the members at or below ``cutoff`` (None: +inf). L <= 8192.
+        ``rows`` (tmpnn_ensemble_stats_rows): an int32 [sum(M L)] row map, ``align_global``'s ``out`` as it is; member m's position q
+        of ensemble e then reads table row ``rows[map0[e] + m L + q]`` (map0 = the running sum of M L) and is out where that entry is
+        negative or >= T. The table may then have any number of rows: members of unequal length, packed ragged."""
         if not isinstance(ddg, torch.Tensor) or not ddg.is_cuda or ddg.dtype != torch.float32 or ddg.dim() != 2:
             raise TmpnnError("ensemble_stats: ddg must be a float32 [T, ld] tensor on the device (the table stays there; there is no CPU path)")
         if ddg.shape[0] > 0 and (ddg.stride(1) != 1 or ddg.stride(0) < ddg.shape[1]):
@@ -631,7 +635,13 @@ class Engine:
         max_len = int(L.max()) if E else 0
         if max_len > _lib.ENS_MAX_LEN:
             raise TmpnnError(f"ensemble_stats: an ensemble of {max_len} residues exceeds {_lib.ENS_MAX_LEN}, the forward's own bound")
-        if int((M * L).sum()) != T:
+        if rows is not None:
+            rows = self._i32(rows).reshape(-1)
+            if int((M * L).sum()) != rows.numel():
+                raise TmpnnError(f"ensemble_stats: the ensembles describe {int((M * L).sum())} map entries, rows has {rows.numel()}")
+            if T > 0x7fffffff:
+                raise TmpnnError(f"ensemble_stats: {T} table rows exceed 2^31 - 1")
+        elif int((M * L).sum()) != T:
             raise TmpnnError(f"ensemble_stats: the ensembles describe {int((M * L).sum())} rows, the table has {T}")
         S = self._i32(S)
         if S.numel() != T:
@@ -648,10 +658,64 @@ class Engine:
         res["status"] = torch.zeros(E, dtype=torch.int32, device=dev)
         if E == 0:
             return res
+        if rows is not None:
+            R = int(rows.numel())
+            with torch.cuda.device(dev):
+                check(self.lib.tmpnn_ensemble_stats_rows(_ptr(ddg) if T > 0 else None, ld, _ptr(S) if T > 0 else None, _ptr(rows) if R > 0 else None,
+                                                         R, _ptr(desc), E, T, T_out, max_len, cut,
+                                                         *[_ptr(res[name]) if T_out > 0 else None for name, _ in _lib.ENS_ARRAYS],
+                                                         _ptr(res["status"]), _stream()), "tmpnn_ensemble_stats_rows")
+            return res
         with torch.cuda.device(dev):
             check(self.lib.tmpnn_ensemble_stats(_ptr(ddg) if T > 0 else None, ld, _ptr(S) if T > 0 else None, _ptr(desc), E, T, T_out, max_len,
                                                 cut, *[_ptr(res[name]) if T_out > 0 else None for name, _ in _lib.ENS_ARRAYS],
                                                 _ptr(res["status"]), _stream()), "tmpnn_ensemble_stats")
+        return res
+
+    # -- global alignment of letter-code sequences ----------------------------------------------------
+    def align_global(self, A, B, desc, max_n: Optional[int] = None, max_m: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                     slots: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """Global alignments of P pairs of letter-code sequences in one launch (tmpnn_align_global: the rule of
+        ``datasets.global_alignment_map``, identical columns count 1, gaps are free; codes match iff equal and in [0, 20)).
+        ``A``, ``B``: int32 code arrays (all axes, all members, back to back); ``desc`` [P, 6] int32 on the host = (a0, n, b0, m, out0,
+        add) per pair: axis ``A[a0 : a0 + n]`` against ``B[b0 : b0 + m]``. -> dict(out int32: ``out[out0 + q] = add + j`` where axis
+        position q is aligned to member position j, else -1; aligned [P]: the number of aligned columns; status [P]: 0, or -1 for a
+        descriptor the device refused, whose entries are not written) on the device. ``max_n`` / ``max_m``: bounds on every n / m
+        (default: the largest in ``desc``), <= 8192. ``out``: a device buffer to write into (default: one of max(out0 + n) entries,
+        prefilled with -1). ``slots``: workspace slots (default: what tmpnn_align_workspace_bytes asks for P pairs); results do not
+        depend on it."""
+        d = np.ascontiguousarray(np.asarray(desc.cpu() if isinstance(desc, torch.Tensor) else desc, dtype=np.int64).reshape(-1, 6))
+        P = int(d.shape[0])
+        if (np.abs(d) > 0x7fffffff).any():
+            raise TmpnnError("align_global: descriptor fields must fit int32")
+        if max_n is None:
+            max_n = int(d[:, 1].max()) if P else 0
+        if max_m is None:
+            max_m = int(d[:, 3].max()) if P else 0
+        max_n, max_m = max(int(max_n), 0), max(int(max_m), 0)
+        if max_n > _lib.ALIGN_MAX_LEN or max_m > _lib.ALIGN_MAX_LEN:
+            raise TmpnnError(f"align_global: sequences of {max_n} and {max_m} codes exceed {_lib.ALIGN_MAX_LEN}")
+        dev = self.device
+        A, B = self._i32(A).reshape(-1), self._i32(B).reshape(-1)
+        if out is None:
+            good = (d[:, :5] >= 0).all(axis=1)
+            n_out = int((d[good, 4] + d[good, 1]).max()) if good.any() else 0
+            out = torch.full((n_out,), -1, dtype=torch.int32, device=dev)
+        elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.int32 or not out.is_contiguous() or out.dim() != 1:
+            raise TmpnnError("align_global: out must be a contiguous int32 [NO] tensor on the device")
+        res = dict(out=out, aligned=torch.zeros(P, dtype=torch.int32, device=dev), status=torch.zeros(P, dtype=torch.int32, device=dev))
+        if P == 0:
+            return res
+        need = self.lib.tmpnn_align_workspace_bytes(max_n, max_m, P if slots is None else max(int(slots), 1))
+        if need == 0:
+            raise TmpnnError(f"align_global: sizes not served (max_n={max_n}, max_m={max_m}, P={P})")
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        desc_dev = torch.from_numpy(d.astype(np.int32)).to(dev)
+        NA, NB, NO = int(A.numel()), int(B.numel()), int(out.numel())
+        with torch.cuda.device(dev):
+            check(self.lib.tmpnn_align_global(_ptr(A) if NA else None, NA, _ptr(B) if NB else None, NB, _ptr(desc_dev), P, max_n, max_m,
+                                              _ptr(out) if NO else None, NO, _ptr(res["aligned"]), _ptr(res["status"]), _ptr(ws),
+                                              ws.numel(), _stream()), "tmpnn_align_global")
         return res
 
     # -- many sequence variants over one backbone ----------------------------------------------------

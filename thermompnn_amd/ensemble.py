@@ -7,14 +7,25 @@ population spread, the smallest and the largest ddG with the members that hold t
 number of those at or below a cutoff. No table goes to the host. The mean is a chain of fp32 adds in ascending member order and the
 spread is taken around it (include/tmpnn.h has the contract to the operation), so every bit is reproducible.
 
-Members must parse to the same length and to the same letter wherever both have a residue (``align_members``; alignment is out of
-scope). A member's own '-', 'X' and rows with a missing backbone atom drop out of that position only. Limits: L <= 8192, 65 535
+By default members must parse to the same length and to the same letter wherever both have a residue (``align_members``). With
+``align=True`` members of unequal length — several PDB entries or predicted models of one protein that differ in construct
+boundaries, numbering, missing termini, tags or a point substitution — are laid on one axis first: ONE ``Engine.align_global`` per
+scan aligns every member to the axis (``reference`` if given, else member 0's parsed sequence) by the rule of
+``datasets.global_alignment_map`` (identical columns count 1, gaps are free: the reference's ``pairwise2.align.globalxx``), the
+members are featurized at their own lengths and packed ragged, and the kernel's output is, as it is, the row map the statistics read
+through (``Engine.ensemble_stats(rows=)``). Only matching letters align, so a substituted residue is out at its column, and without a
+``reference`` the columns where member 0 holds '-' or 'X' get no participants: pass a reference to cover them. A member whose
+identity (aligned columns / its residues that carry one of the 20 letters) is below ``min_identity`` is refused.
+A member's own '-', 'X' and rows with a missing backbone atom drop out of that position only. Limits: L <= 8192, 65 535
 ensembles per call, the released head configuration with ``subtract_mut``, one rank. Multi-MODEL files are read by the Python parser
-(``pdb_io.parse_pdb_models``) only."""
+(``pdb_io.parse_pdb_models``) only. Out of scope: substitution matrices and gap penalties, multiple-sequence alignment, structural
+superposition."""
 from __future__ import annotations
 
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
+
+import os
 
 import numpy as np
 import torch
@@ -85,6 +96,8 @@ class EnsembleTable:
     below: torch.Tensor
     seq: str
     names: List[str]
+    aligned: Optional[torch.Tensor] = None      # align=True: [M, L] int32, the member's own residue index at every axis column, or -1
+    identity: Optional[torch.Tensor] = None     # align=True: [M] float64, aligned columns / the member's residues with one of the 20 letters
 
 
 @dataclass
@@ -109,30 +122,105 @@ def _check_model(model) -> None:
                                   "lightattn) with subtract_mut only; run ssm_table per member for other configurations")
 
 
-def scan_ensembles(model, ensembles: Sequence[Sequence[dict]], cutoff: Optional[float] = None, chunk_residues: int = 1 << 18) -> dict:
+def read_reference(reference: str) -> str:
+    """``reference``: a sequence as a plain string, or the path of a FASTA file with one record -> the axis sequence (upper case,
+    the 20 letters, 'X' and '-'; ValueError for anything else)."""
+    text = str(reference)
+    if os.path.isfile(text):
+        with open(text) as fh:
+            lines = [ln.strip() for ln in fh if ln.strip()]
+        if sum(ln.startswith(">") for ln in lines) > 1:
+            raise ValueError(f"{text}: a reference is ONE sequence, the file holds {sum(ln.startswith('>') for ln in lines)} records")
+        text = "".join(ln for ln in lines if not ln.startswith(">"))
+    seq = "".join(text.split()).upper()
+    bad = sorted(set(seq) - set(ALPHABET) - {"-"})
+    if not seq or bad:
+        raise ValueError(f"reference: {'an empty sequence' if not seq else 'letters ' + ''.join(bad)} (expected the 20 letters, X or -)")
+    return seq
+
+
+def _letter_codes(seq: str) -> np.ndarray:
+    """The letters as the alignment takes them: 0 .. 19, 'X' 20, '-' (anything else) 21: 20 and 21 match nothing."""
+    return np.array([_CODE.get(c, 20 if c == "X" else 21) for c in seq], np.int32).reshape(-1)
+
+
+def scan_ensembles(model, ensembles: Sequence[Sequence[dict]], cutoff: Optional[float] = None, chunk_residues: int = 1 << 18,
+                   align: bool = False, reference: Optional[str] = None, min_identity: float = 0.9) -> dict:
     """Ensembles (each a list of parsed members) -> dict(stats: what ``Engine.ensemble_stats`` returns over ALL ensembles, rows
     ``offsets[e] .. offsets[e + 1]`` being ensemble e; seqs; names: per ensemble its members' names; members: M per ensemble).
     One ``tied_featurize`` per ensemble, ONE forward per chunk of whole members of at most ``chunk_residues`` residues (a chunk may
-    end inside an ensemble: a member's table does not depend on its batch) into one packed device table, and ONE ``ensemble_stats``."""
+    end inside an ensemble: a member's table does not depend on its batch) into one packed device table, and ONE ``ensemble_stats``.
+    ``align=True``: members of unequal length. Every member, member 0 included, is aligned to the ensemble's axis — ``reference`` (a
+    plain string or a one-record FASTA file, the same for every ensemble) or member 0's parsed sequence — in ONE
+    ``Engine.align_global`` whose output is the row map of the statistics; ``seqs`` are the axes, and the dict gains ``aligned``
+    (per ensemble an int32 [M, L] device tensor: the member's own residue index at every axis column, or -1) and ``identity`` (per
+    ensemble a float64 [M] array: aligned columns / the member's residues that carry one of the 20 letters). ValueError, naming the
+    member and the value, for a member below ``min_identity`` (0 disables it). Only ``aligned`` counts and ``status`` come back."""
     _check_model(model)
+    if not align and reference is not None:
+        raise ValueError("reference= belongs to align=True")
     device = next(model.parameters()).device
     eng = model.engine()
     seqs, names, S_stat, pieces, M_of, L_of = [], [], [], [], [], []
+    axis = read_reference(reference) if reference is not None else None
+    A_codes, B_codes, pair_desc, first_row = [], [], [], []
+    a0 = b0 = map0 = 0
     for entries in ensembles:
         entries = list(entries)
-        seq, S = align_members(entries)
+        if align:
+            if not entries:
+                raise ValueError("an ensemble needs at least one member")
+            seq = axis if axis is not None else entries[0]["seq"]
+            L = len(seq)
+            for m, e in enumerate(entries):
+                n_m = len(e["seq"])
+                if n_m > ENS_MAX_LEN:
+                    raise ValueError(f"ensemble member {m} ({e.get('name', '')}) has {n_m} residues, more than {ENS_MAX_LEN}, the forward's own bound")
+                letters = _letter_codes(e["seq"])
+                own = np.where(letters < 20, letters, 20).astype(np.int32)
+                own[~_backbone_complete(e)] = 20
+                S_stat.append(own)
+                B_codes.append(letters)
+                pair_desc.append((a0, L, b0, n_m, map0 + m * L, b0))          # add = the member's first table row = b0: the same packing
+                first_row.append(b0)
+                b0 += n_m
+            A_codes.append(_letter_codes(seq))
+            a0, map0 = a0 + L, map0 + len(entries) * L
+        else:
+            seq, S = align_members(entries)
+            S_stat.append(S.reshape(-1))
         if len(seq) > ENS_MAX_LEN:
             raise ValueError(f"an ensemble of {len(seq)} residues exceeds {ENS_MAX_LEN}, the forward's own bound")
         seqs.append(seq)
         names.append([e.get("name", "") for e in entries])
-        S_stat.append(S.reshape(-1))
         M_of.append(len(entries))
         L_of.append(len(seq))
         feats = tied_featurize(entries, device, None, None, None, None, None, None, ca_only=False)
         X, S_fwd, mask, chain_enc, residue_idx = feats[0], feats[1], feats[2], feats[5], feats[12]
-        pieces.extend((X[m], S_fwd[m], mask[m], residue_idx[m], chain_enc[m]) for m in range(len(entries)))
-    T = sum(m * l for m, l in zip(M_of, L_of))
+        own_len = [len(e["seq"]) for e in entries]                              # (the pack pads behind a member's own rows)
+        pieces.extend((X[m][:n], S_fwd[m][:n], mask[m][:n], residue_idx[m][:n], chain_enc[m][:n]) for m, n in enumerate(own_len))
+    T = sum(p[0].shape[0] for p in pieces)
     with torch.cuda.device(eng.device):
+        if align:                                                                # before the forward: a refusal costs one small launch
+            cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, np.int32)
+            rows_out = torch.full((map0,), -1, dtype=torch.int32, device=eng.device)
+            al = eng.align_global(cat(A_codes), cat(B_codes), np.array(pair_desc, np.int64).reshape(-1, 6), out=rows_out)
+            counts, status = al["aligned"].cpu().numpy(), al["status"].cpu().numpy()
+            if (status != 0).any():
+                raise RuntimeError(f"align_global refused pair {int(np.flatnonzero(status)[0])}")
+            identity, aligned, k, at = [], [], 0, 0
+            first = torch.as_tensor(np.array(first_row, np.int32), device=eng.device)
+            for e, (M, L) in enumerate(zip(M_of, L_of)):
+                letters = np.array([max(int((B_codes[k + m] < 20).sum()), 1) for m in range(M)], np.float64)
+                ident = counts[k:k + M].astype(np.float64) / letters
+                for m in range(M):
+                    if ident[m] < min_identity:
+                        raise ValueError(f"ensemble member {m} ({names[e][m]}) aligns to the axis of ensemble {e} with identity {ident[m]:.3f}, "
+                                         f"below min_identity {min_identity}: {int(counts[k + m])} of its {int(letters[m])} residues")
+                block = rows_out[at:at + M * L].view(M, L)
+                aligned.append(torch.where(block >= 0, block - first[k:k + M, None], block))
+                identity.append(ident)
+                k, at = k + M, at + M * L
         table = torch.empty((T, 21), dtype=torch.float32, device=eng.device)
         pos, k = 0, 0
         while k < len(pieces):
@@ -149,14 +237,20 @@ def scan_ensembles(model, ensembles: Sequence[Sequence[dict]], cutoff: Optional[
             eng.ssm_forward(X, S_fwd, mask, ridx, cenc, offsets, max_len=max(lens), out={"ddg": table[pos:pos + tot]})
             pos += tot
         S_all = np.concatenate(S_stat) if S_stat else np.zeros(0, np.int32)
-        stats = eng.ensemble_stats(table, S_all, M_of, L_of, cutoff=cutoff)
-    return dict(stats=stats, seqs=seqs, names=names, members=M_of)
+        if not align:
+            stats = eng.ensemble_stats(table, S_all, M_of, L_of, cutoff=cutoff)
+            return dict(stats=stats, seqs=seqs, names=names, members=M_of)
+        stats = eng.ensemble_stats(table, S_all, M_of, L_of, cutoff=cutoff, rows=rows_out)
+    return dict(stats=stats, seqs=seqs, names=names, members=M_of, aligned=aligned, identity=identity)
 
 
-def ensemble_table(model, members: Sequence[dict], cutoff: Optional[float] = None) -> EnsembleTable:
-    """``TransferModel.ensemble_table``: one ensemble -> its ``EnsembleTable``."""
-    res = scan_ensembles(model, [members], cutoff=cutoff)
-    return EnsembleTable(**{name: res["stats"][name] for name in STAT_NAMES}, seq=res["seqs"][0], names=res["names"][0])
+def ensemble_table(model, members: Sequence[dict], cutoff: Optional[float] = None, align: bool = False, reference: Optional[str] = None,
+                   min_identity: float = 0.9) -> EnsembleTable:
+    """``TransferModel.ensemble_table``: one ensemble -> its ``EnsembleTable`` (``align``, ``reference``, ``min_identity``:
+    ``scan_ensembles``)."""
+    res = scan_ensembles(model, [members], cutoff=cutoff, align=align, reference=reference, min_identity=min_identity)
+    extra = dict(aligned=res["aligned"][0], identity=torch.from_numpy(res["identity"][0])) if align else {}
+    return EnsembleTable(**{name: res["stats"][name] for name in STAT_NAMES}, seq=res["seqs"][0], names=res["names"][0], **extra)
 
 
 def select_ensemble_hits(engine, stats: Dict[str, torch.Tensor], seqs: Sequence[str], k: int, rank: str = "mean",
@@ -195,10 +289,12 @@ def select_ensemble_hits(engine, stats: Dict[str, torch.Tensor], seqs: Sequence[
 
 
 def ensemble_hits(model, members: Sequence[dict], k: int, rank: str = "mean", cutoff: Optional[float] = None, include_cys: bool = False,
-                  one_per_position: bool = False, min_members: Optional[int] = None) -> List[EnsembleHit]:
+                  one_per_position: bool = False, min_members: Optional[int] = None, align: bool = False, reference: Optional[str] = None,
+                  min_identity: float = 0.9) -> List[EnsembleHit]:
     """``TransferModel.ensemble_hits``: the ``k`` best substitutions of one ensemble by ``rank``. ``cutoff`` keeps hits whose ranked
-    statistic is <= cutoff, and is the cutoff of ``below`` as well."""
+    statistic is <= cutoff, and is the cutoff of ``below`` as well. ``align``, ``reference``, ``min_identity``: ``scan_ensembles``;
+    positions and wild-type letters are then the axis'."""
     if rank not in RANKS:
         raise ValueError(f"rank={rank!r}: one of {sorted(RANKS)}")
-    res = scan_ensembles(model, [members], cutoff=cutoff)
+    res = scan_ensembles(model, [members], cutoff=cutoff, align=align, reference=reference, min_identity=min_identity)
     return select_ensemble_hits(model.engine(), res["stats"], res["seqs"], k, rank, cutoff, include_cys, one_per_position, min_members)[0]

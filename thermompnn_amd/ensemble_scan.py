@@ -13,7 +13,13 @@ offsets[e + 1]`` being ensemble e; ``seqs``, ``names``, ``members`` (M per ensem
 with the columns ``TABLE_COLUMNS``.
 ``--top K``: the K best substitutions of every ensemble by ``--rank`` (mean; worst = the largest ddG over the members, so a hit is
 stabilising in every conformer; best), as a CSV with ``ssm_scan.HIT_COLUMNS`` plus the statistics (``ensemble.select_ensemble_hits``).
-Limits: members of equal length and sequence, L <= 8192, 65 535 ensembles, K <= 256, the released head, one rank, the Python parser."""
+``--align``: members of unequal length (construct boundaries, numbering, missing termini, tags, a point substitution) are aligned on
+the device to ``--reference`` (a sequence or a one-record FASTA file; default: member 0's sequence) by the rule of
+``datasets.global_alignment_map``; a member below ``--min_identity`` (default 0.9; 0 disables it) is refused. The ``.npz`` gains
+``aligned`` (int32, flat: ensemble e's block of members[e] x L_e entries, member-local residue index or -1, the blocks in order) and
+``identity`` (float64, one per member); the CSV layouts do not change.
+Limits: without --align members of equal length and sequence; L <= 8192, 65 535 ensembles, K <= 256, the released head, one rank, the
+Python parser."""
 from __future__ import annotations
 
 import argparse
@@ -37,6 +43,9 @@ def _num(v) -> str:
 
 def write_ensemble_npz(path: str, res: dict) -> None:
     arrays = {name: res["stats"][name].cpu().numpy() for name in STAT_NAMES}
+    if "aligned" in res:
+        arrays["aligned"] = np.concatenate([a.cpu().numpy().reshape(-1) for a in res["aligned"]] + [np.zeros(0, np.int32)]).astype(np.int32)
+        arrays["identity"] = np.concatenate(list(res["identity"]) + [np.zeros(0, np.float64)])
     with open(path, "wb") as fh:
         np.savez(fh, **arrays, offsets=res["stats"]["offsets"].cpu().numpy(), seqs=np.array(res["seqs"]), names=np.array(res["ensemble_names"]),
                  members=np.array(res["members"], np.int32), member_names=np.array([n for group in res["names"] for n in group]))
@@ -107,7 +116,12 @@ def main(argv=None) -> int:
     ap.add_argument("--synthetic_weights", type=int, default=None)
     ap.add_argument("--precision", default=None)
     ap.add_argument("--chunk_residues", type=int, default=1 << 18, help="residues per forward")
+    ap.add_argument("--align", action="store_true", help="align members of unequal length to the axis on the device")
+    ap.add_argument("--reference", default=None, metavar="SEQ|FASTA", help="--align: the axis, a sequence or a one-record FASTA file (default: member 0)")
+    ap.add_argument("--min_identity", type=float, default=None, metavar="F", help="--align: refuse members below this identity (default 0.9; 0: none)")
     a = ap.parse_args(argv)
+    if not a.align and (a.reference is not None or a.min_identity is not None):
+        ap.error("--reference and --min_identity belong to --align")
     if a.top is None and (a.rank or a.min_members is not None or a.include_cys or a.one_per_position):
         ap.error("--rank, --min_members, --include_cys and --one_per_position belong to --top")
     if a.top is not None and not 1 <= a.top <= 256:
@@ -121,7 +135,8 @@ def main(argv=None) -> int:
     ensembles, names = read_ensembles(a.pdbs, a.chain, a.members)
     model = load_model(a.model_path or None, a.thermompnn_dir, a.synthetic_weights, precision=a.precision)
     with torch.no_grad():
-        res = scan_ensembles(model, ensembles, cutoff=a.cutoff, chunk_residues=a.chunk_residues)
+        res = scan_ensembles(model, ensembles, cutoff=a.cutoff, chunk_residues=a.chunk_residues, align=a.align, reference=a.reference,
+                             min_identity=0.9 if a.min_identity is None else a.min_identity)
         res["ensemble_names"] = names
         if a.top is not None:
             hits: List[list] = select_ensemble_hits(model.engine(), res["stats"], res["seqs"], a.top, a.rank or "mean", a.cutoff,

@@ -167,24 +167,28 @@ class TransferModel(_EngineOwner):
         from .variant_scan import multi_mutant_search
         return multi_mutant_search(self, pdb, order, beam, **kw)
 
-    def ensemble_table(self, members, cutoff=None):
+    def ensemble_table(self, members, cutoff=None, align: bool = False, reference=None, min_identity: float = 0.9):
         """Per-mutation statistics across the parsed members of ONE conformer ensemble (``pdb_io.parse_pdb_models`` of a multi-MODEL
         file, or one ``alt_parse_PDB`` entry per file), as ``ensemble.EnsembleTable``: mean, spread, lo, hi, lo_member, hi_member,
         count, below, [L, 20] each, on the model's device. One ``tied_featurize``, ONE fused forward over the packed members and ONE
         reduction on the device (``Engine.ensemble_stats``). ``cutoff`` (None: +inf) is what ``below`` counts against. Serves the
-        released head configuration with ``subtract_mut``; NotImplementedError otherwise."""
+        released head configuration with ``subtract_mut``; NotImplementedError otherwise. ``align=True``: members of unequal length are
+        aligned on the device to ``reference`` (a sequence string or a one-record FASTA file; default: member 0's sequence) by the
+        rule of ``datasets.global_alignment_map`` and the statistics read through that map; the table gains ``aligned`` and
+        ``identity``, and a member below ``min_identity`` raises ValueError (``ensemble.scan_ensembles``)."""
         from .ensemble import ensemble_table
-        return ensemble_table(self, members, cutoff=cutoff)
+        return ensemble_table(self, members, cutoff=cutoff, align=align, reference=reference, min_identity=min_identity)
 
     def ensemble_hits(self, members, k: int, rank: str = "mean", cutoff=None, include_cys: bool = False, one_per_position: bool = False,
-                      min_members=None):
+                      min_members=None, align: bool = False, reference=None, min_identity: float = 0.9):
         """The ``k`` most stabilising substitutions of one conformer ensemble, best first, as ``ensemble.EnsembleHit``: the
         statistics of ``ensemble_table`` and ONE selection on the device over the table ``rank`` names — "mean", "worst" (the
         largest ddG over the members: stabilising in every conformer) or "best" (the smallest). ``min_members`` drops entries in
-        which fewer members take part; the other options are ``hit_list``'s. Only the hits and their statistics are copied back."""
+        which fewer members take part; the other options are ``hit_list``'s. Only the hits and their statistics are copied back.
+        ``align``, ``reference``, ``min_identity``: as ``ensemble_table``; positions are then the axis'."""
         from .ensemble import ensemble_hits
         return ensemble_hits(self, members, k, rank=rank, cutoff=cutoff, include_cys=include_cys, one_per_position=one_per_position,
-                             min_members=min_members)
+                             min_members=min_members, align=align, reference=reference, min_identity=min_identity)
 
     def _encode_structure(self, entry):
         """One parsed structure -> its EncodedBackbone (Engine.encode: the part of a forward that never reads the sequence)."""
