@@ -1,6 +1,7 @@
 """Generate the C-alpha-only (ca_only) fixtures by IMPORTING THE REFERENCE (runs only in the build container, on the CPU).
 
-    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_ca_golden.py
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_ca_golden.py            (every file)
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_ca_golden.py off_tile   (ca_msk_L17 / L47 / L49 only)
 
 Builds the reference's ProteinMPNN(ca_only=True) with thermompnn_amd.weights.synthetic_state_dict(0, "mpnn_ca") (strict load) and
 runs it in float32 and in float64 (default dtype float64 and Tensor.float -> double for the duration of the run: the reference's
@@ -18,6 +19,8 @@ ca_<case>.npz, every array with a leading batch axis B:
     min_window_margin: the smallest distance of a C-alpha step length from 3.6 and 4.0 (asserted >= 1e-3).
 Ties: torch.topk is replaced by a stable sort for the whole script (equal distances: lowest index first, the engine's rule).
 Cases: syn_L32 (Keff 32 < 48), syn_L40 with k_neighbors = 30, msk_L40, msk_L56_2ch (tests/masked_backbones.py: missing C-alpha -> 0),
+msk_L17, msk_L47 and msk_L49 at K = 48 (Keff 17, 47 and 48: off-tile row counts with missing C-alpha atoms; the layouts as they are,
+no translation and no other seed was needed for the conditions below),
 pad_L32_L40 (syn_L32 and syn_L40 as one padded batch, K = 48), 2OCJ_A and 2OCJ_AB through the reference's alt_parse_PDB(ca_only=True)
 and tied_featurize(ca_only=True). Never batch size 3 or padded length 6: the reference's torch.cross calls pass no dim.
 ca_params.npz: names and shapes of the reference model's state_dict(). ca_parse_2OCJ.npz: what the reference's parser and packer
@@ -36,6 +39,7 @@ import make_tied_sample_golden as mts
 
 sys.path.insert(0, os.path.join(mg.REPO, "tests"))
 import ca_restatement as car                               # noqa: E402
+from ca_inputs import frame_conditioned                    # noqa: E402
 from masked_backbones import layout_arrays                 # noqa: E402
 from thermompnn_amd.synthetic import AA20, synthetic_backbone   # noqa: E402
 from thermompnn_amd.weights import synthetic_state_dict    # noqa: E402
@@ -156,9 +160,14 @@ def run(c, K, f64, graph=None):
     return dict(E=cap["E"].numpy(), E_idx=cap["E_idx"].numpy(), hidden=np.stack([cap[f"h{l}"].numpy() for l in range(3)]), log_probs=lp.numpy())
 
 
-def store_case(name, c, K, want_hidden=True, rows=None):
+def store_case(name, c, K, want_hidden=True, rows=None, new_rules=False):
+    """``new_rules`` (the cases added after ca_inputs.frame_conditioned existed): every framed row passes frame_conditioned and the
+    ill-conditioned share is at most 10 %, asserted here; the earlier cases keep their files byte for byte."""
     margin = window_margin(c)
     assert margin >= 1e-3, (name, margin)
+    if new_rules:
+        for b in range(c["Ca"].shape[0]):
+            assert bool(frame_conditioned(torch.from_numpy(c["Ca"][b]).double()).all()), (name, b)
     r32 = run(c, K, False)
     r64 = run(c, K, True, graph=r32["E_idx"])
     assert np.array_equal(r32["E_idx"], r64["E_idx"])
@@ -174,6 +183,7 @@ def store_case(name, c, K, want_hidden=True, rows=None):
         err = float((Er - t(r64["E"][b])).abs().max())
         assert err <= 1e-12, (name, b, err)
     d = np.abs(r32["E"].astype(np.float64) - r64["E"]).max(-1)
+    assert not new_rules or float((~well).mean()) <= 0.10, (name, float((~well).mean()))
     out = dict(Ca=c["Ca"].astype(np.float32), S=c["S"].astype(np.int16), mask=c["mask"].astype(np.float32), residue_idx=c["residue_idx"].astype(np.int32),
                chain_enc=c["chain_enc"].astype(np.int16), K=np.int32(K), E_idx=E_idx.astype(np.int16), rows=np.array(rows, np.int32),
                E64_rows=r64["E"][:, rows], ref32_well=np.float64(d[well].max()), ref32_ill=np.float64(d[~well].max() if (~well).any() else 0.0),
@@ -206,9 +216,20 @@ def probs_case(name, c, n):
     print(f"ca_probs_{name}: {int((cond != 0).any(-1).sum())} conditional rows of {L}")
 
 
+OFF_TILE = ("msk_L17", "msk_L47", "msk_L49")
+
+
+def off_tile_cases():
+    for name in OFF_TILE:
+        m = single(name)
+        store_case(name, {k: v[None] for k, v in m.items()}, 48, new_rules=True)
+
+
 def main():
     torch.manual_seed(0)
     torch.topk = stable_topk                                # for every run of the reference below
+    if sys.argv[1:] == ["off_tile"]:                        # only the cases added later: the other files are left as they are
+        return off_tile_cases()
     with torch.no_grad():
         sd = ca_model(48).state_dict()
     np.savez_compressed(os.path.join(HERE, "ca_params.npz"), names=np.array(list(sd)), shapes=np.array(json.dumps([list(v.shape) for v in sd.values()])))
@@ -218,6 +239,7 @@ def main():
     store_case("syn_L40", one(singles["syn_L40"]), 30)
     store_case("msk_L40", one(singles["msk_L40"]), 48)
     store_case("msk_L56_2ch", one(singles["msk_L56_2ch"]), 48)
+    off_tile_cases()
     store_case("pad_L32_L40", padded([singles["syn_L32"], singles["syn_L40"]]), 48, rows=[0, 1, 29, 30, 31, 32, 38, 39])   # (the shorter member's end)
     pdb = os.path.join(HERE, "2OCJ.pdb")
     parse = {}

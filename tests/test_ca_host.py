@@ -12,7 +12,7 @@ import torch
 import ca_restatement as car
 from conftest import GOLDEN, load_golden
 
-CASES = ["syn_L32", "syn_L40", "msk_L40", "msk_L56_2ch", "pad_L32_L40", "2OCJ_A", "2OCJ_AB"]
+CASES = ["syn_L32", "syn_L40", "msk_L40", "msk_L56_2ch", "pad_L32_L40", "2OCJ_A", "2OCJ_AB", "msk_L17", "msk_L47", "msk_L49"]
 
 
 def ca_weights():

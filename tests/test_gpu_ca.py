@@ -25,7 +25,7 @@ TOL_INTERMEDIATE = 1e-5
 F64_FACTOR = 2.5
 ILL_CAP = 0.10
 PRECISIONS = ["fp32", "f16x2", "bf16x3"]
-SMALL = ["syn_L32", "syn_L40", "msk_L40", "msk_L56_2ch", "pad_L32_L40"]
+SMALL = ["syn_L32", "syn_L40", "msk_L40", "msk_L56_2ch", "pad_L32_L40", "msk_L17", "msk_L47", "msk_L49"]
 CASES = SMALL + ["2OCJ_A", "2OCJ_AB"]
 _ENGINES, _MODELS, _TRUTH = {}, {}, {}
 
