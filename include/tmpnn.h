@@ -715,6 +715,37 @@ int tmpnn_beam_step(const float *ddg, int ld, const int32_t *S_var, const float 
                     const int32_t *allowed_opt, int64_t V, int64_t L, int k, float cutoff, int flags, int32_t *out_muts,
                     float *out_score, int32_t *out_parent, int32_t *out_S, int32_t *out_count, void *workspace,
                     size_t workspace_bytes, tmpnn_stream_t stream);
+/* The same step for P PROTEINS of a packed axis of T rows in one call: row v of the [V, T] arrays holds beam slot v of EVERY protein,
+ * so one tmpnn_decode_variants per round serves the whole pack. All pointers are device pointers: ddg [V, T, ld] (ld >= 20), S_var
+ * [V, T], score [P, V], muts [P, V, d - 1] (words q << 5 | b with q the position WITHIN the protein; NULL allowed at d = 1; a member
+ * with a negative entry is dead), allowed_opt [T] or NULL, offsets [P + 1] (int32, as for tmpnn_select_hits). For protein p with rows
+ * [o_p, o_p + L_p) = [offsets[p], offsets[p + 1]) everything is tmpnn_beam_step's contract, word for word — the candidate rule, the one
+ * fp32 add, the key hits_ord(sum) << 32 | v << 16 | q << 5 | b, the child sets, the walk, the padding, the caller's promise and
+ * k d <= 256 — applied to ddg[:, o_p : o_p + L_p], S_var[:, o_p : o_p + L_p], score[p], muts[p] and allowed[o_p : o_p + L_p].
+ * Outputs: out_muts [P, k, d], out_score [P, k], out_parent [P, k], out_count [P], and out_S [k, T]: row r holds, in protein p's
+ * columns, the sequence of p's r-th child, 20 there in p's padding rows. The outputs are the next round's S_var, score and muts as they
+ * stand, with V = k.
+ * The offsets live in device memory, so the DEVICE checks them, in 64-bit arithmetic: 0 <= offsets[p] <= offsets[p + 1] <= T and
+ * L_p <= max_len (<= 2048). Every workgroup of a protein evaluates the same predicate. A protein that fails gets out_count[p] = -1 and
+ * padding in its out_muts, out_score and out_parent; no column of out_S is written for it and none of its table rows, scores or
+ * substitutions is read; its neighbours are served. L_p = 0 is a good protein with count 0. No access ever leaves the buffers. Columns
+ * of out_S that two proteins both claim are the caller's error: undefined values, still inside the buffers.
+ * Three launches on `stream`, no atomics, no grid barrier: slots (p, w), W = min(V ceil(max_len / 256), 8192 / m - 1) per protein (m =
+ * the power of two >= k d), where (p, w) loops over p's own items w, w + W, ... (an item = a member's block of 256 of p's rows), keeps m
+ * leaders in LDS and leaves k d keys in the workspace; one workgroup per protein sorts them, builds the child sets, drops the
+ * duplicates and writes the first k and the padding; (protein, kept row, block of 256 rows) writes out_S. Each grid is capped at 8192
+ * workgroups that loop over their slots. Every output bit of a protein is independent of P, of its place in the pack, of W, of the
+ * grid, and of a rerun.
+ * With P == 0 nothing is launched. With V == 0 or T == 0 every input pointer may be NULL, offsets included: they are not read, every
+ * protein gets count 0 and padding, and out_S (which may be NULL when T == 0) is not written.
+ * tmpnn_beam_step_each_workspace_bytes: P W k d keys of 8 bytes plus P k words; 0 for sizes that are not served. Errors before any
+ * launch: null pointer, k < 1, depth outside [1, 8], ld < 20, negative sizes, unknown flag bits, NaN cutoff -> TMPNN_E_INVALID;
+ * k depth > 256, max_len > 2048, V > 65536 or V * T > 2^31 - 1 -> TMPNN_E_UNSUPPORTED; a short workspace -> TMPNN_E_WORKSPACE. */
+size_t tmpnn_beam_step_each_workspace_bytes(int P, int64_t V, int max_len, int k, int depth);   /* 0 for sizes not served */
+int tmpnn_beam_step_each(const float *ddg, int ld, const int32_t *S_var, const float *score, const int32_t *muts, int depth,
+                         const int32_t *allowed_opt, const int32_t *offsets, int P, int64_t T, int64_t V, int max_len, int k,
+                         float cutoff, int flags, int32_t *out_muts, float *out_score, int32_t *out_parent, int32_t *out_S,
+                         int32_t *out_count, void *workspace, size_t workspace_bytes, tmpnn_stream_t stream);
 
 /* ---- conformer ensembles: per-mutation ddG statistics across the members of an ensemble -------------------------------------------
  * Whether a substitution is stabilising in ALL NMR models, AF2 ranks or MD frames, or in one conformer only. The members of an

@@ -104,6 +104,9 @@ SIGNATURES = {
     "tmpnn_pair_map": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "tmpnn_beam_step_workspace_bytes": (_sz, [_i64, _i64, _i, _i]),
     "tmpnn_beam_step": (_i, [_p, _i, _p, _p, _p, _i, _p, _i64, _i64, _i, C.c_float, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "tmpnn_beam_step_each_workspace_bytes": (_sz, [_i, _i64, _i, _i, _i]),
+    "tmpnn_beam_step_each": (_i, [_p, _i, _p, _p, _p, _i, _p, _p, _i, _i64, _i64, _i, _i, C.c_float, _i, _p, _p, _p, _p, _p, _p, _sz,
+                                  _p]),
     "tmpnn_ensemble_stats": (_i, [_p, _i, _p, _p, _i, _i64, _i64, _i, C.c_float, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "tmpnn_ensemble_stats_rows": (_i, [_p, _i, _p, _p, _i64, _p, _i, _i64, _i64, _i, C.c_float, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "tmpnn_align_workspace_bytes": (_sz, [_i, _i, _i64]),

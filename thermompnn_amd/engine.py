@@ -547,6 +547,81 @@ class Engine:
                   "tmpnn_beam_step")
         return res
 
+    def beam_step_each(self, ddg, S_var, score, muts, offsets, depth: int, k: int, allowed=None, cutoff: Optional[float] = None,
+                       include_cys: bool = False, max_len: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """``beam_step`` for the P proteins of a packed axis of T rows in one call (tmpnn_beam_step_each: three launches): ``ddg``
+        [V, T, ld >= 20] float32 (``decode_variants``' tables over the pack: row v holds beam slot v of every protein), ``S_var``
+        [V, T], ``score`` [P, V], ``muts`` [P, V, depth - 1] (q << 5 | b with q the position within the protein; None when ``depth``
+        = 1), ``offsets`` [P + 1], ``allowed`` [T] or None. Protein p gets exactly what ``beam_step`` gives on its slice
+        ddg[:, o_p : o_p + L_p], S_var[:, o_p : o_p + L_p], score[p], muts[p], allowed[o_p : o_p + L_p]: every bit, wherever it lies
+        in the pack. -> dict(out_muts [P, k, depth], out_score [P, k], out_parent [P, k], out_count [P], out_S [k, T]) on the device;
+        they are the next round's ``muts``, ``score`` and ``S_var`` as they stand. The device checks the offsets: a protein whose
+        range is not inside [0, T], descends or is longer than ``max_len`` gets count -1 and padding, and its columns of ``out_S``
+        keep the 20 they are allocated with. ``max_len``: the longest protein (derived from host offsets; needed with offsets on
+        the device). 1 <= depth <= 8, k * depth <= 256, every protein <= 2048 rows, V <= 65536, V * T <= 2**31 - 1."""
+        if not isinstance(ddg, torch.Tensor) or not ddg.is_cuda or ddg.dtype != torch.float32 or ddg.dim() != 3:
+            raise TmpnnError("beam_step_each: ddg must be a float32 [V, T, ld] tensor on the device (the tables stay there; there is no CPU path)")
+        V, T, cols = (int(n) for n in ddg.shape)
+        if V > 0 and T > 0 and (ddg.stride(2) != 1 or ddg.stride(1) < cols or ddg.stride(0) != T * ddg.stride(1)):
+            ddg = ddg.contiguous()
+        ld = int(ddg.stride(1)) if V > 0 and T > 0 else cols
+        depth, k = int(depth), int(k)
+        if not 1 <= depth <= _lib.BEAM_MAX_DEPTH:
+            raise TmpnnError(f"beam_step_each: depth={depth} outside [1, {_lib.BEAM_MAX_DEPTH}]")
+        if k < 1 or k * depth > _lib.BEAM_MAX_KD:
+            raise TmpnnError(f"beam_step_each: k={k} at depth {depth}: k must be at least 1 and k * depth at most {_lib.BEAM_MAX_KD}")
+        cut = float("inf") if cutoff is None else float(cutoff)
+        if cut != cut:
+            raise TmpnnError("beam_step_each: the cutoff is NaN")
+        if V > _lib.BEAM_MAX_V:
+            raise TmpnnError(f"beam_step_each: V={V} members exceed {_lib.BEAM_MAX_V}, the key's 16 member bits")
+        if isinstance(offsets, torch.Tensor) and offsets.is_cuda:
+            if max_len is None:
+                raise TmpnnError("beam_step_each: offsets on the device need max_len (the device checks every protein against it)")
+            max_len = int(max_len)
+        else:                                                       # (host offsets may be wrong on purpose: the device refuses those proteins)
+            o = np.asarray(offsets).astype(np.int64).reshape(-1)
+            max_len = int(max_len) if max_len is not None else int(np.clip(o[1:] - o[:-1], 0, T).max()) if o.size > 1 else 0
+        if not 0 <= max_len <= _lib.BEAM_MAX_LEN:
+            raise TmpnnError(f"beam_step_each: max_len={max_len} residues outside [0, {_lib.BEAM_MAX_LEN}], the key's 11 position bits")
+        dev = self.device
+        S_var, score, offsets = self._i32(S_var), self._f32(score), self._i32(offsets).reshape(-1)
+        P = offsets.numel() - 1
+        if P < 0:
+            raise TmpnnError("beam_step_each: offsets must hold P + 1 entries")
+        if muts is None:
+            if depth > 1:
+                raise TmpnnError(f"beam_step_each: depth {depth} needs muts [P, V, {depth - 1}]")
+        else:
+            muts = self._i32(muts)
+            if tuple(muts.shape) != (P, V, depth - 1):
+                raise TmpnnError(f"beam_step_each: muts must be [{P}, {V}, {depth - 1}] at depth {depth}, got {tuple(muts.shape)}")
+            if depth == 1:
+                muts = None
+        if allowed is not None:
+            allowed = self._i32(allowed)
+            if allowed.numel() != T:
+                raise TmpnnError(f"beam_step_each: allowed has {allowed.numel()} entries for {T} rows")
+        if tuple(S_var.shape) != (V, T) or tuple(score.shape) != (P, V):
+            raise TmpnnError(f"beam_step_each: tables {(V, T, cols)} and {P} proteins need S_var [V, T] and score [P, V]; got "
+                             f"{tuple(S_var.shape)}, {tuple(score.shape)}")
+        res = dict(out_muts=torch.empty((P, k, depth), dtype=torch.int32, device=dev), out_score=torch.empty((P, k), dtype=torch.float32, device=dev),
+                   out_parent=torch.empty((P, k), dtype=torch.int32, device=dev), out_S=torch.full((k, T), 20, dtype=torch.int32, device=dev),
+                   out_count=torch.empty(P, dtype=torch.int32, device=dev))
+        if P == 0:
+            return res
+        need = self.lib.tmpnn_beam_step_each_workspace_bytes(P, V, max_len, k, depth)
+        if need == 0 or V * T > 0x7fffffff:
+            raise TmpnnError(f"beam_step_each: sizes not served (P={P}, V={V}, T={T}, max_len={max_len}, k={k}, depth={depth})")
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        flags = _lib.BEAM_INCLUDE_CYS if include_cys else 0
+        with torch.cuda.device(dev):
+            check(self.lib.tmpnn_beam_step_each(_ptr(ddg), ld, _ptr(S_var), _ptr(score), _ptr(muts), depth, _ptr(allowed), _ptr(offsets), P, T,
+                                                V, max_len, k, cut, flags, _ptr(res["out_muts"]), _ptr(res["out_score"]),
+                                                _ptr(res["out_parent"]), _ptr(res["out_S"]) if T > 0 else None, _ptr(res["out_count"]),
+                                                _ptr(ws), ws.numel(), _stream()), "tmpnn_beam_step_each")
+        return res
+
     def pair_map(self, ddg, S_var, base, row, letter, wt, R: int, skip=None, include_cys: bool = False, upper: bool = False,
                  state: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """One chunk of variant tables that is already on the device reduced into a per-(row, position) state (tmpnn_pair_map: two

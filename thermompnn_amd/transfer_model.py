@@ -167,6 +167,13 @@ class TransferModel(_EngineOwner):
         from .variant_scan import multi_mutant_search
         return multi_mutant_search(self, pdb, order, beam, **kw)
 
+    def multi_mutant_search_each(self, pdbs, order: int, beam: int, **kw):
+        """``multi_mutant_search`` for many parsed structures at once, one list of levels per structure with the same hits, bit for
+        bit: the structures are packed, every pack is encoded once, and every round is ONE decode of the pack's beams and ONE step
+        on the device for all of its proteins (``variant_scan.multi_mutant_search_each``)."""
+        from .variant_scan import multi_mutant_search_each
+        return multi_mutant_search_each(self, pdbs, order, beam, **kw)
+
     def ensemble_table(self, members, cutoff=None, align: bool = False, reference=None, min_identity: float = 0.9):
         """Per-mutation statistics across the parsed members of ONE conformer ensemble (``pdb_io.parse_pdb_models`` of a multi-MODEL
         file, or one ``alt_parse_PDB`` entry per file), as ``ensemble.EnsembleTable``: mean, spread, lo, hi, lo_member, hi_member,
@@ -199,6 +206,22 @@ class TransferModel(_EngineOwner):
         L = X.shape[1]
         with torch.cuda.device(eng.device):
             return eng.encode(X[0], mask[0], residue_idx[0], chain_enc[0], torch.tensor([0, L], dtype=torch.int32), max_len=L)
+
+    def _encode_structures(self, entries):
+        """The packed sibling of ``_encode_structure``: several parsed structures -> ONE EncodedBackbone over their rows laid end to
+        end (one Engine.encode; ``enc.offsets`` [P + 1] on the device). Every structure is featurized as ``_encode_structure``
+        featurizes it alone, so the forward's batch independence makes its rows those of its own encoding."""
+        device = next(self.parameters()).device
+        parts = []
+        for entry in entries:
+            feats = tied_featurize([entry], device, None, None, None, None, None, None, ca_only=False)
+            parts.append((feats[0][0], feats[2][0], feats[12][0], feats[5][0]))
+        lens = [int(p[0].shape[0]) for p in parts]
+        X, mask, residue_idx, chain_enc = (torch.cat([p[i] for p in parts]) for i in range(4))
+        offsets = torch.tensor(np.concatenate([[0], np.cumsum(lens)]), dtype=torch.int32)
+        eng = self.engine()
+        with torch.cuda.device(eng.device):
+            return eng.encode(X, mask, residue_idx, chain_enc, offsets, max_len=max(lens))
 
     def _tables_over(self, enc, Sv) -> torch.Tensor:
         """The body of ``variant_tables`` behind the encoder: ``Sv`` [V, L] index matrix -> [V, L, 21] over an EncodedBackbone, which

@@ -22,7 +22,9 @@ Limits of the pair map: L <= 2048, one protein, one rank; the state is five [L, 
 per mutant, levels ascending (``multi_mutant_search`` / ``MultiHit``): every round decodes the beam's sequences in their own
 backgrounds and one step on the device keeps the K best distinct children with their sequence rows (Engine.beam_step,
 csrc/tmpnn_beam.hip); no table goes to the host and no sequence comes back.
-Limits of the beam search: L <= 2048, N <= 8, K * N <= 256, one protein, one rank.
+Limits of the beam search: L <= 2048, N <= 8, K * N <= 256, one protein, one rank. Many structures in one search:
+``multi_mutant_search_each`` (one encode per pack, one decode and one Engine.beam_step_each per round for all of its proteins), with
+its own command line, ``python -m thermompnn_amd.combine_scan``.
 Not here: the native writer, multi-GPU sharding of the variants, hipGraph capture, the training paths, ProteinMPNN.forward and
 examples/."""
 from __future__ import annotations
@@ -401,17 +403,97 @@ def multi_mutant_search(model, pdb, order: int, beam: int, positions: Optional[S
         rounds.append((res["out_muts"][:n], res["out_score"][:n], res["out_parent"][:n]))
     table = np.asarray(wt.cpu(), dtype=np.float32)
     name = entry.get("name", "")
-    levels = []
-    for m_d, s_d, p_d in rounds:
-        m_h, s_h, p_h = (np.asarray(x.cpu()) for x in (m_d, s_d, p_d))
-        hits = []
-        for row, val, par in zip(m_h, s_h, p_h):
-            subs = [(int(e) >> 5, int(e) & 31) for e in row]
-            add = sum(float(table[q, b]) for q, b in subs)
-            hits.append(MultiHit(tuple(Mutation(q, seq[q], ALPHABET[b], float(table[q, b]), name) for q, b in subs), float(val), add,
-                                 float(val) - add, int(par)))
-        levels.append(hits)
+    levels = [_multi_hits(table, seq, name, *(np.asarray(x.cpu()) for x in rnd)) for rnd in rounds]
     return levels + [[] for _ in range(order - len(levels))]
+
+
+def _multi_hits(table: np.ndarray, seq: str, name: str, m_h, s_h, p_h) -> List[MultiHit]:
+    """One level's rows on the host (substitution words [n, d], fp32 sums [n], parents [n]) -> its ``MultiHit``s; ``table`` is the
+    wild type's [L, 21]."""
+    hits = []
+    for row, val, par in zip(m_h, s_h, p_h):
+        subs = [(int(e) >> 5, int(e) & 31) for e in row]
+        add = sum(float(table[q, b]) for q, b in subs)
+        hits.append(MultiHit(tuple(Mutation(q, seq[q], ALPHABET[b], float(table[q, b]), name) for q, b in subs), float(val), add,
+                             float(val) - add, int(par)))
+    return hits
+
+
+def multi_mutant_search_each(model, pdbs, order: int, beam: int, positions: Optional[Sequence[Optional[Sequence[int]]]] = None,
+                             cutoff: Optional[float] = None, include_cys: bool = False, pack_residues: int = 16384,
+                             _tables: Optional[Callable] = None, _step: Optional[Callable] = None) -> List[List[List[MultiHit]]]:
+    """``multi_mutant_search`` for many parsed structures in one call -> one list of levels per structure, each equal to what
+    ``multi_mutant_search`` returns for that structure alone: the same sets, parents and score bits (the step's contract is per
+    protein and the forward's tables do not depend on the batch).
+    ``pdbs``: parsed structures (an entry, or ``alt_parse_PDB``'s one-entry list, each). ``positions``: None, or one list (or None)
+    per structure, local positions. The structures are grouped in argument order into packs of at most ``pack_residues`` residues
+    (``design_scan.pack_batches``; a longer structure gets a pack of its own). Per pack the backbones are encoded ONCE, together;
+    round d is ONE decode of the ``beam`` rows (round 1: one row, the wild types) — row v holds beam slot v of every protein — and ONE
+    ``Engine.beam_step_each``, whose outputs are the next round's rows, scores and substitutions as they stand. The host reads the
+    pack's counts once per round, stops when no protein has a child left, and builds the lists at the end as
+    ``multi_mutant_search`` does. A protein whose beam dies keeps empty levels while the others go on.
+    ValueError, naming the structure: as ``multi_mutant_search``; and a ``positions`` list of another length than ``pdbs``.
+    (``_tables(S [V, T], offsets [P + 1]) -> [V, T, 21]`` over a pack and ``_step(ddg, S_var, score, muts, offsets, depth, k,
+    allowed=, cutoff=, include_cys=, max_len=)``: the table function and the step, defaults the model's and its engine's.)"""
+    from .design_scan import pack_batches
+    entries = [p[0] if isinstance(p, (list, tuple)) else p for p in pdbs]
+    order, beam = int(order), int(beam)
+    if not 1 <= order <= BEAM_MAX_ORDER:
+        raise ValueError(f"multi_mutant_search_each: order={order} outside [1, {BEAM_MAX_ORDER}]")
+    if beam < 1 or beam * order > BEAM_MAX_KD:
+        raise ValueError(f"multi_mutant_search_each: beam={beam} at order {order}: beam must be at least 1 and beam * order at most "
+                         f"{BEAM_MAX_KD}")
+    if positions is not None and len(positions) != len(entries):
+        raise ValueError(f"multi_mutant_search_each: positions has {len(positions)} lists for {len(entries)} structures")
+    if int(pack_residues) < 1:
+        raise ValueError(f"multi_mutant_search_each: pack_residues={pack_residues}")
+    label = lambda i: f"structure {i} ({entries[i].get('name', '')})"
+    wt_idx = [sequence_indices(e["seq"]) for e in entries]
+    allowed = [None] * len(entries)
+    for i, e in enumerate(entries):
+        L = len(e["seq"])
+        if L > PAIR_MAX_LEN:
+            raise ValueError(f"multi_mutant_search_each: {label(i)}: {L} residues exceed {PAIR_MAX_LEN} (the step's key holds 11 position bits)")
+        if positions is not None and positions[i] is not None:
+            allowed[i] = np.zeros(L, dtype=np.int32)
+            for p in positions[i]:
+                if not 0 <= int(p) < L or wt_idx[i][int(p)] >= 20:
+                    raise ValueError(f"{label(i)}: position {p}: outside the sequence or a residue without one of the 20 letters")
+                allowed[i][int(p)] = 1
+    results: List[Optional[List[List[MultiHit]]]] = [None] * len(entries)
+    for pack in pack_batches([len(e["seq"]) for e in entries], int(pack_residues)):
+        lens = [len(entries[i]["seq"]) for i in pack]
+        offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+        P, T = len(pack), int(offsets[-1])
+        al = None
+        if any(allowed[i] is not None for i in pack):
+            al = np.concatenate([np.ones(n, np.int32) if allowed[i] is None else allowed[i] for i, n in zip(pack, lens)])
+        if _tables is None:
+            enc = model._encode_structures([entries[i] for i in pack])     # the pack's only encoder run
+            tables = lambda s, _o, enc=enc: model._tables_over(enc, s)
+        else:
+            tables = _tables
+        step = model.engine().beam_step_each if _step is None else _step
+        S = np.concatenate([wt_idx[i] for i in pack])[None] if pack else np.zeros((1, 0), np.int64)
+        score, muts, wt, rounds = np.zeros((P, 1), dtype=np.float32), None, None, []
+        for d in range(1, order + 1):
+            t = tables(S, offsets)                                         # [V, T, 21]: the previous round's tables are free by now
+            if d == 1:
+                wt = t[0]
+            res = step(t, S, score, muts, offsets, d, beam, allowed=al, cutoff=cutoff, include_cys=include_cys, max_len=max(lens))
+            del t
+            counts = np.asarray(res["out_count"].cpu()).reshape(P)         # the round's one read on the host
+            if (counts <= 0).all():
+                break
+            S, score, muts = res["out_S"], res["out_score"], res["out_muts"]
+            rounds.append((counts, res["out_muts"], res["out_score"], res["out_parent"]))
+        table = np.asarray(wt.cpu(), dtype=np.float32)
+        host = [(c, *(np.asarray(x.cpu()) for x in rest)) for c, *rest in rounds]
+        for j, i in enumerate(pack):
+            own, seq, name = table[offsets[j]:offsets[j + 1]], entries[i]["seq"], entries[i].get("name", "")
+            levels = [_multi_hits(own, seq, name, m[j, :c[j]], s[j, :c[j]], p[j, :c[j]]) if c[j] > 0 else [] for c, m, s, p in host]
+            results[i] = levels + [[] for _ in range(order - len(levels))]
+    return results
 
 
 MULTI_CSV_HEADER = ["order", "rank", "mutations", "ddG", "ddG_additive", "epistasis"]
