@@ -827,6 +827,59 @@ int tmpnn_align_global(const int32_t *A, int64_t NA, const int32_t *B, int64_t N
                        int32_t *out, int64_t NO, int32_t *aligned, int32_t *status, void *workspace, size_t workspace_bytes,
                        tmpnn_stream_t stream);
 
+/* ---- rigid-body superposition of ensemble members: RMSD, per-column deviation, RMSF ----------------------------------------------
+ * Why a ddG spread is large at a position: the backbone moves there, or it does not and the model is sensitive. And whether a member
+ * is the same conformation at all. One optimal rigid-body fit of every member onto the ensemble's member fit_to, then reductions per
+ * member and per axis column, from what a scan holds on the device before its forward. All pointers are device pointers.
+ * Inputs: X [T, 4, 3] fp32 (only atom slot 1, C-alpha, is read), mask [T] fp32, rows [R] int32 or NULL (the identity map; R is then
+ *   still the size of dev), desc [E, 6] int32 = (map0, M, L, out_row0, mem0, fit_to): M members of L axis columns each; max_len >= L.
+ * Outputs: n_fit [NM] int32, rmsd [NM] fp32, xform [NM, 12] float64 (R row-major, then t: x' = R x + t takes the member into the
+ *   frame of member fit_to), all three at member slot mem0 + m; dev [R] fp32 at map0 + m L + q, indexed like the map; rmsf [T_out]
+ *   fp32 and col_count [T_out] int32 at out_row0 + q; status [E] int32.
+ * Row r of (m, q) is rows[map0 + m L + q], or map0 + m L + q when rows is NULL. (m, q) is VALID when (uint32)r < T, mask[r] > 0 and
+ *   the three C-alpha floats are finite (tested on the exponent bits). Two members may name the same rows.
+ * The fit set of member m: F = {q : (m, q) and (fit_to, q) are both valid}; n_fit = |F|.
+ * (R, t): the PROPER rotation (det = +1, never a reflection) and the translation that minimise sum_F |R p_m + t - p_f|^2, in float64:
+ *   the centroids c_m, c_f over F; S[a][b] = sum_F (p_m - c_m)_a (p_f - c_f)_b; Horn's symmetric 4 x 4 matrix
+ *     [Sxx+Syy+Szz  Syz-Szy       Szx-Sxz       Sxy-Syx     ]
+ *     [             Sxx-Syy-Szz   Sxy+Syx       Szx+Sxz     ]
+ *     [                           -Sxx+Syy-Szz  Syz+Szy     ]
+ *     [                                         -Sxx-Syy+Szz]
+ *   solved by cyclic Jacobi (rotations (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) per sweep, until the off-diagonal squares sum to at most
+ *   1e-40 of the diagonal squares, 32 sweeps at most); the eigenvector of the largest eigenvalue (ties: the first column), normalised,
+ *   is the unit quaternion (w, x, y, z) of R; t = c_f - R c_m. A unit quaternion always gives a proper rotation, so a mirrored member,
+ *   collinear points, two points or one need no special case: where the largest eigenvalue is not simple (such point sets; a vanishing
+ *   gap to the second eigenvalue) the rotation is one of the minimisers, not a unique one. That is documented, not an error.
+ *   rmsd = sqrt(sum_F |R p_m + t - p_f|^2 / n_fit), from the residuals and not from the eigenvalue (which loses everything to
+ *   cancellation for near-identical members), in float64, rounded to fp32 once. Unique whenever n_fit >= 1.
+ *   dev[map0 + m L + q] = |R p_m(q) + t - p_f(q)| (float64, rounded to fp32 once) for q in F when n_fit >= 3; 0x7fc00000 everywhere
+ *   else in the member's L entries.
+ *   m == fit_to: R = I and t = 0 exactly, rmsd = +0.0, dev = +0.0 on its valid columns whatever its n_fit (0x7fc00000 on the others).
+ *   n_fit == 0 (the fit target with no valid column included): R = I, t = 0, rmsd = 0x7fc00000, dev all 0x7fc00000.
+ *   n_fit 1 or 2: rmsd and xform as defined above; the member takes no part in dev or rmsf.
+ * Column q: the PARTICIPANTS are the members valid at q that have n_fit >= 3 or are member fit_to. col_count = their number n;
+ *   mu = sum x' / n with x' = R p + t, the sum taken in ascending m, in float64; rmsf = sqrt(sum |x' - mu|^2 / n), again in ascending
+ *   m, rounded to fp32 once; n == 0 (M == 0 included): 0x7fc00000.
+ * The DEVICE checks every descriptor in 64-bit arithmetic before any other access: map0, M, L, out_row0, mem0 >= 0, L <= max_len,
+ *   map0 + M L <= R (and <= T when rows is NULL), out_row0 + L <= T_out, mem0 + M <= NM, 0 <= fit_to < M unless M == 0. An ensemble
+ *   that fails gets status[e] = -1 and none of its outputs is written; a good one gets 0 and is served whatever its neighbours are.
+ *   No access leaves the buffers. Output ranges or member slots that two good ensembles share are the caller's error.
+ * Two launches on `stream`, no workspace, no atomics. Launch 1: one workgroup of 256 threads per member slot g < NM; it finds the
+ *   smallest good ensemble e with mem0 <= g < mem0 + M (the host does not know M) and makes three sweeps over the member's columns
+ *   (centroids; covariance; residuals), one thread solving the 4 x 4 between the second and the third. ORDER of every float64 sum:
+ *   thread t of 256 takes the columns t, t + 256, ... in ascending order; a wavefront folds its 64 threads at distances 32, 16, .. 1
+ *   (lane l takes lane l + distance); the four wavefront sums are added in ascending order. No contraction. Launch 2: one thread per
+ *   (ensemble, column) on a grid of (ceil(max_len / 256), E); it loops over the members in ascending order and writes status. The
+ *   order of every sum depends on (M, L, the data) only: every output bit, the float64 ones included, is reproducible on a rerun and
+ *   independent of E, NM and the ensemble's place in the call.
+ * E == 0 is a no-op. Errors before any launch: negative sizes, null pointer (X and mask may be NULL when T == 0, dev when R == 0, n_fit,
+ *   rmsd, xform when NM == 0, rmsf and col_count when T_out == 0; rows may always be NULL) -> TMPNN_E_INVALID; T, T_out, R or NM >
+ *   2^31 - 1, max_len > 8192 or E > 65535 -> TMPNN_E_UNSUPPORTED.
+ * Limits: C-alpha only, one fit target per ensemble, no iteration to the mean structure, unweighted. */
+int tmpnn_superpose(const float *X, const float *mask, const int32_t *rows, int64_t R, const int32_t *desc, int E, int64_t T, int64_t NM,
+                    int64_t T_out, int max_len, int32_t *n_fit, float *rmsd, double *xform, float *dev, float *rmsf, int32_t *col_count,
+                    int32_t *status, tmpnn_stream_t stream);
+
 /* ---- bootstrap confidence intervals of the benchmark metrics (the reference's analysis/bootstrap.py) ------------------------------
  * B resamples with replacement of a table of N rows, and per resample and prediction column the five metrics of the benchmarking
  * script. No resample is sorted: the ranks inside a resample follow from one histogram over the tie groups of the original column and

@@ -111,6 +111,7 @@ SIGNATURES = {
     "tmpnn_ensemble_stats_rows": (_i, [_p, _i, _p, _p, _i64, _p, _i, _i64, _i64, _i, C.c_float, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "tmpnn_align_workspace_bytes": (_sz, [_i, _i, _i64]),
     "tmpnn_align_global": (_i, [_p, _i64, _p, _i64, _p, _i, _i, _i, _p, _i64, _p, _p, _p, _sz, _p]),
+    "tmpnn_superpose": (_i, [_p, _p, _p, _i64, _p, _i, _i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "tmpnn_bootstrap_workspace_bytes": (_sz, [_i, _i64, _i64, _i]),
     "tmpnn_bootstrap_metrics": (_i, [_p, _p, _i, _i64, _p, _i64, _p, _p, _p, _p, _sz, _i, _p]),
     "tmpnn_pdb_parse": (_i, [C.c_char_p, C.c_char_p, C.POINTER(_p)]),
@@ -175,7 +176,9 @@ BEAM_MAX_LEN, BEAM_MAX_V, BEAM_MAX_DEPTH, BEAM_MAX_KD = 2048, 65536, 8, 256   # 
 ENS_MAX_LEN, ENS_MAX_E = 8192, 65535                       # tmpnn_ensemble_stats: the forward's own length bound, grid.y
 ENS_ARRAYS = (("mean", "float32"), ("spread", "float32"), ("lo", "float32"), ("hi", "float32"), ("lo_member", "int32"),
               ("hi_member", "int32"), ("count", "int32"), ("below", "int32"))
-ALIGN_MAX_LEN = 8192                                       # tmpnn_align_global: 16-bit scores and both strings in LDS
+SUP_ARRAYS = (("n_fit", "int32"), ("rmsd", "float32"), ("xform", "float64"), ("dev", "float32"), ("rmsf", "float32"),
+              ("col_count", "int32"))                      # tmpnn_superpose's outputs in argument order (status last); its bounds are ENS_*
+ALIGN_MAX_LEN = 8192                                    # tmpnn_align_global: 16-bit scores and both strings in LDS
 BOOT_LDS_N, BOOT_MAX_N, BOOT_MAX_B, BOOT_MAX_M = 16384, 1 << 20, 1 << 20, 8   # tmpnn_bootstrap_metrics: the LDS form's N, 4 N^3 < 2^63
 BOOT_FORCE_WORKSPACE = 1                                   # the flag of tmpnn_bootstrap_metrics
 BOOT_METRICS = ("r2", "mse", "rmse", "spearman", "pearson")

@@ -17,7 +17,7 @@ DEBUG_LIB = os.path.join(HERE, "libtmpnn_debug.so")
 SOURCES = ["tmpnn_api.hip", "tmpnn_graph.hip", "tmpnn_graph_ca.hip", "tmpnn_layers.hip", "tmpnn_head.hip", "tmpnn_split.hip", "tmpnn_edge.hip", "tmpnn_msg.hip",
            "tmpnn_edge_msg.hip", "tmpnn_node.hip", "tmpnn_variants.hip", "tmpnn_sample.hip", "tmpnn_train.hip", "tmpnn_finetune.hip", "tmpnn_seqbatch.hip",
            "tmpnn_coordgrad.hip", "tmpnn_hits.hip", "tmpnn_variant_hits.hip", "tmpnn_pair_map.hip", "tmpnn_beam.hip",
-           "tmpnn_ensemble.hip", "tmpnn_align.hip", "tmpnn_bootstrap.hip", "tmpnn_pdb.cpp", "tmpnn_csv.cpp"]
+           "tmpnn_ensemble.hip", "tmpnn_align.hip", "tmpnn_bootstrap.hip", "tmpnn_superpose.hip", "tmpnn_pdb.cpp", "tmpnn_csv.cpp"]
 HEADERS = ["tmpnn_common.h", "tmpnn_split.h", "tmpnn_internal.h", "tmpnn_head_body.h", "tmpnn_ft.h", "tmpnn_hits.h", os.path.join("..", "..", "include", "tmpnn.h"),
            os.path.join("..", "..", "include", "tmpnn_debug.h"), "tmpnn_host_guard.hpp"]
 # -mcode-object-version=5: tm_nblk() / tm_bdim() (tmpnn_common.h) read gridDim / blockDim at fixed offsets of the v5
@@ -45,6 +45,8 @@ FILE_FLAGS["tmpnn_beam.hip"] = []
 FILE_FLAGS["tmpnn_ensemble.hip"] = []
 # ... and the bootstrap of the benchmark metrics: its float64 sums, divides and roots are plain IEEE, and a NaN is a result to write
 FILE_FLAGS["tmpnn_bootstrap.hip"] = []
+# ... and the superposition of ensemble members: mask > 0 must be false for a NaN mask, its float64 work is plain IEEE, NaN is a result
+FILE_FLAGS["tmpnn_superpose.hip"] = []
 
 
 def _hipcc() -> str:

@@ -747,6 +747,67 @@ class Engine:
                                                 _ptr(res["status"]), _stream()), "tmpnn_ensemble_stats")
         return res
 
+    def superpose(self, X, mask, members: Sequence[int], lengths: Sequence[int], rows=None, fit_to=0) -> Dict[str, torch.Tensor]:
+        """Rigid-body superposition of the members of conformer ensembles on the C-alpha atoms (tmpnn_superpose: two launches, no
+        workspace), from the packed backbone that is already on the device: ``X`` [T, 4, 3] float32 (only atom slot 1 is read),
+        ``mask`` [T], and per ensemble, on the host, ``members`` (M) and ``lengths`` (L) as ``ensemble_stats`` takes them; ``rows``:
+        an int32 [sum(M L)] row map, ``align_global``'s ``out`` as it is (None: the identity map, and sum(M L) == T). ``fit_to``: the
+        member every other member of its ensemble is laid on, one number for all ensembles or one per ensemble.
+        -> dict(n_fit [NM] int32: the columns valid in the member and in the fit target; rmsd [NM] float32; xform [NM, 12] float64:
+        R row-major, then t, x' = R x + t; dev [sum(M L)] float32, indexed like the map: the distance to the fit target's atom after
+        the fit, NaN outside the fit set and for members with n_fit < 3; rmsf [sum(L)] float32 and col_count [sum(L)] int32 per axis
+        column over the superposed members; offsets [E + 1] of the ensembles' columns; status [E]) on the device, NM = sum(M), the
+        members in order. include/tmpnn.h has the contract to the operation and the order of every sum. L <= 8192."""
+        if not isinstance(X, torch.Tensor) or not X.is_cuda or X.dtype != torch.float32 or X.dim() != 3 or tuple(X.shape[1:]) != (4, 3):
+            raise TmpnnError("superpose: X must be a float32 [T, 4, 3] tensor on the device (the backbone stays there; there is no CPU path)")
+        X = X.contiguous()
+        T = int(X.shape[0])
+        M, L = np.asarray(members, dtype=np.int64).reshape(-1), np.asarray(lengths, dtype=np.int64).reshape(-1)
+        E = int(M.size)
+        if L.size != E or (M < 0).any() or (L < 0).any():
+            raise TmpnnError(f"superpose: members and lengths must be {E} non-negative numbers each, one per ensemble")
+        if E > _lib.ENS_MAX_E:
+            raise TmpnnError(f"superpose: {E} ensembles exceed {_lib.ENS_MAX_E} per call")
+        max_len = int(L.max()) if E else 0
+        if max_len > _lib.ENS_MAX_LEN:
+            raise TmpnnError(f"superpose: an ensemble of {max_len} residues exceeds {_lib.ENS_MAX_LEN}, the forward's own bound")
+        fit = np.asarray(fit_to, dtype=np.int64).reshape(-1)
+        if np.ndim(fit_to) == 0:
+            fit = np.repeat(fit, E)
+        if fit.size != E or ((M > 0) & ((fit < 0) | (fit >= M))).any():
+            raise TmpnnError(f"superpose: fit_to must name a member of every ensemble (0 <= fit_to < M), one number or {E}")
+        fit = np.where(M > 0, fit, 0)
+        R = int((M * L).sum())
+        if T > 0x7fffffff or R > 0x7fffffff:
+            raise TmpnnError(f"superpose: {T} backbone rows or {R} map entries exceed 2^31 - 1")
+        if rows is not None:
+            rows = self._i32(rows).reshape(-1)
+            if R != rows.numel():
+                raise TmpnnError(f"superpose: the ensembles describe {R} map entries, rows has {rows.numel()}")
+        elif R != T:
+            raise TmpnnError(f"superpose: the ensembles describe {R} rows, the backbone has {T}")
+        mask = self._f32(mask).reshape(-1)
+        if mask.numel() != T:
+            raise TmpnnError(f"superpose: mask has {mask.numel()} entries for a backbone of {T} rows")
+        out_off = np.concatenate([[0], np.cumsum(L)])
+        T_out, NM = int(out_off[-1]), int(M.sum())
+        map0 = np.concatenate([[0], np.cumsum(M * L)])[:-1]
+        mem0 = np.concatenate([[0], np.cumsum(M)])[:-1]
+        dev = self.device
+        desc = torch.from_numpy(np.stack([map0, M, L, out_off[:-1], mem0, fit], axis=1).astype(np.int32).reshape(E, 6)).to(dev)
+        shape = dict(n_fit=(NM,), rmsd=(NM,), xform=(NM, 12), dev=(R,), rmsf=(T_out,), col_count=(T_out,))
+        res = {name: torch.empty(shape[name], dtype=getattr(torch, dt), device=dev) for name, dt in _lib.SUP_ARRAYS}
+        res["offsets"] = torch.from_numpy(out_off.astype(np.int32)).to(dev)
+        res["status"] = torch.zeros(E, dtype=torch.int32, device=dev)
+        if E == 0:
+            return res
+        with torch.cuda.device(dev):
+            check(self.lib.tmpnn_superpose(_ptr(X) if T > 0 else None, _ptr(mask) if T > 0 else None,
+                                           _ptr(rows) if rows is not None and R > 0 else None, R, _ptr(desc), E, T, NM, T_out, max_len,
+                                           *[_ptr(res[name]) if res[name].numel() > 0 else None for name, _ in _lib.SUP_ARRAYS],
+                                           _ptr(res["status"]), _stream()), "tmpnn_superpose")
+        return res
+
     # -- global alignment of letter-code sequences ----------------------------------------------------
     def align_global(self, A, B, desc, max_n: Optional[int] = None, max_m: Optional[int] = None, out: Optional[torch.Tensor] = None,
                      slots: Optional[int] = None) -> Dict[str, torch.Tensor]:

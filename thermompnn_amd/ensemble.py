@@ -18,8 +18,16 @@ through (``Engine.ensemble_stats(rows=)``). Only matching letters align, so a su
 identity (aligned columns / its residues that carry one of the 20 letters) is below ``min_identity`` is refused.
 A member's own '-', 'X' and rows with a missing backbone atom drop out of that position only. Limits: L <= 8192, 65 535
 ensembles per call, the released head configuration with ``subtract_mut``, one rank. Multi-MODEL files are read by the Python parser
-(``pdb_io.parse_pdb_models``) only. Out of scope: substitution matrices and gap penalties, multiple-sequence alignment, structural
-superposition."""
+(``pdb_io.parse_pdb_models``) only.
+
+``superpose=True`` says why a spread is large and refuses a member that is another conformation: ONE ``Engine.superpose`` per scan
+(csrc/tmpnn_superpose.hip, two small launches before the forward, after the alignment and through its row map as it is) lays every
+member on member ``fit_to`` of its ensemble by the optimal proper rotation of the C-alpha atoms both have, and gives per member the
+RMSD, the number of fitted columns and the transform, per (member, column) the deviation after the fit and per column the RMSF of the
+superposed members. A member whose RMSD exceeds ``max_rmsd`` is refused by name before any forward. The ddG statistics do not change.
+
+Out of scope: substitution matrices and gap penalties, multiple-sequence alignment; in the superposition, iterating to the mean
+structure, other atoms than C-alpha, weights."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -98,6 +106,11 @@ class EnsembleTable:
     names: List[str]
     aligned: Optional[torch.Tensor] = None      # align=True: [M, L] int32, the member's own residue index at every axis column, or -1
     identity: Optional[torch.Tensor] = None     # align=True: [M] float64, aligned columns / the member's residues with one of the 20 letters
+    rmsd: Optional[torch.Tensor] = None         # superpose=True: [M] float32, C-alpha RMSD to member fit_to after the optimal fit (NaN: n_fit 0)
+    n_fit: Optional[torch.Tensor] = None        # superpose=True: [M] int32, the columns valid in the member and in member fit_to
+    rmsf: Optional[torch.Tensor] = None         # superpose=True: [L] float32, per column over the superposed members (NaN: none there)
+    deviation: Optional[torch.Tensor] = None    # superpose=True: [M, L] float32, the distance to member fit_to's atom after the fit, or NaN
+    xform: Optional[torch.Tensor] = None        # superpose=True: [M, 12] float64, R row-major then t: x' = R x + t
 
 
 @dataclass
@@ -114,6 +127,7 @@ class EnsembleHit:
     below: int
     lo_member: int = -1
     hi_member: int = -1
+    rmsf: float = float("nan")      # superpose=True: the RMSF of the hit's position
 
 
 def _check_model(model) -> None:
@@ -145,7 +159,8 @@ def _letter_codes(seq: str) -> np.ndarray:
 
 
 def scan_ensembles(model, ensembles: Sequence[Sequence[dict]], cutoff: Optional[float] = None, chunk_residues: int = 1 << 18,
-                   align: bool = False, reference: Optional[str] = None, min_identity: float = 0.9) -> dict:
+                   align: bool = False, reference: Optional[str] = None, min_identity: float = 0.9, superpose: bool = False,
+                   fit_to: int = 0, max_rmsd: Optional[float] = None) -> dict:
     """Ensembles (each a list of parsed members) -> dict(stats: what ``Engine.ensemble_stats`` returns over ALL ensembles, rows
     ``offsets[e] .. offsets[e + 1]`` being ensemble e; seqs; names: per ensemble its members' names; members: M per ensemble).
     One ``tied_featurize`` per ensemble, ONE forward per chunk of whole members of at most ``chunk_residues`` residues (a chunk may
@@ -155,10 +170,19 @@ def scan_ensembles(model, ensembles: Sequence[Sequence[dict]], cutoff: Optional[
     ``Engine.align_global`` whose output is the row map of the statistics; ``seqs`` are the axes, and the dict gains ``aligned``
     (per ensemble an int32 [M, L] device tensor: the member's own residue index at every axis column, or -1) and ``identity`` (per
     ensemble a float64 [M] array: aligned columns / the member's residues that carry one of the 20 letters). ValueError, naming the
-    member and the value, for a member below ``min_identity`` (0 disables it). Only ``aligned`` counts and ``status`` come back."""
+    member and the value, for a member below ``min_identity`` (0 disables it). Only ``aligned`` counts and ``status`` come back.
+    ``superpose=True``: the packed X and mask of all members go through ONE ``Engine.superpose`` before the forward (after the
+    alignment, through its row map as it is): every member is laid on member ``fit_to`` of its ensemble, and the dict gains
+    ``superposed``: what ``Engine.superpose`` returns over all ensembles (n_fit, rmsd, xform per member, the members in order; dev
+    per map entry; rmsf, col_count per column). ValueError, naming the member and the value, for a member whose RMSD exceeds
+    ``max_rmsd`` or that shares no column with member ``fit_to`` (None: no member is refused); only ``rmsd`` comes back for it."""
     _check_model(model)
     if not align and reference is not None:
         raise ValueError("reference= belongs to align=True")
+    if not superpose and (fit_to != 0 or max_rmsd is not None):
+        raise ValueError("fit_to= and max_rmsd= belong to superpose=True")
+    if max_rmsd is not None and not max_rmsd >= 0:
+        raise ValueError(f"max_rmsd={max_rmsd}: a distance, >= 0")
     device = next(model.parameters()).device
     eng = model.engine()
     seqs, names, S_stat, pieces, M_of, L_of = [], [], [], [], [], []
@@ -167,6 +191,8 @@ def scan_ensembles(model, ensembles: Sequence[Sequence[dict]], cutoff: Optional[
     a0 = b0 = map0 = 0
     for entries in ensembles:
         entries = list(entries)
+        if superpose and not 0 <= fit_to < len(entries):
+            raise ValueError(f"fit_to={fit_to}: ensemble {len(seqs)} has {len(entries)} members")
         if align:
             if not entries:
                 raise ValueError("an ensemble needs at least one member")
@@ -221,6 +247,21 @@ def scan_ensembles(model, ensembles: Sequence[Sequence[dict]], cutoff: Optional[
                 aligned.append(torch.where(block >= 0, block - first[k:k + M, None], block))
                 identity.append(ident)
                 k, at = k + M, at + M * L
+        if superpose:                                                            # before the forward too: a refusal costs two small launches
+            X_all = torch.cat([p[0] for p in pieces]) if pieces else torch.zeros((0, 4, 3))
+            mask_all = torch.cat([p[2] for p in pieces]) if pieces else torch.zeros(0)
+            sup = eng.superpose(X_all.to(device=eng.device, dtype=torch.float32), mask_all, M_of, L_of, rows=rows_out if align else None,
+                                fit_to=fit_to)
+            if (sup["status"] != 0).any():
+                raise RuntimeError(f"superpose refused ensemble {int(torch.nonzero(sup['status'])[0])}")
+            if max_rmsd is not None:
+                rmsd, k = sup["rmsd"].cpu().numpy(), 0
+                for e, M in enumerate(M_of):
+                    for m in range(M):
+                        if not rmsd[k + m] <= max_rmsd:
+                            raise ValueError(f"ensemble member {m} ({names[e][m]}) lies {rmsd[k + m]:.3f} A (C-alpha RMSD) from member {fit_to} "
+                                             f"({names[e][fit_to]}) of ensemble {e}, above max_rmsd {max_rmsd}")
+                    k += M
         table = torch.empty((T, 21), dtype=torch.float32, device=eng.device)
         pos, k = 0, 0
         while k < len(pieces):
@@ -237,29 +278,35 @@ def scan_ensembles(model, ensembles: Sequence[Sequence[dict]], cutoff: Optional[
             eng.ssm_forward(X, S_fwd, mask, ridx, cenc, offsets, max_len=max(lens), out={"ddg": table[pos:pos + tot]})
             pos += tot
         S_all = np.concatenate(S_stat) if S_stat else np.zeros(0, np.int32)
+        extra = dict(superposed=sup) if superpose else {}
         if not align:
             stats = eng.ensemble_stats(table, S_all, M_of, L_of, cutoff=cutoff)
-            return dict(stats=stats, seqs=seqs, names=names, members=M_of)
+            return dict(stats=stats, seqs=seqs, names=names, members=M_of, **extra)
         stats = eng.ensemble_stats(table, S_all, M_of, L_of, cutoff=cutoff, rows=rows_out)
-    return dict(stats=stats, seqs=seqs, names=names, members=M_of, aligned=aligned, identity=identity)
+    return dict(stats=stats, seqs=seqs, names=names, members=M_of, aligned=aligned, identity=identity, **extra)
 
 
 def ensemble_table(model, members: Sequence[dict], cutoff: Optional[float] = None, align: bool = False, reference: Optional[str] = None,
-                   min_identity: float = 0.9) -> EnsembleTable:
-    """``TransferModel.ensemble_table``: one ensemble -> its ``EnsembleTable`` (``align``, ``reference``, ``min_identity``:
-    ``scan_ensembles``)."""
-    res = scan_ensembles(model, [members], cutoff=cutoff, align=align, reference=reference, min_identity=min_identity)
+                   min_identity: float = 0.9, superpose: bool = False, fit_to: int = 0, max_rmsd: Optional[float] = None) -> EnsembleTable:
+    """``TransferModel.ensemble_table``: one ensemble -> its ``EnsembleTable`` (``align``, ``reference``, ``min_identity``,
+    ``superpose``, ``fit_to``, ``max_rmsd``: ``scan_ensembles``)."""
+    res = scan_ensembles(model, [members], cutoff=cutoff, align=align, reference=reference, min_identity=min_identity, superpose=superpose,
+                         fit_to=fit_to, max_rmsd=max_rmsd)
     extra = dict(aligned=res["aligned"][0], identity=torch.from_numpy(res["identity"][0])) if align else {}
+    if superpose:
+        sup, M = res["superposed"], res["members"][0]
+        extra.update(rmsd=sup["rmsd"], n_fit=sup["n_fit"], rmsf=sup["rmsf"], deviation=sup["dev"].view(M, -1), xform=sup["xform"])
     return EnsembleTable(**{name: res["stats"][name] for name in STAT_NAMES}, seq=res["seqs"][0], names=res["names"][0], **extra)
 
 
 def select_ensemble_hits(engine, stats: Dict[str, torch.Tensor], seqs: Sequence[str], k: int, rank: str = "mean",
                          cutoff: Optional[float] = None, include_cys: bool = False, one_per_position: bool = False,
-                         min_members: Optional[int] = None) -> List[List[EnsembleHit]]:
+                         min_members: Optional[int] = None, rmsf: Optional[torch.Tensor] = None) -> List[List[EnsembleHit]]:
     """Ranked hit lists of every ensemble of a ``scan_ensembles`` result, best first: ONE ``Engine.select_hits`` on the [sum(L), 20]
     table that ``rank`` names ("mean"; "worst": the largest ddG over the members, so a hit is stabilising in every conformer;
     "best": the smallest), with ld = 20. ``min_members``: entries in which fewer members take part are set to NaN in the ranked copy
-    (one masked fill on the device), so they are no candidates. Only the hits and their statistics are copied back."""
+    (one masked fill on the device), so they are no candidates. ``rmsf``: the [sum(L)] RMSF of a superposed scan
+    (``res["superposed"]["rmsf"]``); every hit then carries its position's. Only the hits and their statistics are copied back."""
     if rank not in RANKS:
         raise ValueError(f"rank={rank!r}: one of {sorted(RANKS)}")
     ranked = stats[RANKS[rank]]
@@ -274,6 +321,7 @@ def select_ensemble_hits(engine, stats: Dict[str, torch.Tensor], seqs: Sequence[
         pos, aa = res["hit_pos"].clamp(min=0).long(), res["hit_aa"].clamp(min=0).long()
         rows = torch.as_tensor(offsets[:-1], device=engine.device).long()[:, None] + pos
         picked = {name: stats[name][rows[live], aa[live]].cpu().numpy() for name in STAT_NAMES}
+        at_hit = rmsf[rows[live]].cpu().numpy() if rmsf is not None else None
         val, pos, aa = res["hit_ddg"][live].cpu().numpy(), res["hit_pos"][live].cpu().numpy(), res["hit_aa"][live].cpu().numpy()
     out, at = [], 0
     for e, seq in enumerate(seqs):
@@ -282,7 +330,8 @@ def select_ensemble_hits(engine, stats: Dict[str, torch.Tensor], seqs: Sequence[
             p = int(pos[i])
             hits.append(EnsembleHit(p, seq[p], ALPHABET[int(aa[i])], float(val[i]), float(picked["mean"][i]), float(picked["spread"][i]),
                                     float(picked["lo"][i]), float(picked["hi"][i]), int(picked["count"][i]), int(picked["below"][i]),
-                                    int(picked["lo_member"][i]), int(picked["hi_member"][i])))
+                                    int(picked["lo_member"][i]), int(picked["hi_member"][i]),
+                                    **({} if at_hit is None else dict(rmsf=float(at_hit[i])))))
         at += int(counts[e])
         out.append(hits)
     return out
@@ -290,11 +339,14 @@ def select_ensemble_hits(engine, stats: Dict[str, torch.Tensor], seqs: Sequence[
 
 def ensemble_hits(model, members: Sequence[dict], k: int, rank: str = "mean", cutoff: Optional[float] = None, include_cys: bool = False,
                   one_per_position: bool = False, min_members: Optional[int] = None, align: bool = False, reference: Optional[str] = None,
-                  min_identity: float = 0.9) -> List[EnsembleHit]:
+                  min_identity: float = 0.9, superpose: bool = False, fit_to: int = 0, max_rmsd: Optional[float] = None) -> List[EnsembleHit]:
     """``TransferModel.ensemble_hits``: the ``k`` best substitutions of one ensemble by ``rank``. ``cutoff`` keeps hits whose ranked
     statistic is <= cutoff, and is the cutoff of ``below`` as well. ``align``, ``reference``, ``min_identity``: ``scan_ensembles``;
-    positions and wild-type letters are then the axis'."""
+    positions and wild-type letters are then the axis'. ``superpose``, ``fit_to``, ``max_rmsd``: ``scan_ensembles``; every hit then
+    carries the RMSF of its position."""
     if rank not in RANKS:
         raise ValueError(f"rank={rank!r}: one of {sorted(RANKS)}")
-    res = scan_ensembles(model, [members], cutoff=cutoff, align=align, reference=reference, min_identity=min_identity)
-    return select_ensemble_hits(model.engine(), res["stats"], res["seqs"], k, rank, cutoff, include_cys, one_per_position, min_members)[0]
+    res = scan_ensembles(model, [members], cutoff=cutoff, align=align, reference=reference, min_identity=min_identity, superpose=superpose,
+                         fit_to=fit_to, max_rmsd=max_rmsd)
+    return select_ensemble_hits(model.engine(), res["stats"], res["seqs"], k, rank, cutoff, include_cys, one_per_position, min_members,
+                                rmsf=res["superposed"]["rmsf"] if superpose else None)[0]

@@ -18,6 +18,11 @@ the device to ``--reference`` (a sequence or a one-record FASTA file; default: m
 ``datasets.global_alignment_map``; a member below ``--min_identity`` (default 0.9; 0 disables it) is refused. The ``.npz`` gains
 ``aligned`` (int32, flat: ensemble e's block of members[e] x L_e entries, member-local residue index or -1, the blocks in order) and
 ``identity`` (float64, one per member); the CSV layouts do not change.
+``--superpose``: before the forward every member is laid on member ``--fit_to`` (default 0) of its ensemble by the optimal proper
+rotation of the C-alpha atoms both have (``Engine.superpose``, csrc/tmpnn_superpose.hip); a member whose RMSD exceeds ``--max_rmsd``
+is refused by name before any forward. The ``.npz`` gains ``rmsd`` (float32) and ``n_fit`` (int32), one per member, ``xform``
+(float64 [members, 12]: R row-major, then t), ``deviation`` (float32, flat like ``aligned``) and ``rmsf`` (float32 [sum(L)], rows like
+the statistics); the ``--top`` CSV gains an ``rmsf`` column. Without the flag every layout is as it was.
 Limits: without --align members of equal length and sequence; L <= 8192, 65 535 ensembles, K <= 256, the released head, one rank, the
 Python parser."""
 from __future__ import annotations
@@ -34,6 +39,7 @@ from .datasets import ALPHABET
 from .ensemble import RANKS, STAT_NAMES, scan_ensembles, select_ensemble_hits
 from .ssm_scan import HIT_COLUMNS
 
+SUPERPOSE_ARRAYS = dict(rmsd="rmsd", n_fit="n_fit", xform="xform", deviation="dev", rmsf="rmsf")    # .npz name -> Engine.superpose's
 TABLE_COLUMNS = ["Model", "Dataset", "pdb", "position", "wildtype", "mutation"] + list(STAT_NAMES)
 
 
@@ -46,6 +52,8 @@ def write_ensemble_npz(path: str, res: dict) -> None:
     if "aligned" in res:
         arrays["aligned"] = np.concatenate([a.cpu().numpy().reshape(-1) for a in res["aligned"]] + [np.zeros(0, np.int32)]).astype(np.int32)
         arrays["identity"] = np.concatenate(list(res["identity"]) + [np.zeros(0, np.float64)])
+    if "superposed" in res:
+        arrays.update({name: res["superposed"][key].cpu().numpy() for name, key in SUPERPOSE_ARRAYS.items()})
     with open(path, "wb") as fh:
         np.savez(fh, **arrays, offsets=res["stats"]["offsets"].cpu().numpy(), seqs=np.array(res["seqs"]), names=np.array(res["ensemble_names"]),
                  members=np.array(res["members"], np.int32), member_names=np.array([n for group in res["names"] for n in group]))
@@ -73,15 +81,17 @@ def write_ensemble_csv(path: str, res: dict, model_name: str = "ThermoMPNN", dat
 
 
 def write_ensemble_hits_csv(path: str, hits: Sequence[Sequence], names: Sequence[str], model_name: str = "ThermoMPNN",
-                            dataset: str = "custom") -> int:
+                            dataset: str = "custom", rmsf: bool = False) -> int:
+    """``rmsf``: a last column with the RMSF of the hit's position (a superposed scan)."""
     n = 0
     with open(path, "w", newline="") as fh:
         w = csv.writer(fh, lineterminator="\n")
-        w.writerow([""] + HIT_COLUMNS + list(STAT_NAMES))
+        w.writerow([""] + HIT_COLUMNS + list(STAT_NAMES) + (["rmsf"] if rmsf else []))
         for name, group in zip(names, hits):
             for r, h in enumerate(group):
                 w.writerow([n, model_name, dataset, repr(h.ddG), h.position, h.wildtype, h.mutation, r, name] +
-                           [_num(getattr(h, s)) if s in ("lo_member", "hi_member", "count", "below") else repr(getattr(h, s)) for s in STAT_NAMES])
+                           [_num(getattr(h, s)) if s in ("lo_member", "hi_member", "count", "below") else repr(getattr(h, s)) for s in STAT_NAMES] +
+                           ([repr(h.rmsf)] if rmsf else []))
                 n += 1
     return n
 
@@ -119,7 +129,12 @@ def main(argv=None) -> int:
     ap.add_argument("--align", action="store_true", help="align members of unequal length to the axis on the device")
     ap.add_argument("--reference", default=None, metavar="SEQ|FASTA", help="--align: the axis, a sequence or a one-record FASTA file (default: member 0)")
     ap.add_argument("--min_identity", type=float, default=None, metavar="F", help="--align: refuse members below this identity (default 0.9; 0: none)")
+    ap.add_argument("--superpose", action="store_true", help="superpose the members on the device: RMSD, deviations and RMSF beside the statistics")
+    ap.add_argument("--fit_to", type=int, default=None, metavar="I", help="--superpose: the member every other one is laid on (default 0)")
+    ap.add_argument("--max_rmsd", type=float, default=None, metavar="X", help="--superpose: refuse members further than X A (C-alpha RMSD) from it")
     a = ap.parse_args(argv)
+    if not a.superpose and (a.fit_to is not None or a.max_rmsd is not None):
+        ap.error("--fit_to and --max_rmsd belong to --superpose")
     if not a.align and (a.reference is not None or a.min_identity is not None):
         ap.error("--reference and --min_identity belong to --align")
     if a.top is None and (a.rank or a.min_members is not None or a.include_cys or a.one_per_position):
@@ -136,12 +151,14 @@ def main(argv=None) -> int:
     model = load_model(a.model_path or None, a.thermompnn_dir, a.synthetic_weights, precision=a.precision)
     with torch.no_grad():
         res = scan_ensembles(model, ensembles, cutoff=a.cutoff, chunk_residues=a.chunk_residues, align=a.align, reference=a.reference,
-                             min_identity=0.9 if a.min_identity is None else a.min_identity)
+                             min_identity=0.9 if a.min_identity is None else a.min_identity, superpose=a.superpose, fit_to=a.fit_to or 0,
+                             max_rmsd=a.max_rmsd)
         res["ensemble_names"] = names
         if a.top is not None:
             hits: List[list] = select_ensemble_hits(model.engine(), res["stats"], res["seqs"], a.top, a.rank or "mean", a.cutoff,
-                                                    a.include_cys, a.one_per_position, a.min_members)
-            rows = write_ensemble_hits_csv(a.out, hits, names, a.model_name, a.dataset)
+                                                    a.include_cys, a.one_per_position, a.min_members,
+                                                    rmsf=res["superposed"]["rmsf"] if a.superpose else None)
+            rows = write_ensemble_hits_csv(a.out, hits, names, a.model_name, a.dataset, rmsf=a.superpose)
             print(f"{rows} hits of {len(names)} ensembles ({sum(res['members'])} members) -> {a.out}")
             return 0
     if a.out.endswith(".npz"):

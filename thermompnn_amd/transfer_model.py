@@ -174,7 +174,8 @@ class TransferModel(_EngineOwner):
         from .variant_scan import multi_mutant_search_each
         return multi_mutant_search_each(self, pdbs, order, beam, **kw)
 
-    def ensemble_table(self, members, cutoff=None, align: bool = False, reference=None, min_identity: float = 0.9):
+    def ensemble_table(self, members, cutoff=None, align: bool = False, reference=None, min_identity: float = 0.9,
+                       superpose: bool = False, fit_to: int = 0, max_rmsd=None):
         """Per-mutation statistics across the parsed members of ONE conformer ensemble (``pdb_io.parse_pdb_models`` of a multi-MODEL
         file, or one ``alt_parse_PDB`` entry per file), as ``ensemble.EnsembleTable``: mean, spread, lo, hi, lo_member, hi_member,
         count, below, [L, 20] each, on the model's device. One ``tied_featurize``, ONE fused forward over the packed members and ONE
@@ -182,20 +183,28 @@ class TransferModel(_EngineOwner):
         released head configuration with ``subtract_mut``; NotImplementedError otherwise. ``align=True``: members of unequal length are
         aligned on the device to ``reference`` (a sequence string or a one-record FASTA file; default: member 0's sequence) by the
         rule of ``datasets.global_alignment_map`` and the statistics read through that map; the table gains ``aligned`` and
-        ``identity``, and a member below ``min_identity`` raises ValueError (``ensemble.scan_ensembles``)."""
+        ``identity``, and a member below ``min_identity`` raises ValueError (``ensemble.scan_ensembles``). ``superpose=True``: before
+        the forward every member is laid on member ``fit_to`` by the optimal proper rotation of the C-alpha atoms both have
+        (``Engine.superpose``, two small launches); the table gains ``rmsd`` [M], ``n_fit`` [M], ``rmsf`` [L], ``deviation`` [M, L] and
+        ``xform`` [M, 12], and a member whose RMSD exceeds ``max_rmsd`` raises ValueError before any forward. The ddG statistics are
+        the same bits with and without it."""
         from .ensemble import ensemble_table
-        return ensemble_table(self, members, cutoff=cutoff, align=align, reference=reference, min_identity=min_identity)
+        return ensemble_table(self, members, cutoff=cutoff, align=align, reference=reference, min_identity=min_identity, superpose=superpose,
+                              fit_to=fit_to, max_rmsd=max_rmsd)
 
     def ensemble_hits(self, members, k: int, rank: str = "mean", cutoff=None, include_cys: bool = False, one_per_position: bool = False,
-                      min_members=None, align: bool = False, reference=None, min_identity: float = 0.9):
+                      min_members=None, align: bool = False, reference=None, min_identity: float = 0.9, superpose: bool = False,
+                      fit_to: int = 0, max_rmsd=None):
         """The ``k`` most stabilising substitutions of one conformer ensemble, best first, as ``ensemble.EnsembleHit``: the
         statistics of ``ensemble_table`` and ONE selection on the device over the table ``rank`` names — "mean", "worst" (the
         largest ddG over the members: stabilising in every conformer) or "best" (the smallest). ``min_members`` drops entries in
         which fewer members take part; the other options are ``hit_list``'s. Only the hits and their statistics are copied back.
-        ``align``, ``reference``, ``min_identity``: as ``ensemble_table``; positions are then the axis'."""
+        ``align``, ``reference``, ``min_identity``: as ``ensemble_table``; positions are then the axis'. ``superpose``, ``fit_to``,
+        ``max_rmsd``: as ``ensemble_table``; every hit then carries ``rmsf``, the RMSF of its position."""
         from .ensemble import ensemble_hits
         return ensemble_hits(self, members, k, rank=rank, cutoff=cutoff, include_cys=include_cys, one_per_position=one_per_position,
-                             min_members=min_members, align=align, reference=reference, min_identity=min_identity)
+                             min_members=min_members, align=align, reference=reference, min_identity=min_identity, superpose=superpose,
+                             fit_to=fit_to, max_rmsd=max_rmsd)
 
     def _encode_structure(self, entry):
         """One parsed structure -> its EncodedBackbone (Engine.encode: the part of a forward that never reads the sequence)."""
