@@ -1,7 +1,8 @@
 """Fixtures for tmpnn_superpose, shared by tests/test_superpose_host.py and tests/test_gpu_superpose.py, which therefore see the same
 coordinates; no GPU, no torch. Random-walk C-alpha chains of 3.8 A steps stored as fp32, centroids up to 500 A from the origin; the
 members of an ensemble are rotated and translated copies of its chain with coordinate noise of 0, 0.3 and 2.0 A in turn. The other
-three atom slots of X hold NaN in every fourth row: the entry reads slot 1 only."""
+three atom slots of X hold NaN in every fourth row: the entry reads slot 1 only. degenerate(): the fits whose rotation is not unique
+or nearly so, and structurally special ones, for tests/test_gpu_superpose_degenerate.py; centroids out to 9 000 A."""
 import numpy as np
 
 SHAPES = ((1, 19), (2, 3), (3, 70), (17, 257), (5, 1025), (0, 5), (300, 19))   # (M, L): L = 257 and 1 025 leave one column to a second
@@ -142,6 +143,144 @@ def special(seed=23):
     rows[d1:d1 + 40] = np.arange(d1 + 120, d1 + 160)
     return dict(X=X, mask=mask, rows=rows, desc=desc, R=T, T=T, NM=NM, T_out=T_out, max_len=max_len, members=[M for M, _ in shapes],
                 lengths=[L for _, L in shapes], fit_to=list(fit_to), coord=float(np.abs(X[:, 1]).max()), loose=[NM - 1], loose_ensembles=[2])
+
+
+DEGENERATE_SIZES = (3, 4, 19, 257)
+DEGENERATE_LONG = 1025                                                             # the collinear and the planar families only
+LOOSE_FAMILIES = ("collinear", "collinear_noisy", "near_collinear_4", "near_collinear_10", "near_collinear_16", "coincident",
+                  "both_coincident", "inverted_cube", "inverted_tetrahedron", "inverted_near_cube_10", "inverted_near_cube_16",
+                  "inverted_near_cube_22")
+CONDITIONED_FAMILIES = ("half_turn_x", "half_turn_y", "half_turn_z", "half_turn_generic", "far", "inversion", "quarter_turn_z",
+                        "translation", "planar_mirror", "planar_mirror_noisy")
+
+
+def _f32(P):
+    """P rounded to fp32 and back: what a member built from ANOTHER member's stored coordinates starts from."""
+    return np.asarray(P, np.float64).astype(np.float32).astype(np.float64)
+
+
+def _unit(rng):
+    v = rng.standard_normal(3)
+    return v / np.linalg.norm(v)
+
+
+def _line_ensemble(L, rng):
+    """The target: L points at 3.8 A steps on a line of generic direction (fp32 storage leaves it collinear to about 2^-16 A). The
+    members: a moved copy, one with 0.3 A of noise, and moved copies with transverse offsets of 2^-k A, k = 4, 10, 16."""
+    u = _unit(rng)
+    line = chain(1, rng) + 3.8 * np.arange(L)[:, None] * u
+    members, names = [line, moved(line, rng, 0.0), moved(line, rng, 0.3)], ["target", "collinear", "collinear_noisy"]
+    for k in (4, 10, 16):
+        across = np.cross(rng.standard_normal((L, 3)), u)
+        across *= 2.0 ** -k / np.linalg.norm(across, axis=1, keepdims=True)
+        members.append(moved(line + across, rng, 0.0))
+        names.append(f"near_collinear_{k}")
+    return members, names
+
+
+def _generic_ensemble(L, rng):
+    """The target: a chain. The members: every point the same point; the target's stored coordinates turned by 180 degrees about x, y
+    and z (sign changes: exact) and about a generic axis; a copy with 0.3 A of noise whose centroid is 9 000 A out; the inversion of
+    the target through its centroid, moved, with 0.3 A of noise."""
+    P = _f32(chain(L, rng))
+    c = P.mean(axis=0)
+    u = _unit(rng)
+    far = moved(P, rng, 0.3)
+    far += _unit(rng) * 9000.0 - far.mean(axis=0)
+    members = [P, np.repeat(chain(1, rng), L, axis=0), P * np.array([1.0, -1.0, -1.0]), P * np.array([-1.0, 1.0, -1.0]),
+               P * np.array([-1.0, -1.0, 1.0]), (P - c) @ (2.0 * np.outer(u, u) - np.eye(3)).T + c + rng.standard_normal(3) * 30.0, far,
+               moved(2.0 * c - P, rng, 0.3)]
+    return members, ["target", "coincident", "half_turn_x", "half_turn_y", "half_turn_z", "half_turn_generic", "far", "inversion"]
+
+
+def _integer_ensemble(L, rng):
+    """The target: a chain rounded to integer coordinates. The members: (x, y, z) -> (-y, x, z) and an integer shift, both exact."""
+    P = np.round(chain(L, rng))
+    return [P, P[:, [1, 0, 2]] * np.array([-1.0, 1.0, 1.0]), P + np.array([17.0, -230.0, 64.0])], ["target", "quarter_turn_z", "translation"]
+
+
+def _point_ensemble(L, rng):
+    return [np.repeat(_f32(chain(1, rng)), L, axis=0), np.repeat(_f32(chain(1, rng)), L, axis=0)], ["target", "both_coincident"]
+
+
+def _planar_ensemble(L, rng):
+    """The target: a walk of 3.8 A steps in a plane of generic orientation. The members: its mirror image IN that plane (one in-plane
+    coordinate negated about the centroid), moved, without noise and with 0.3 A of noise. Turning the plane over undoes the mirror."""
+    e1 = _unit(rng)
+    e2 = np.cross(e1, _unit(rng))
+    e2 /= np.linalg.norm(e2)
+    ang = rng.uniform(0.0, 2.0 * np.pi, L)
+    uv = np.cumsum(3.8 * np.stack([np.cos(ang), np.sin(ang)], axis=1), axis=0)
+    uv -= uv.mean(axis=0)
+    centre = chain(1, rng)
+    P = centre + uv[:, :1] * e1 + uv[:, 1:] * e2
+    Q = centre + uv[:, :1] * e1 - uv[:, 1:] * e2
+    return [P, moved(Q, rng, 0.0), moved(Q, rng, 0.3)], ["target", "planar_mirror", "planar_mirror_noisy"]
+
+
+def _inverted_solid(corners, centre, name):
+    """``corners`` (half-edge units, exact in fp32) around ``centre`` and their inversion through the centroid, shifted by integers:
+    the centred covariance is diagonal and exact, Horn's matrix is diagonal."""
+    P = np.asarray(corners, np.float64) + np.asarray(centre, np.float64)
+    return [P, 2.0 * np.asarray(centre, np.float64) - P + (np.array([16.0, 32.0, -48.0]) if any(centre) else 0.0)], ["target", name]
+
+
+def degenerate(seed=41):
+    """Fits whose rotation is not unique or nearly so, and structurally special ones, in one batch through the identity map; no
+    holes. One ensemble per (kind of target, size); member 0 is the fit target and every other member belongs to one family.
+      line     L = 3, 4, 19, 257, 1 025   collinear, collinear_noisy, near_collinear_{4, 10, 16}
+      generic  L = 3, 4, 19, 257          coincident, half_turn_{x, y, z, generic}, far, inversion
+      integer  L = 3, 4, 19, 257          quarter_turn_z, translation
+      point    L = 3, 4, 19, 257          both_coincident
+      planar   L = 3, 4, 19, 257, 1 025   planar_mirror, planar_mirror_noisy
+      cube (L = 8), tetrahedron (L = 4), near_cube_{10, 16, 22} (L = 8, edges 1 : 1 + 2^-k : 1 + 2^-k+1, centred at the origin): inverted
+    -> the batch dict of crafted() plus ca [T, 3] float32, names [E], family [NM] ('target' for member 0), loose / conditioned: the
+    member slots of LOOSE_FAMILIES / CONDITIONED_FAMILIES, loose_ensembles, and ensembles: {kind of target: its ensembles}."""
+    rng = np.random.default_rng(seed)
+    built = []
+    for kind, make, sizes in (("line", _line_ensemble, DEGENERATE_SIZES + (DEGENERATE_LONG,)), ("generic", _generic_ensemble, DEGENERATE_SIZES),
+                             ("integer", _integer_ensemble, DEGENERATE_SIZES), ("point", _point_ensemble, DEGENERATE_SIZES),
+                             ("planar", _planar_ensemble, DEGENERATE_SIZES + (DEGENERATE_LONG,))):
+        built += [(kind, L) + make(L, rng) for L in sizes]
+    cube = [(sx, sy, sz) for sx in (-2.0, 2.0) for sy in (-2.0, 2.0) for sz in (-2.0, 2.0)]
+    built.append(("cube", 8) + _inverted_solid(cube, (304.0, -208.0, 96.0), "inverted_cube"))
+    built.append(("tetrahedron", 4) + _inverted_solid([(2.0, 2.0, 2.0), (2.0, -2.0, -2.0), (-2.0, 2.0, -2.0), (-2.0, -2.0, 2.0)],
+                                                      (-176.0, 240.0, 320.0), "inverted_tetrahedron"))
+    for k in (10, 16, 22):
+        edges = np.array([1.0, 1.0 + 2.0 ** -k, 1.0 + 2.0 ** (1 - k)])
+        built.append((f"near_cube_{k}", 8) + _inverted_solid(np.array(cube) * edges, (0.0, 0.0, 0.0), f"inverted_near_cube_{k}"))
+    shapes = tuple((len(members), L) for _, L, members, _ in built)
+    desc, T, NM, T_out, max_len = pack(shapes, (0,) * len(shapes))
+    ca = np.concatenate([np.concatenate(members) for _, _, members, _ in built])
+    family = [name for _, _, _, names in built for name in names]
+    assert ca.shape == (T, 3) and len(family) == NM and set(family) == set(LOOSE_FAMILIES + CONDITIONED_FAMILIES + ("target",))
+    X = backbone(ca, rng)
+    ensembles = {}
+    for e, (kind, _, _, _) in enumerate(built):
+        ensembles.setdefault(kind.rsplit("_", 1)[0] if kind.startswith("near_cube") else kind, []).append(e)
+    loose = [g for g, name in enumerate(family) if name in LOOSE_FAMILIES]
+    return dict(X=X, mask=np.ones(T, np.float32), rows=np.arange(T, dtype=np.int32), desc=desc, R=T, T=T, NM=NM, T_out=T_out,
+                max_len=max_len, members=[M for M, _ in shapes], lengths=[L for _, L in shapes], fit_to=[0] * len(shapes),
+                coord=float(np.abs(X[:, 1]).max()), ca=X[:, 1].copy(), names=[f"{kind}:{L}" for kind, L, _, _ in built], family=family,
+                loose=loose, conditioned=[g for g, name in enumerate(family) if name in CONDITIONED_FAMILIES],
+                loose_ensembles=sorted({e for e, d in enumerate(desc) if set(range(d[4], d[4] + d[1])) & set(loose)}), ensembles=ensembles)
+
+
+def scaled(c, k):
+    """Batch c with every coordinate multiplied by 2^k in fp32 (exact unless it leaves fp32's normal range: the caller checks)."""
+    return dict(c, X=(c["X"] * np.float32(2.0 ** k)).astype(np.float32), coord=c["coord"] * 2.0 ** k)
+
+
+SCALE_ENSEMBLES = ("generic:19", "line:257", "near_cube_10:8", "near_cube_16:8", "near_cube_22:8")
+SCALE_K = (-60, -20, 20, 60)
+
+
+def scale_subset(c):
+    """The ensembles of degenerate() that the power-of-two tests run, as a batch of their own -> (batch, its member slots, output
+    columns and map entries)."""
+    sub, _, _ = subset(c, [c["names"].index(name) for name in SCALE_ENSEMBLES], mem_gap=0)
+    entries = np.concatenate([np.arange(int(d[0]), int(d[0]) + int(d[1]) * int(d[2])) for d in sub["desc"]])
+    return sub, np.arange(sub["NM"]), np.arange(sub["T_out"]), entries
 
 
 def bad_descriptors(c):
