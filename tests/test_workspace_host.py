@@ -6,7 +6,8 @@ from the code under test): every row must still come out, the zeros at and beyon
 their sizers with fake, never dereferenced pointers: one byte less than a pre-checking entry's size is refused with both numbers in
 the message; an entry that takes whatever its carve fits is refused one byte below what the carve takes. tmpnn_sample, the one entry
 with a refusal behind its workspace check (an fp32 handle), also shows the other side on any base alignment; for the others that
-side needs launches and is tests/test_gpu_workspace.py. The range-retry helper of engine.py is tested here with stub callables."""
+side needs launches and is tests/test_gpu_workspace.py, whose table of covered entries is held to include/tmpnn.h here. The
+range-retry helper of engine.py is tested here with stub callables."""
 import ctypes as C
 import json
 import os
@@ -138,6 +139,25 @@ def test_head_and_training_entries_need_exactly_their_size(lib):
     refused_below(lib, ft_fwd, saved)
     refused_below(lib, lambda ws, n: ft_bwd(ws, n, BUF, 1 << 40), saved)
     refused_below(lib, lambda ws, n: ft_bwd(BUF, saved, ws, n), lib.tmpnn_finetune_scratch_bytes(L, M, 2, 1, 3, cd))
+
+
+def test_every_entry_with_a_caller_owned_buffer_has_a_window_test():
+    """include/tmpnn.h: every function with a ``void *`` or ``const void *`` parameter named workspace, saved, scratch, packed or ctx
+    is a key of tests/test_gpu_workspace.py's COVERED table, the table names nothing else, and every test it names exists."""
+    import importlib
+    import re
+    header = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), os.pardir, "include", "tmpnn.h")).read()
+    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    takes_buffer = re.compile(r"\b(?:const\s+)?void\s*\*\s*(?:workspace|saved|scratch|packed|ctx)\b")
+    declared = {name for name, params in re.findall(r"\b(tmpnn_\w+)\s*\(([^;{]*?)\)\s*;", header) if takes_buffer.search(params)}
+    assert len(declared) >= 34 and {"tmpnn_ssm_forward", "tmpnn_weights_create", "tmpnn_seqloss_batch_backward_x"} <= declared
+    covered = importlib.import_module("test_gpu_workspace").COVERED
+    assert sorted(covered) == sorted(declared)
+    for entry, tests in covered.items():
+        assert tests, entry
+        for where in tests:
+            module, test = where.split("::")
+            assert module in ("test_gpu_workspace", "test_gpu_workspace_entries") and callable(getattr(importlib.import_module(module), test)), where
 
 
 # ---- engine.range_retry: the one range contract of ssm_forward, decode_variants, decode_ordered and sample --------------------------
